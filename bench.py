@@ -23,7 +23,13 @@ Synthetic data: 64 unique blocks from the repo's deterministic LZ4
 sequence generator (seed 0x4C5A3441 + i), tiled to size; each rank's shard
 is assembled in host memory and copied to the GPU once.  Golden check:
 per-block XXH32 of every decoded slot (on the GPU) against the generator's
-plaintext hash, after the warmup.
+plaintext hash, after the warmup (with --full).
+
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps, checks every block's status, writes its outputs if --dump-outputs is
+given and prints the result line.  Everything else -- the golden check, the
+two halves timed alone, the content-checksum leg, the other configs, content
+classes, the facade rows and the CPU baselines -- runs only with --full.
 
 Multi-GPU: one process per GPU (torch.distributed, RCCL); blocks shard
 across ranks with no data-path collective.  Timing: barrier +
@@ -84,6 +90,13 @@ def parse_args(argv=None):
                     help="test hook: start the ranks, check the process group (gloo, no GPU), "
                          "print one JSON line")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_decode.json"))
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the golden check of "
+                         "the output, the two halves of the step alone, and (N=1) the content-"
+                         "checksum leg, the other configs, classes, facade rows and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left to DIR/<name>.npy "
+                         "(block statuses, a seeded sample of the decoded bytes)")
     return ap.parse_args(argv)
 
 
@@ -256,6 +269,60 @@ def golden_check(lz4ada, torch, d_status, descs, nb, op, dp, sp, d_hash, exp_has
     got = [h & 0xffffffff for h in d_hash[:nb].cpu().tolist()]
     assert got == exp_hash, f"{what}: decoded output differs from the generator's plaintext"
     return st
+
+
+DUMP_SAMPLE = 8 << 20  # decoded bytes written by --dump-outputs (32 MiB as float32)
+
+
+def sample_positions(torch, out_len, out_off, limit=DUMP_SAMPLE):
+    """Byte positions of the output buffer that --dump-outputs writes, and
+    which of them hold a decoded byte: every valid byte (out_off[i] ..
+    out_off[i] + out_len[i] of each slot, in order) when there are at most
+    `limit`; else `limit` draws of (block, place within its decoded bytes)
+    from a generator seeded with SEED0, ascending.  The same lengths give the
+    same positions in every run."""
+    out_len = torch.tensor(out_len, dtype=torch.int64)
+    out_off = torch.tensor(out_off, dtype=torch.int64)
+    nb = out_len.numel()
+    if int(out_len.sum()) <= limit:
+        blk = torch.repeat_interleave(torch.arange(nb), out_len)
+        first = (out_len.cumsum(0) - out_len)[blk]  # index of each block's first byte in the dump
+        return out_off[blk] + torch.arange(blk.numel()) - first, torch.ones(blk.numel(), dtype=torch.bool)
+    gen = torch.Generator().manual_seed(SEED0)
+    blk = torch.randint(0, nb, (limit,), generator=gen)
+    frac = torch.rand(limit, generator=gen, dtype=torch.float64)
+    pos, order = (out_off[blk] + (frac * out_len[blk]).long()).sort()
+    return pos, (out_len[blk] > 0)[order]
+
+
+def dump_outputs(lz4ada, torch, dirname, d_out, st, descs, nb, dp, sp, d_hash, sh, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as .npy
+    files two builds can be compared by (same arguments, same inputs):
+      status         float64 [nb, 3]: each block's code, out_len and cksum
+                     (the XXH32 of its compressed payload)
+      output_sample  float32: the decoded bytes at DUMP_SAMPLE positions
+                     drawn once from a seeded generator over the valid bytes
+                     of every slot, in ascending order (all of the valid
+                     bytes when there are no more than that); -1 where the
+                     drawn block decoded to nothing
+      output_xxh32   float64 [nb]: XXH32 of each whole decoded slot (computed
+                     on the GPU from the output, after the timed steps), so
+                     bytes outside the sample still count
+    `st` are the statuses of that step, already on the host."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, f"status{suffix}.npy"),
+            np.array([[s.code, s.out_len, s.cksum] for s in st], dtype=np.float64).reshape(nb, 3))
+    pos, valid = sample_positions(torch, [min(s.out_len, descs[i].out_cap) for i, s in enumerate(st)],
+                                  [descs[i].out_off for i in range(nb)])
+    sample = d_out[pos.to(d_out.device)].cpu().to(torch.float32)
+    sample[~valid] = -1.0
+    np.save(os.path.join(dirname, f"output_sample{suffix}.npy"), sample.numpy())
+    lz4ada.output_checksums_device(d_out.data_ptr(), dp, sp, nb, d_hash.data_ptr(), sh)
+    torch.cuda.synchronize()
+    np.save(os.path.join(dirname, f"output_xxh32{suffix}.npy"),
+            (d_hash[:nb].cpu().to(torch.int64) & 0xffffffff).to(torch.float64).numpy())
+    log(f"[bench] outputs written to {dirname}")
 
 
 # --------------------------------------------------------------- CPU baseline
@@ -949,10 +1016,11 @@ def main():
         step()
     torch.cuda.synchronize()
     # ---- golden check (outside the timed region)
-    st = golden_check(lz4ada, torch, d_status, descs, nb, op, dp, sp, d_hash, exp_hash, sh,
-                      "headline")
-    assert sum(s.out_len for s in st) == raw_bytes
-    log("[bench] golden check passed (per-block XXH32 of output, block checksums)")
+    if args.full:
+        st = golden_check(lz4ada, torch, d_status, descs, nb, op, dp, sp, d_hash, exp_hash, sh,
+                          "headline")
+        assert sum(s.out_len for s in st) == raw_bytes
+        log("[bench] golden check passed (per-block XXH32 of output, block checksums)")
 
     # ---- timed region: exactly K steps
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -976,11 +1044,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         local_bad = int(t.item())
     assert local_bad == 0
+    if args.dump_outputs:
+        dump_outputs(lz4ada, torch, args.dump_outputs, d_out, st, descs, nb, dp, sp, d_hash, sh,
+                     f"_rank{rank}" if world > 1 else "")
     # the two halves alone (after the timed region, same stream): what the
-    # overlap hides
-    alone = {}
-    for name, fn in (("block_checksums", lambda: lz4ada.launch_block_checksums(fp, dp, nb, sp, sh)),
-                     ("decode", lambda: lz4ada.launch_decode(fp, frame_len, dp, nb, op, sp, sh))):
+    # overlap hides (--full)
+    halves = (("block_checksums", lambda: lz4ada.launch_block_checksums(fp, dp, nb, sp, sh)),
+              ("decode", lambda: lz4ada.launch_decode(fp, frame_len, dp, nb, op, sp, sh)))
+    alone = {} if args.full else None
+    for name, fn in halves if args.full else ():
         a_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 for _ in range(3)]
         for a, b in a_ev:
@@ -1055,7 +1127,7 @@ def main():
                                "kernel_ms": round(float(t[1].item()), 3)}
                               for r, t in enumerate(allr)]
 
-    extra = world == 1 and rank == 0
+    extra = args.full and world == 1 and rank == 0
     # ---- configs[2] e2e: + frame-wide content XXH32 (one serial chain), run
     # by the D2H + host-chain pipeline (lz4ada_content_xxh32_d2h) the bulk
     # path uses: chunks are hashed while the next one is in flight

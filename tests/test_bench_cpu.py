@@ -75,6 +75,34 @@ def test_assemble_shard_device_tiling(first, nblocks, unique):
     assert eh == [recs[(first + i) % unique][3] for i in range(nblocks)]
 
 
+def test_plain_run_is_the_default():
+    """--full is off unless asked for; --dump-outputs takes the folder."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 3, 1)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_sample_positions():
+    """--dump-outputs' byte positions: all valid bytes of every slot when
+    they fit, else a fixed seeded draw -- inside the decoded part of a slot,
+    ascending, the same in every run, empty blocks flagged."""
+    import torch
+    import bench
+    lens, offs = [5, 0, 3, 7], [0, 16, 32, 48]
+    pos, valid = bench.sample_positions(torch, lens, offs)
+    assert pos.tolist() == [0, 1, 2, 3, 4, 32, 33, 34, 48, 49, 50, 51, 52, 53, 54] and bool(valid.all())
+    pos, valid = bench.sample_positions(torch, lens, offs, limit=10)
+    again = bench.sample_positions(torch, lens, offs, limit=10)
+    assert pos.numel() == 10 and pos.tolist() == sorted(pos.tolist())
+    assert pos.tolist() == again[0].tolist() and valid.tolist() == again[1].tolist()
+    for p, v in zip(pos.tolist(), valid.tolist()):
+        i = p // 16
+        assert (p - offs[i] < lens[i]) if v else (lens[i] == 0 and p == offs[i])
+    assert set(valid.tolist()) == {True, False}  # block 1 is drawn at least once in 10 (seeded)
+
+
 def test_kernel_code_hash_guards_traffic_figure():
     """the PMC traffic figure is reused only while the
     headline kernel's machine code is the one it was measured with -- the

@@ -5,7 +5,7 @@
 #   bash tools/gpu_steps.sh TAG step [step ...]
 #
 #   suite    full `pytest -m gpu` (per-test timeout)
-#   bench    the default bench line                  -> gpurun_out/TAG_bench.json
+#   bench    the whole bench line (bench.py --full)  -> TAG_bench.json in the output folder
 #   trace    rocprofv3 --kernel-trace --stats of the reduced bench (headline only)
 #   pmc      one rocprofv3 --pmc pass per tools/pmc_groups.txt line, same command
 #            (both into gpurun_out/prof_TAG/, as tools/pmc_summary.py reads them)
@@ -33,7 +33,7 @@ for step in "$@"; do
       > $O/${TAG}_suite.log 2>&1 || fail suite $O/${TAG}_suite.log
     tail -2 $O/${TAG}_suite.log ;;
   bench)
-    timeout -k 10 900 python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log || fail bench $O/${TAG}_bench.log
+    timeout -k 10 900 python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log || fail bench $O/${TAG}_bench.log
     cat $O/${TAG}_bench.json ;;
   trace)
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
