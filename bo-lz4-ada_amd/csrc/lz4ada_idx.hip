@@ -91,7 +91,7 @@ __device__ __forceinline__ void vm_wait()
 // waves (each stamp drains the wave's memory counters: read shares).
 enum IdxPhase { I_STAGE, I_WALK0, I_ITER, I_CHUNKS, I_ITERS,
 	            D_STAGE, D_WALK1, D_WALK2, D_TLDS, D_LIT, D_MFAR, D_NEAR, D_FLUSH, D_GLOBAL,
-	            D_BATCHES, D_GBATCHES, D_ROUNDS, D_TASKS, D_LANES, I_STEPS, I_MAXST, IDX_NST };
+	            D_BATCHES, D_GBATCHES, D_ROUNDS, D_TASKS, D_LANES, I_STEPS, I_MAXST, I_LEAD, IDX_NST };
 #ifdef LZ4ADA_IDX_STAMPS
 __device__ unsigned long long g_idx_stamps[IDX_NST];
 #define ISTAMP_DECL uint64_t ist[IDX_NST] = {}; uint64_t ist_t = __builtin_amdgcn_s_memtime()
@@ -378,11 +378,30 @@ __device__ __forceinline__ void gstore_n(g8* dst, u32x4 v, int32_t n)
 
 // ------------------------------------------------------------------ pass 1
 
+// the 16-bit output counts of a lane's records: two to a dword, so the
+// first walk can add into one with a 32-bit LDS add; read and written as
+// halves everywhere else
+typedef uint16_t __attribute__((may_alias)) cnt16;
+typedef uint32_t __attribute__((may_alias)) cnt32;
+
 struct alignas(16) IdxLds {
 	uint8_t buf[CHUNK + 16];       // staged chunk; + mirror of its first 16 bytes
 	uint32_t rbm[64][NSUB + 1];    // each lane's records from its latest walk: start
-	uint16_t rcnt[64][NSUB + 1];   // bitmaps and output bytes (>= 0xFFFF: in HBM)
+	cnt32 rcnt[64][NSUB / 2 + 1];  // bitmaps and output bytes (>= 0xFFFF: in HBM)
 };
+static_assert(sizeof(IdxLds) <= 20480, "8 waves per CU: at most 20 KiB of LDS per wave");
+
+// a lane's counts as halves (record k: half k)
+template <int N>
+__device__ __forceinline__ cnt16* halves(cnt32 (&row)[N])
+{
+	return reinterpret_cast<cnt16*>(row);
+}
+template <int N>
+__device__ __forceinline__ const cnt16* halves(const cnt32 (&row)[N])
+{
+	return reinterpret_cast<const cnt16*>(row);
+}
 
 // Walk the chain from e (an entry at or after this lane's segment start s)
 // over the sequences starting before seg_end; returns the exit (first
@@ -408,7 +427,7 @@ struct alignas(16) IdxLds {
 // a segment.
 template <int NS = NSUB>
 __device__ __forceinline__ int32_t walk_segment(const Src& S, int32_t e, int32_t s, int32_t seg_end,
-                                                int32_t n, uint32_t* rb, uint16_t* rc, uint32_t* ghi,
+                                                int32_t n, uint32_t* rb, cnt16* rc, uint32_t* ghi,
                                                 bool& err, int32_t& epos, int32_t y_old,
                                                 bool may_stop, int32_t& nst)
 {
@@ -487,19 +506,142 @@ __device__ __forceinline__ int32_t walk_segment(const Src& S, int32_t e, int32_t
 	return p;
 }
 
-// The chain position after the sequence at p, for the lead-in walk: only
-// a guess, so no checks, and every length extension taken as one byte (a
-// longer one just makes a wrong guess, which the re-walks fix) -- then the
-// token's dword pair is the one LDS read the step waits for.
-__device__ __forceinline__ int32_t skip_seq(const Src& S, int32_t p)
+// A lane's first walk of a chunk: walk_segment(may_stop = false) from an
+// entry e >= s, leaving exactly the records it would, with the per-step
+// bookkeeping (the sub-segment transition, the zero fill, the merge tests)
+// replaced by two LDS read-modify-writes into rows zeroed up front: the
+// start bit is OR-ed into rb[k], L + ml added to the 16-bit half k of rc
+// (no other lane touches the row, and a wave's LDS operations execute in
+// order).  Positions are buffer offsets (the staged chunk is linear here:
+// byte p at buf[p - S.lo]), so no read wraps; one past the staged bytes
+// returns other LDS contents, which the window test rejects.
+//
+// A sub-segment starts at most 11 sequences the branch-free parse accepts
+// (3 bytes or more each, L <= 269, ml <= 273), so their sum cannot carry
+// out of its half.  The first sequence it rejects (a longer length extension, bytes
+// past the staged window, the block's last sequences, malformed data) ends
+// the adds for its sub-segment: the rest of that sub-segment goes through
+// parse_seq with an exact 32-bit count, stored saturated with the exact
+// value in HBM as walk_segment's put() does.
+template <int NS = NSUB>
+__device__ __forceinline__ int32_t walk_first(const Src& S, int32_t e, int32_t s, int32_t seg_end,
+                                              int32_t n, uint32_t* rb, cnt32* rc, uint32_t* ghi,
+                                              bool& err, int32_t& epos, int32_t& nst)
 {
-	const uint32_t a = uint32_t(p + S.mis) & S.mask;
-	const uint32_t* wa = reinterpret_cast<const uint32_t*>(S.lds + (a & ~3u));
+	static_assert(NS % 2 == 0, "two counts to a dword");
+	nst = 0;
+	err = false;
+	epos = INT32_MAX;
+#pragma unroll
+	for (int k = 0; k < NS; ++k)
+		rb[k] = 0;
+#pragma unroll
+	for (int k = 0; k < NS / 2; ++k)
+		rc[k] = 0;
+	const uint8_t* buf = S.lds;
+	auto pair_at = [&](int32_t P) -> uint32_t {
+		const uint32_t a = uint32_t(P);
+		const uint32_t* wa = reinterpret_cast<const uint32_t*>(buf + (a & ~3u));
+		return __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
+	};
+	const int32_t B = S.lo;
+	const int32_t S0 = s - B, END = seg_end - B;
+	const int32_t LIM8 = min(S.hi, n) - 8 - B;  // the latest x with 8 staged bytes inside the block
+	int32_t P = e - B;                          // e >= s >= S.lo
+	uint32_t w = P < END ? pair_at(P) : 0u;
+	while (P < END) {
+		const uint32_t d = uint32_t(P - S0);
+		const uint32_t k = d >> 5, bit = 1u << (d & 31u);
+		++nst;
+		const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
+		const bool x1 = tk >= 0xf0u, x2 = (tk & 15u) == 15u;
+		const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
+		const int32_t x = P + 1 + (x1 ? 1 : 0) + L;
+		const int32_t np = x + 2 + (x2 ? 1 : 0);
+		// the offset pair at x and the next token pair load together, before
+		// the branch below (left to the compiler, the second read sinks past
+		// it and a step waits for two LDS round trips)
+		const uint32_t w2 = pair_at(x), wn = pair_at(np);
+		asm volatile("" ::"v"(wn));
+		const uint32_t e2 = (w2 >> 16) & 0xffu;
+		const uint32_t c =uint32_t(L) + (tk & 15u) + 4u + (x2 ? e2 : 0u);
+		const bool ok = x <= LIM8 && !(x1 && e1 == 255u) && !(x2 && e2 == 255u) && (w2 & 0xffffu) != 0;
+		if (__builtin_expect(!ok, 0)) {
+			const uint32_t sh = (k & 1u) * 16u;
+			const uint32_t old = (__hip_atomic_load(&rc[k >> 1], __ATOMIC_RELAXED,
+			                                        __HIP_MEMORY_SCOPE_WAVEFRONT) >> sh) & 0xffffu;
+			uint32_t bm = 0, cnt = old;
+			int32_t p = P + B;
+			do {
+				Seq q;
+				if (!parse_seq(S, p, n, q)) {
+					err = true;
+					epos = p;
+					return seg_end;
+				}
+				bm |= 1u << (uint32_t(p - s) & 31u);
+				cnt += uint32_t(q.L + q.ml);
+				p = q.next;
+				if (p < seg_end && uint32_t(p - s) >> 5 == k)
+					++nst;
+				else
+					break;
+			} while (true);
+			__hip_atomic_fetch_or(&rb[k], bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+			__hip_atomic_fetch_add(&rc[k >> 1], (min(cnt, 0xFFFFu) - old) << sh, __ATOMIC_RELAXED,
+			                       __HIP_MEMORY_SCOPE_WAVEFRONT);
+			if (cnt >= 0xFFFFu)
+				ghi[2 * k] = cnt;
+			P = p - B;
+			w = P < END ? pair_at(P) : 0u;
+			continue;
+		}
+		__hip_atomic_fetch_or(&rb[k], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+		__hip_atomic_fetch_add(&rc[k >> 1], c << ((k & 1u) * 16u), __ATOMIC_RELAXED,
+		                       __HIP_MEMORY_SCOPE_WAVEFRONT);
+		P = np;
+		w = wn;
+	}
+	return P + B;
+}
+
+// The chain position after the sequence at buffer offset P (the staged
+// chunk is linear: byte p at buf[p - S.lo]), for the lead-in walk: only a
+// guess, so no checks, and every length extension taken as one byte (a
+// longer one just makes a wrong guess, which the re-walks fix) -- then the
+// token and the byte after it are all a step reads, with no address
+// arithmetic: the lead-in keeps P itself.
+#ifndef LZ4ADA_LEAD_READ
+#define LZ4ADA_LEAD_READ 2  // 0: aligned dword pair + v_alignbyte, 1: one unaligned 16-bit read, 2: two byte reads
+#endif
+__device__ __forceinline__ int32_t skip_seq(const uint8_t* buf, int32_t P)
+{
+#if LZ4ADA_LEAD_READ == 2
+	const uint32_t tk = buf[P], e1 = buf[P + 1];
+#elif LZ4ADA_LEAD_READ == 1
+	typedef uint16_t __attribute__((aligned(1))) u16u;
+	const uint32_t w = *reinterpret_cast<const u16u*>(buf + P);
+	const uint32_t tk = w & 0xffu, e1 = w >> 8;
+#else
+	const uint32_t a = uint32_t(P);
+	const uint32_t* wa = reinterpret_cast<const uint32_t*>(buf + (a & ~3u));
 	const uint32_t w = __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
-	const uint32_t tk = w & 0xffu;
+	const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
+#endif
 	const int32_t x1 = tk >= 0xf0u ? 1 : 0;
-	const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t((w >> 8) & 0xffu) : 0);
-	return p + 3 + x1 + L + ((tk & 15u) == 15u ? 1 : 0);
+	const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
+	return P + 3 + x1 + L + ((tk & 15u) == 15u ? 1 : 0);
+}
+
+// The lead-in of a lane whose segment starts at s > C: from `lead` bytes
+// before s (inside the staged chunk), the first guessed chain position >= s.
+__device__ __forceinline__ int32_t lead_in_walk(const Src& S, int32_t C, int32_t s, int32_t lead)
+{
+	const int32_t S0 = s - S.lo;
+	int32_t P = max(s - lead, C) - S.lo;
+	while (P < S0)
+		P = skip_seq(S.lds, P);
+	return P + S.lo;
 }
 
 __device__ __forceinline__ int32_t lead_in_bytes(int32_t starts)
@@ -592,11 +734,9 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 			// with the true one within ~14 sequences, so by s this one mostly
 			// has, and the re-walk rounds below (most of pass 1's time) are
 			// rarely needed.
-			int32_t p = max(s - lead, C);  // inside the staged chunk
-			while (p < s)
-				p = skip_seq(S, p);
-			ein = p;
+			ein = lead_in_walk(S, C, s, lead);
 		}
+		ISTAMP(I_LEAD);
 		uint32_t* ghi = reinterpret_cast<uint32_t*>(tab + (C >> 5) + NSUB * lane) + 1;
 #ifdef LZ4ADA_IDX_NO_MERGE_STOP
 		constexpr bool no_stop = true;
@@ -606,9 +746,15 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 		int32_t epos = INT32_MAX;
 		bool err = false;
 		int32_t nst = 0;
-		int32_t y = (s < n) ? walk_segment(S, ein, s, seg_end, n, X.rbm[lane], X.rcnt[lane], ghi, err,
-		                                   epos, 0, false, nst)
+#ifdef LZ4ADA_IDX_OLD_FIRST_WALK  // A/B: the first walk by walk_segment
+		int32_t y = (s < n) ? walk_segment(S, ein, s, seg_end, n, X.rbm[lane], halves(X.rcnt[lane]), ghi,
+		                                   err, epos, 0, false, nst)
 		                    : ein;
+#else
+		int32_t y = (s < n) ? walk_first(S, ein, s, seg_end, n, X.rbm[lane], X.rcnt[lane], ghi, err, epos,
+		                                 nst)
+		                    : ein;
+#endif
 		ISTAMP(I_WALK0);
 		ICOUNT(I_STEPS, __shfl(wave_incl_scan(nst), 63));
 		ICOUNT(I_MAXST, __shfl(wave_incl_max(nst), 63));
@@ -624,8 +770,8 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 			if (changed) {
 				ein = prev;
 				if (s < n) {
-					y = walk_segment(S, ein, s, seg_end, n, X.rbm[lane], X.rcnt[lane], ghi, err, epos, y,
-					                 !err && !no_stop, nst);
+					y = walk_segment(S, ein, s, seg_end, n, X.rbm[lane], halves(X.rcnt[lane]), ghi, err,
+					                 epos, y, !err && !no_stop, nst);
 				} else {
 					y = ein;
 					err = false;
@@ -647,7 +793,7 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 		for (int i = 0; i < NSUB; ++i) {
 			const int32_t r = 64 * i + lane, sg = r / NSUB, sb = r & (NSUB - 1);
 			if (C + SEG * sg < n) {
-				const uint32_t bmv = X.rbm[sg][sb], c16 = X.rcnt[sg][sb];
+				const uint32_t bmv = X.rbm[sg][sb], c16 = halves(X.rcnt[sg])[sb];
 				starts += __popc(bmv);
 				if (c16 != 0xFFFFu)
 					tab[(C >> 5) + r] = uint64_t(bmv) | (uint64_t(c16) << 32);
@@ -2265,7 +2411,7 @@ constexpr int32_t LEAD_SEQ2 = LZ4ADA_LEAD_SEQ2;
 struct alignas(16) IdxLds2 {
 	uint8_t buf[CHUNK + 16];
 	uint32_t rbm[128][NSUB2 + 1];
-	uint16_t rcnt[128][NSUB2 + 1];
+	cnt32 rcnt[128][NSUB2 / 2 + 1];
 	int32_t xa;        // wave 0's largest exit (wave 1's lane-0 entry)
 	int32_t xs[2][4];  // per wave: largest exit, sequence starts, bad, used sub-segments
 };
@@ -2342,18 +2488,21 @@ __device__ __forceinline__ void index_block2(IdxLds2& X, const uint8_t* __restri
 		const int32_t seg_end = min(s + SEG2, n);
 		int32_t ein = (tid == 0) ? E : s;
 		if (tid > 0 && s < n) {  // lead-in (index_block)
-			int32_t p = max(s - lead, C);
-			while (p < s)
-				p = skip_seq(S, p);
-			ein = p;
+			ein = lead_in_walk(S, C, s, lead);
 		}
 		uint32_t* ghi = reinterpret_cast<uint32_t*>(tab + (C >> 5) + NSUB2 * tid) + 1;
 		int32_t epos = INT32_MAX;
 		bool err = false;
 		int32_t nst = 0;
-		int32_t y = (s < n) ? walk_segment<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], X.rcnt[tid], ghi, err,
-		                                          epos, 0, false, nst)
+#ifdef LZ4ADA_IDX_OLD_FIRST_WALK
+		int32_t y = (s < n) ? walk_segment<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], halves(X.rcnt[tid]), ghi,
+		                                          err, epos, 0, false, nst)
 		                    : ein;
+#else
+		int32_t y = (s < n) ? walk_first<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], X.rcnt[tid], ghi, err,
+		                                        epos, nst)
+		                    : ein;
+#endif
 		// this wave's lane-0 entry: exact for wave 0, wave 1's lead-in guess
 		// until wave 0's largest exit is known
 		int32_t e0 = __shfl(ein, 0);
@@ -2368,8 +2517,8 @@ __device__ __forceinline__ void index_block2(IdxLds2& X, const uint8_t* __restri
 				if (changed) {
 					ein = prev;
 					if (s < n) {
-						y = walk_segment<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], X.rcnt[tid], ghi, err,
-						                        epos, y, !err, nst);
+						y = walk_segment<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], halves(X.rcnt[tid]), ghi,
+						                        err, epos, y, !err, nst);
 					} else {
 						y = ein;
 						err = false;
@@ -2399,7 +2548,7 @@ __device__ __forceinline__ void index_block2(IdxLds2& X, const uint8_t* __restri
 		for (int i = 0; i < NSUB2; ++i) {
 			const int32_t r = 64 * i + lane, sg = 64 * w + r / NSUB2, sb = r & (NSUB2 - 1);
 			if (C + SEG2 * sg < n) {
-				const uint32_t bmv = X.rbm[sg][sb], c16 = X.rcnt[sg][sb];
+				const uint32_t bmv = X.rbm[sg][sb], c16 = halves(X.rcnt[sg])[sb];
 				starts += __popc(bmv);
 				if (c16 != 0xFFFFu)
 					tab[(C >> 5) + 256 * w + r] = uint64_t(bmv) | (uint64_t(c16) << 32);

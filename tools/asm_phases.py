@@ -1,44 +1,98 @@
 #!/usr/bin/env python3
-"""Static instruction counts of k_decode_idx by decode_block phase (the
-call-site line inside decode_block / index_block from each .loc's inline
-chain) in a -gline-tables-only device assembly:
-    python tools/asm_phases.py /tmp/idxg.s"""
-import re, sys, collections
-PH = [(487, 655, 'pass1'), (1339, 1430, 'setup'), (1431, 1476, 'stage+cut'), (1477, 1509, 'global'),
-      (1510, 1529, 'starts'), (1530, 1574, 'P parse'), (1575, 1653, 'HBM loads'),
-      (1654, 1697, 'literals'), (1698, 1761, 'HBM stores'), (1762, 1787, 'ring'),
-      (1788, 1805, 'flush'), (1805, 1830, 'end')]
-def phase(line):
-    for a, b, n in PH:
-        if a <= line <= b:
-            return n
-    return 'other:%d' % line
-path = sys.argv[1]
-lines = open(path).read().split('\n')
-start = next(i for i, l in enumerate(lines) if re.match(r'^_ZN6lz4ada3idx12k_decode_idxE\w*:', l))
-cnt = collections.defaultdict(collections.Counter)
-cur = 'none'
-for l in lines[start:]:
-    if l.startswith('.Lfunc_end'):
-        break
-    m = re.match(r'\s*\.loc\s+\d+\s+\d+.*?;\s*(.*)$', l)
-    if m:
-        chain = re.findall(r'lz4ada_idx\.hip:(\d+)', m.group(1))
-        chain = [int(x) for x in chain]
-        inner = [x for x in chain if not (1837 <= x <= 1889)]
-        cur = phase(inner[-1]) if inner else 'kernel'
-        continue
-    s = l.strip()
-    if not s or s.startswith(('.', ';')) or s.endswith(':'):
-        continue
-    op = s.split()[0]
-    c = cnt[cur]
-    c['all'] += 1
-    if op.startswith('v_'): c['valu'] += 1
-    elif op.startswith(('s_cbranch', 's_branch')): c['br'] += 1
-    elif op.startswith('s_waitcnt') or op.startswith('s_nop'): c['wait'] += 1
-    elif op.startswith('s_'): c['salu'] += 1
-    elif op.startswith('ds_'): c['lds'] += 1
-    elif op.startswith(('global_', 'buffer_', 'flat_')): c['vmem'] += 1
-for k, c in sorted(cnt.items(), key=lambda kv: -kv[1]['all']):
-    print(f"{k:14s} {c['all']:6d} v{c['valu']:5d} s{c['salu']:5d} br{c['br']:4d} w{c['wait']:4d} lds{c['lds']:4d} vm{c['vmem']:4d}")
+"""Static instruction counts of k_decode_idx by phase, from a
+-gline-tables-only device assembly:
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Ibo-lz4-ada_amd/csrc \
+        -mllvm -amdgpu-sched-strategy=iterative-ilp -gline-tables-only -S \
+        --cuda-device-only -o /tmp/idxg.s bo-lz4-ada_amd/csrc/lz4ada_idx.hip
+    python tools/asm_phases.py /tmp/idxg.s
+
+An instruction belongs to the call-site line inside decode_block or
+index_block that its .loc's inline chain leads to.  The phases are the
+stretches between the ISTAMP() marks of those two functions, read from the
+source, so they follow the file as it changes: pass 1's stage / lead-in /
+first walk / re-walk / table write (index_block) and pass 2's phases
+(decode_block), named as tools/idx_stamps.py names their cycles."""
+import collections
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "bo-lz4-ada_amd", "csrc", "lz4ada_idx.hip")
+P1_NAMES = {"I_STAGE": "p1 stage", "I_LEAD": "p1 lead-in", "I_WALK0": "p1 first walk",
+            "I_ITER": "p1 re-walk"}
+
+
+def func_range(src, name):
+    """(first, last) 1-based lines of the definition of `name`: from its
+    header to the closing brace in column 0."""
+    a = next(i for i, l in enumerate(src) if re.match(r"^__(device|global)__ .*\b%s\(" % name, l))
+    b = next(i for i in range(a, len(src)) if src[i].startswith("}"))
+    return a + 1, b + 1
+
+
+def phases(src):
+    """[(first line, last line, name)] of index_block and decode_block."""
+    ph = []
+    for fn, tail, names in (("index_block", "p1 table write", P1_NAMES), ("decode_block", "end", {})):
+        a, b = func_range(src, fn)
+        cur = a
+        for i in range(a, b + 1):
+            m = re.search(r"\bISTAMP\((\w+)\)", src[i - 1])
+            if m:
+                ph.append((cur, i, names.get(m.group(1), m.group(1))))
+                cur = i + 1
+        ph.append((cur, b, tail))
+    return ph
+
+
+def main():
+    src = open(SRC).read().split("\n")
+    ph = phases(src)
+    kern = func_range(src, "k_decode_idx")
+
+    def phase(line):
+        for a, b, n in ph:
+            if a <= line <= b:
+                return n
+        return "other:%d" % line
+
+    lines = open(sys.argv[1]).read().split("\n")
+    start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN6lz4ada3idx12k_decode_idxE\w*:", l))
+    cnt = collections.defaultdict(collections.Counter)
+    cur = "none"
+    for l in lines[start:]:
+        if l.startswith(".Lfunc_end"):
+            break
+        m = re.match(r"\s*\.loc\s+\d+\s+\d+.*?;\s*(.*)$", l)
+        if m:
+            chain = [int(x) for x in re.findall(r"lz4ada_idx\.hip:(\d+)", m.group(1))]
+            inner = [x for x in chain if not kern[0] <= x <= kern[1]]
+            cur = phase(inner[-1]) if inner else "kernel"
+            continue
+        s = l.strip()
+        if not s or s.startswith((".", ";")) or s.endswith(":"):
+            continue
+        op = s.split()[0]
+        c = cnt[cur]
+        c["all"] += 1
+        if op.startswith("v_"):
+            c["valu"] += 1
+        elif op.startswith(("s_cbranch", "s_branch")):
+            c["br"] += 1
+        elif op.startswith("s_waitcnt") or op.startswith("s_nop"):
+            c["wait"] += 1
+        elif op.startswith("s_"):
+            c["salu"] += 1
+        elif op.startswith("ds_"):
+            c["lds"] += 1
+        elif op.startswith(("global_", "buffer_", "flat_")):
+            c["vmem"] += 1
+    for k, c in sorted(cnt.items(), key=lambda kv: -kv[1]["all"]):
+        print(f"{k:16s} {c['all']:6d} v{c['valu']:5d} s{c['salu']:5d} br{c['br']:4d} w{c['wait']:4d} "
+              f"lds{c['lds']:4d} vm{c['vmem']:4d}")
+
+
+if __name__ == "__main__":
+    main()
