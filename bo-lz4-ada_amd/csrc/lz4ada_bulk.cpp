@@ -402,9 +402,11 @@ int lz4ada_launch_decode_variant(const void* d_frame, uint64_t frame_len,
 // Test-only (lz4ada_hip.h): k_index alone into a scratch table, copied out.
 int lz4ada_index_table_debug(const void* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_descs,
                              int64_t nblocks, void* host_out, int64_t host_cap,
-                             lz4ada_block_status* d_status, void* stream)
+                             lz4ada_block_status* d_status, void* stream, int waves)
 {
 	return guarded(nullptr, [&] {
+		if (waves != 1 && waves != 2)
+			raise(LZ4ADA_CONSTRAINT_ERROR, "pass 1 runs on one or two waves per block");
 		const size_t bytes = index_table_bytes(frame_len, uint32_t(nblocks));
 		if (nblocks < 0 || host_cap < 0 || size_t(host_cap) < bytes)
 			raise(LZ4ADA_CONSTRAINT_ERROR, "index table larger than the host buffer");
@@ -420,7 +422,7 @@ int lz4ada_index_table_debug(const void* d_frame, uint64_t frame_len, const lz4a
 		HIP_OK(hipMalloc(&tab.p, bytes));
 		HIP_OK(hipMemsetAsync(tab.p, 0, bytes, s));
 		HIP_OK(launch_index(static_cast<const uint8_t*>(d_frame), frame_len, d_descs, uint32_t(nblocks),
-		                    static_cast<uint8_t*>(tab.p), d_status, s));
+		                    static_cast<uint8_t*>(tab.p), d_status, s, waves));
 		HIP_OK(hipStreamSynchronize(s));
 		HIP_OK(hipMemcpy(host_out, tab.p, bytes, hipMemcpyDeviceToHost));
 	});

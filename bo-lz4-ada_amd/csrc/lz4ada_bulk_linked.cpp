@@ -160,8 +160,8 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 		hipStream_t side = stream;
 		if (!serial)
 			HIP_OK(side_fork(stream, &side));
-		HIP_OK(launch_decode_idx_tab(d_frame, frame_len, d_desc.p, nb, tab.p, bz.p, sz.p, 6, side));
-		HIP_OK(launch_decode_idx_tab(d_frame, frame_len, d_desc.p, nb, tab.p, bx.p, sx.p, 2, stream));
+		HIP_OK(launch_decode_idx_tab(d_frame, frame_len, d_desc.p, nb, tab.p, bz.p, sz.p, IdxMode::LINKED_ZL, side));
+		HIP_OK(launch_decode_idx_tab(d_frame, frame_len, d_desc.p, nb, tab.p, bx.p, sx.p, IdxMode::LINKED_LK, stream));
 		HIP_OK(launch_decode_pc(d_frame, frame_len, d_desc.p, nb, bx.p, sx.p, 1, LINK_HIST, stream));
 		HIP_OK(side_join(stream));  // plane z and the checksums
 		phase("decodes");
@@ -272,7 +272,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 				lz4ada_block_status* const s_dev = sz.p;
 				HIP_OK(hipMemcpyAsync(s_dev, s3.data(), sbn, hipMemcpyHostToDevice, stream));
 				uint8_t* buf = k == 0 ? py : ph;
-				HIP_OK(launch_decode_idx_tab(d_frame, frame_len, d_desc.p, nb, tab.p, buf, s_dev, 2, stream));
+				HIP_OK(launch_decode_idx_tab(d_frame, frame_len, d_desc.p, nb, tab.p, buf, s_dev, IdxMode::LINKED_LK, stream));
 				HIP_OK(launch_decode_pc(d_frame, frame_len, d_desc.p, nb, buf, s_dev, 1, LINK_HIST, stream));
 				s_plane[k].resize(nb);
 				d2h(s_plane[k].data(), s_dev, sbn, stream);

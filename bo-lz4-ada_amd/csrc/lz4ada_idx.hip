@@ -47,10 +47,8 @@ namespace idx {
 #ifndef LZ4ADA_STORED_NT
 #define LZ4ADA_STORED_NT 2
 #endif
-constexpr int SEG = 256;            // pass-1 segment per lane
-constexpr int CHUNK = 64 * SEG;     // pass-1 staged chunk (16 KiB)
+constexpr int CHUNK = 16384;        // pass-1 staged chunk (16 KiB)
 constexpr int SUB = 32;             // pass-2 sub-segment per lane
-constexpr int NSUB = SEG / SUB;     // index records per segment
 constexpr int BATCH = 64 * SUB;     // pass-2 batch (2 KiB of input)
 constexpr int RING = 4 * BATCH;     // pass-2 staging ring
 constexpr int LONG = 256;           // runs longer than this are copied by the whole wave
@@ -384,12 +382,27 @@ __device__ __forceinline__ void gstore_n(g8* dst, u32x4 v, int32_t n)
 typedef uint16_t __attribute__((may_alias)) cnt16;
 typedef uint32_t __attribute__((may_alias)) cnt32;
 
-struct alignas(16) IdxLds {
-	uint8_t buf[CHUNK + 16];       // staged chunk; + mirror of its first 16 bytes
-	uint32_t rbm[64][NSUB + 1];    // each lane's records from its latest walk: start
-	cnt32 rcnt[64][NSUB / 2 + 1];  // bitmaps and output bytes (>= 0xFFFF: in HBM)
+// Pass 1 runs on the W waves of a block's workgroup (1: k_index and
+// k_decode_idx; 2: k_decode_pp2): 64 * W lanes share each staged chunk.
+template <int W>
+struct Pass1 {
+	static_assert(W == 1 || W == 2, "one or two waves per block");
+	static constexpr int SEG = CHUNK / (64 * W);  // segment per lane
+	static constexpr int NSUB = SEG / SUB;        // index records per segment
+	static constexpr int STRIDE = 16 * 64 * W;    // bytes one 16-byte load per thread covers
+	static constexpr int PF = CHUNK / STRIDE;     // 16-byte loads per thread per chunk
 };
-static_assert(sizeof(IdxLds) <= 20480, "8 waves per CU: at most 20 KiB of LDS per wave");
+
+template <int W>
+struct alignas(16) IdxLds {
+	uint8_t buf[CHUNK + 16];                     // staged chunk; + mirror of its first 16 bytes
+	uint32_t rbm[64 * W][Pass1<W>::NSUB + 1];    // each lane's records from its latest walk: start
+	cnt32 rcnt[64 * W][Pass1<W>::NSUB / 2 + 1];  // bitmaps and output bytes (>= 0xFFFF: in HBM)
+	// the exchange words of two waves (no bytes with one)
+	int32_t xa[W - 1];        // wave 0's largest exit (wave 1's lane-0 entry)
+	int32_t xs[W - 1][2][4];  // per wave: largest exit, sequence starts, bad, used sub-segments
+};
+static_assert(sizeof(IdxLds<1>) <= 20480, "8 waves per CU: at most 20 KiB of LDS per wave");
 
 // a lane's counts as halves (record k: half k)
 template <int N>
@@ -410,7 +423,7 @@ __device__ __forceinline__ const cnt16* halves(const cnt32 (&row)[N])
 // entry that is just a dead chain, and a -1 would poison every lane after
 // it one iteration at a time.
 //
-// Every walk rewrites the segment's NSUB records (sub-segment k = bytes
+// Every walk rewrites the segment's NS records (sub-segment k = bytes
 // [s + 32k, s + 32k + 32)) in LDS: rb[k] bit j = a sequence starts at byte
 // j, rc[k] = the output bytes (literals + match) of the sequences starting
 // there.  The lane's last walk -- from the true entry -- leaves the exact
@@ -425,7 +438,7 @@ __device__ __forceinline__ const cnt16* halves(const cnt32 (&row)[N])
 // stops: later records and the exit are the previous walk's.  Chains from a
 // wrong entry merge within ~14 sequences, so a re-walk costs a fraction of
 // a segment.
-template <int NS = NSUB>
+template <int NS>
 __device__ __forceinline__ int32_t walk_segment(const Src& S, int32_t e, int32_t s, int32_t seg_end,
                                                 int32_t n, uint32_t* rb, cnt16* rc, uint32_t* ghi,
                                                 bool& err, int32_t& epos, int32_t y_old,
@@ -523,7 +536,7 @@ __device__ __forceinline__ int32_t walk_segment(const Src& S, int32_t e, int32_t
 // the adds for its sub-segment: the rest of that sub-segment goes through
 // parse_seq with an exact 32-bit count, stored saturated with the exact
 // value in HBM as walk_segment's put() does.
-template <int NS = NSUB>
+template <int NS>
 __device__ __forceinline__ int32_t walk_first(const Src& S, int32_t e, int32_t s, int32_t seg_end,
                                               int32_t n, uint32_t* rb, cnt32* rc, uint32_t* ghi,
                                               bool& err, int32_t& epos, int32_t& nst)
@@ -611,23 +624,9 @@ __device__ __forceinline__ int32_t walk_first(const Src& S, int32_t e, int32_t s
 // longer one just makes a wrong guess, which the re-walks fix) -- then the
 // token and the byte after it are all a step reads, with no address
 // arithmetic: the lead-in keeps P itself.
-#ifndef LZ4ADA_LEAD_READ
-#define LZ4ADA_LEAD_READ 2  // 0: aligned dword pair + v_alignbyte, 1: one unaligned 16-bit read, 2: two byte reads
-#endif
 __device__ __forceinline__ int32_t skip_seq(const uint8_t* buf, int32_t P)
 {
-#if LZ4ADA_LEAD_READ == 2
 	const uint32_t tk = buf[P], e1 = buf[P + 1];
-#elif LZ4ADA_LEAD_READ == 1
-	typedef uint16_t __attribute__((aligned(1))) u16u;
-	const uint32_t w = *reinterpret_cast<const u16u*>(buf + P);
-	const uint32_t tk = w & 0xffu, e1 = w >> 8;
-#else
-	const uint32_t a = uint32_t(P);
-	const uint32_t* wa = reinterpret_cast<const uint32_t*>(buf + (a & ~3u));
-	const uint32_t w = __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
-	const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
-#endif
 	const int32_t x1 = tk >= 0xf0u ? 1 : 0;
 	const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
 	return P + 3 + x1 + L + ((tk & 15u) == 15u ? 1 : 0);
@@ -650,23 +649,31 @@ __device__ __forceinline__ int32_t lead_in_bytes(int32_t starts)
 	return __builtin_amdgcn_readfirstlane(min(max(l, LEAD_MIN), LEAD_MAX));
 }
 
-// Pass 1 of block b (the body of k_index; k_decode_idx mode 3 runs it
-// before pass 2 of the same block).
-__device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict__ frame,
+// Pass 1 of block b by the W waves of its workgroup (the body of k_index;
+// the fused kernels run it before pass 2 of the same block: k_decode_idx
+// with one wave, k_decode_pp2 with two).  With two waves, 128 lanes walk
+// each chunk, 128 bytes each: wave 0's lane 0 enters at the exact chain
+// position, wave 1's lane 0 at its lead-in guess until wave 0's exit is
+// known (one LDS exchange per chunk), and the chunk's totals are combined
+// through LDS; one wave keeps everything in registers.
+template <int W>
+__device__ __forceinline__ void index_block(IdxLds<W>& X, const uint8_t* __restrict__ frame,
                                             uint64_t frame_len,
                                             const lz4ada_block_desc* __restrict__ desc, uint32_t b,
                                             uint8_t* __restrict__ tab_all,
                                             lz4ada_block_status* __restrict__ status)
 {
-	const int32_t lane = int32_t(lane_id());
+	constexpr int SEG = Pass1<W>::SEG, NSUB = Pass1<W>::NSUB, PF = Pass1<W>::PF, STRIDE = Pass1<W>::STRIDE;
+	const int32_t tid = int32_t(threadIdx.x) & (64 * W - 1);  // thread of the block's workgroup
+	const int32_t w = tid >> 6, lane = tid & 63;               // its wave, its lane
 	const lz4ada_block_desc d = desc[b];
 	if (d.flags & LZ4ADA_BLOCK_STORED) {
-		if (lane == 0)
+		if (tid == 0)
 			status[b].code = DS_OK;
 		return;
 	}
 	if (d.in_len >= RLE_MIN_IN && uint64_t(d.in_len) * RLE_RATIO < uint64_t(d.out_cap)) {
-		if (lane == 0)
+		if (tid == 0)
 			status[b].code = DS_SPARSE;
 		return;
 	}
@@ -683,21 +690,21 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 	S.in = in;
 	S.lim = lim;
 
-	// 16 KiB chunk at aligned address a (lanes: 16 x 16 bytes each), the
+	// 16 KiB chunk at aligned address a (threads: PF x 16 bytes each), the
 	// next one loaded while the current one is walked
-	auto load16k = [&](uintptr_t a, u32x4 (&v)[CHUNK / 1024]) {
+	auto load16k = [&](uintptr_t a, u32x4 (&v)[PF]) {
 		if (a + CHUNK <= lim) {
 #pragma unroll
-			for (int r = 0; r < CHUNK / 1024; ++r)
-				__builtin_memcpy(&v[r], reinterpret_cast<cg8*>(a + uintptr_t(1024 * r + 16 * lane)), 16);
+			for (int r = 0; r < PF; ++r)
+				__builtin_memcpy(&v[r], reinterpret_cast<cg8*>(a + uintptr_t(STRIDE * r + 16 * tid)), 16);
 		} else {
 #pragma unroll
-			for (int r = 0; r < CHUNK / 1024; ++r)
-				v[r] = gload16(a + uintptr_t(1024 * r + 16 * lane), lim);
+			for (int r = 0; r < PF; ++r)
+				v[r] = gload16(a + uintptr_t(STRIDE * r + 16 * tid), lim);
 		}
 	};
 	const uintptr_t abase = reinterpret_cast<uintptr_t>(in) - uintptr_t(mis);
-	u32x4 pf[CHUNK / 1024];
+	u32x4 pf[PF];
 	if (n > 0)
 		load16k(abase, pf);
 
@@ -709,9 +716,9 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 	for (int32_t C = 0; C < n && !bad; C += CHUNK) {
 		// stage block-relative [C - mis, C - mis + CHUNK) (16-byte aligned addresses)
 #pragma unroll
-		for (int r = 0; r < CHUNK / 1024; ++r)
-			*reinterpret_cast<u32x4*>(&X.buf[1024 * r + 16 * lane]) = pf[r];
-		if (lane == 0)
+		for (int r = 0; r < PF; ++r)
+			*reinterpret_cast<u32x4*>(&X.buf[STRIDE * r + 16 * tid]) = pf[r];
+		if (tid == 0)
 			*reinterpret_cast<u32x4*>(&X.buf[CHUNK]) = pf[0];
 		__syncthreads();
 		if (C + CHUNK < n)
@@ -721,14 +728,14 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 		ISTAMP(I_STAGE);
 		ICOUNT(I_CHUNKS, 1);
 
-		const int32_t s = C + SEG * lane;
+		const int32_t s = C + SEG * tid;
 		const int32_t seg_end = min(s + SEG, n);
 		// Entry of lane i = max exit of lanes < i (lane 0: the exact entry E).
 		// True exits never decrease along the chunk, so the fixed point is
 		// the true chain, and a run of segments a long sequence jumps over
 		// is crossed in one step instead of one iteration per segment.
-		int32_t ein = (lane == 0) ? E : s;
-		if (lane > 0 && s < n) {
+		int32_t ein = (tid == 0) ? E : s;
+		if (tid > 0 && s < n) {
 			// Lead-in: walk from OV bytes before the segment to find a
 			// likelier entry than s itself -- chains from a wrong start merge
 			// with the true one within ~14 sequences, so by s this one mostly
@@ -737,61 +744,70 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 			ein = lead_in_walk(S, C, s, lead);
 		}
 		ISTAMP(I_LEAD);
-		uint32_t* ghi = reinterpret_cast<uint32_t*>(tab + (C >> 5) + NSUB * lane) + 1;
-#ifdef LZ4ADA_IDX_NO_MERGE_STOP
-		constexpr bool no_stop = true;
-#else
-		constexpr bool no_stop = false;
-#endif
+		uint32_t* ghi = reinterpret_cast<uint32_t*>(tab + (C >> 5) + NSUB * tid) + 1;
 		int32_t epos = INT32_MAX;
 		bool err = false;
 		int32_t nst = 0;
-#ifdef LZ4ADA_IDX_OLD_FIRST_WALK  // A/B: the first walk by walk_segment
-		int32_t y = (s < n) ? walk_segment(S, ein, s, seg_end, n, X.rbm[lane], halves(X.rcnt[lane]), ghi,
-		                                   err, epos, 0, false, nst)
+		int32_t y = (s < n) ? walk_first<NSUB>(S, ein, s, seg_end, n, X.rbm[tid], X.rcnt[tid], ghi, err,
+		                                       epos, nst)
 		                    : ein;
-#else
-		int32_t y = (s < n) ? walk_first(S, ein, s, seg_end, n, X.rbm[lane], X.rcnt[lane], ghi, err, epos,
-		                                 nst)
-		                    : ein;
-#endif
 		ISTAMP(I_WALK0);
 		ICOUNT(I_STEPS, __shfl(wave_incl_scan(nst), 63));
 		ICOUNT(I_MAXST, __shfl(wave_incl_max(nst), 63));
-		for (int it = 0; it < 64; ++it) {
-			int32_t prev = __shfl_up(wave_incl_max(y), 1);
-			if (lane == 0)
-				prev = E;
-			const bool changed = prev != ein;
-			if (!__any(changed))
-				break;
-			ICOUNT(I_ITERS, 1);
-			nst = 0;
-			if (changed) {
-				ein = prev;
-				if (s < n) {
-					y = walk_segment(S, ein, s, seg_end, n, X.rbm[lane], halves(X.rcnt[lane]), ghi, err,
-					                 epos, y, !err && !no_stop, nst);
-				} else {
-					y = ein;
-					err = false;
+		// this wave's lane-0 entry: the exact one, but for wave 1 its lead-in
+		// guess until wave 0's largest exit is known
+		int32_t e0 = E;
+		if constexpr (W == 2)
+			e0 = __shfl(ein, 0);
+		auto converge = [&]() {
+			for (int it = 0; it < 64; ++it) {
+				int32_t prev = __shfl_up(wave_incl_max(y), 1);
+				if (lane == 0)
+					prev = e0;
+				const bool changed = prev != ein;
+				if (!__any(changed))
+					break;
+				ICOUNT(I_ITERS, 1);
+				nst = 0;
+				if (changed) {
+					ein = prev;
+					if (s < n) {
+						y = walk_segment<NSUB>(S, ein, s, seg_end, n, X.rbm[tid], halves(X.rcnt[tid]), ghi,
+						                       err, epos, y, !err, nst);
+					} else {
+						y = ein;
+						err = false;
+					}
+				}
+				ICOUNT(I_STEPS, __shfl(wave_incl_scan(nst), 63));
+				ICOUNT(I_MAXST, __shfl(wave_incl_max(nst), 63));
+			}
+		};
+		converge();
+		if constexpr (W == 2) {
+			const int32_t mx = __shfl(wave_incl_max(y), 63);
+			if (tid == 0)
+				X.xa[0] = mx;
+			__syncthreads();
+			if (w == 1) {
+				const int32_t ea = X.xa[0];
+				if (ea != e0) {  // the guess missed: the lanes it reached walk again
+					e0 = ea;
+					converge();
 				}
 			}
-			ICOUNT(I_STEPS, __shfl(wave_incl_scan(nst), 63));
-			ICOUNT(I_MAXST, __shfl(wave_incl_max(nst), 63));
 		}
 		ISTAMP(I_ITER);
 		// converged: every entry is the true chain position, and every
 		// lane's records are those of its last walk: to HBM, coalesced
-		if (s < n && err)
-			bad = true;
-
-		bad = __any(bad);
+		bad = __any(s < n && err);
 		wave_lds_fence();
 		int32_t starts = 0;  // sequence starts in this chunk (sizes the next lead-in)
 #pragma unroll
 		for (int i = 0; i < NSUB; ++i) {
-			const int32_t r = 64 * i + lane, sg = r / NSUB, sb = r & (NSUB - 1);
+			// this wave's record q (segment sg, sub-segment sb), the chunk's record r
+			const int32_t q = 64 * i + lane, sg = 64 * w + q / NSUB, sb = q & (NSUB - 1);
+			const int32_t r = W == 2 ? q + 256 * w : q;
 			if (C + SEG * sg < n) {
 				const uint32_t bmv = X.rbm[sg][sb], c16 = halves(X.rcnt[sg])[sb];
 				starts += __popc(bmv);
@@ -801,38 +817,58 @@ __device__ __forceinline__ void index_block(IdxLds& X, const uint8_t* __restrict
 					*reinterpret_cast<uint32_t*>(tab + (C >> 5) + r) = bmv;
 			}
 		}
+		// Sparse chains (over 64 input bytes per sequence: long literal
+		// runs) defeat the speculative walks -- every segment's guess
+		// misses and the entries crawl one lane per iteration -- and are
+		// the one-wave scalar parse's best case: decline the block (large
+		// blocks only: a short one costs a few chunks either way).
+		const bool sparse_test = C == 0 && n >= 4 * CHUNK;
+		int32_t used = 0;  // sub-segments holding a sequence start
 		E = __shfl(wave_incl_max(y), 63);
-		lead = lead_in_bytes(__shfl(wave_incl_scan(starts), 63));
-		if (C == 0 && n >= 4 * CHUNK) {
-			// Sparse chains (over 64 input bytes per sequence: long literal
-			// runs) defeat the speculative walks -- every segment's guess
-			// misses and the entries crawl one lane per iteration -- and are
-			// the one-wave scalar parse's best case: decline the block (large
-			// blocks only: a short one costs a few chunks either way).
-			int32_t used = 0;  // sub-segments holding a sequence start
+		starts = __shfl(wave_incl_scan(starts), 63);
+		if (sparse_test) {
 			if (s < n)
 				for (int k = 0; k < NSUB; ++k)
-					used += X.rbm[lane][k] ? 1 : 0;
-			if (!bad && __shfl(wave_incl_scan(used), 63) < CHUNK / SUB / 4)
-				bad = sparse = true;
+					used += X.rbm[tid][k] ? 1 : 0;
+			used = __shfl(wave_incl_scan(used), 63);
 		}
-		__syncthreads();  // the next chunk overwrites the staging buffer
+		if constexpr (W == 2) {  // the chunk's totals over both waves
+			if (lane == 0) {
+				X.xs[0][w][0] = E;
+				X.xs[0][w][1] = starts;
+				X.xs[0][w][2] = bad ? 1 : 0;
+				X.xs[0][w][3] = used;
+			}
+			__syncthreads();  // also: every read of this chunk's staging is done
+			E = max(X.xs[0][0][0], X.xs[0][1][0]);
+			starts = X.xs[0][0][1] + X.xs[0][1][1];
+			bad = (X.xs[0][0][2] | X.xs[0][1][2]) != 0;
+			used = X.xs[0][0][3] + X.xs[0][1][3];
+		}
+		lead = lead_in_bytes(starts);
+		if (sparse_test && !bad && used < CHUNK / SUB / 4)
+			bad = sparse = true;
+		if constexpr (W == 1)
+			__syncthreads();  // the next chunk overwrites the staging buffer
 	}
 	if (E != n)
 		bad = true;
-	if (lane == 0)
+	if (tid == 0)
 		status[b].code = bad ? (sparse ? DS_SPARSE : DS_RETRY) : DS_OK;
 	ISTAMP_FLUSH();
 }
 
-__global__ __launch_bounds__(64) void k_index(const uint8_t* __restrict__ frame, uint64_t frame_len,
-                                               const lz4ada_block_desc* __restrict__ desc,
-                                               uint32_t nblocks, uint8_t* __restrict__ tab_all,
-                                               lz4ada_block_status* __restrict__ status)
+// Pass 1 alone, 64 * W threads per block.  The product launches W = 1;
+// W = 2 puts k_decode_pp2's pass 1 under the table test.
+template <int W>
+__global__ __launch_bounds__(64 * W) void k_index(const uint8_t* __restrict__ frame, uint64_t frame_len,
+                                                   const lz4ada_block_desc* __restrict__ desc,
+                                                   uint32_t nblocks, uint8_t* __restrict__ tab_all,
+                                                   lz4ada_block_status* __restrict__ status)
 {
-	__shared__ IdxLds X;
+	__shared__ IdxLds<W> X;
 	if (blockIdx.x < nblocks)
-		index_block(X, frame, frame_len, desc, blockIdx.x, tab_all, status);
+		index_block<W>(X, frame, frame_len, desc, blockIdx.x, tab_all, status);
 }
 
 // ------------------------------------------------------------------ pass 2
@@ -1712,6 +1748,17 @@ __device__ __forceinline__ bool d1_emulable(int32_t mdst, int32_t L, int32_t& li
 	return ok;
 }
 
+// The status of a block with nothing to report but its code and, when that
+// is DS_OK, its output length (written by one lane).
+__device__ __forceinline__ void put_status(lz4ada_block_status& st, int32_t code, int32_t len)
+{
+	st.code = code;
+	st.aux = 0;
+	st.detail = 0;
+	st.err_out_pos = 0;
+	st.out_len = code == DS_OK ? uint32_t(len) : 0u;
+}
+
 // One block.  hist: output bytes right before this block's slot that its
 // matches may read -- 0 for independent blocks; in a linked frame, the
 // earlier blocks' output, contiguous when every one of them is full.
@@ -1765,13 +1812,8 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			else
 				wave_literal<LZ4ADA_STORED_NT>(ob, 0, S0, 0, n);
 		}
-		if (lane == 0) {
-			status[b].code = code;
-			status[b].aux = 0;
-			status[b].detail = 0;
-			status[b].err_out_pos = 0;
-			status[b].out_len = code == DS_OK ? uint32_t(n) : 0u;
-		}
+		if (lane == 0)
+			put_status(status[b], code, n);
 		out_len = code == DS_OK ? n : 0;
 		return code;
 	}
@@ -2297,50 +2339,60 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 	return bad ? DS_RETRY : DS_OK;
 }
 
-// Independent blocks (linked 0): one wave per block.  Linked frames in the
-// history layout of lz4ada_linked.hip (linked 2): one wave per block, each
-// slot preceded by LINK_HIST readable bytes.  Linked frames in contiguous
-// slots (linked 1, launched as one workgroup): the blocks in order, each
-// reading the previous ones' output as history while every block so far is
-// full (its slot then continues the previous one); a declined or short
-// block leaves every later block DS_RETRY for the exact path.  Pinned to two waves per
-// SIMD (at most 256 registers, so the allocator never reaches for AGPRs):
-// LDS allows 8 waves per CU, and the bench's 2048 blocks are all resident.
+// What k_decode_idx runs (its runtime argument).
+enum KIdxMode : int {
+	K_PASS2 = 0,   // pass 2 of independent blocks, one wave per block
+	K_SERIAL = 1,  // a linked frame in contiguous slots, launched as one workgroup
+	K_HIST = 2,    // K_PASS2 with LINK_HIST history bytes before each slot: no launcher passes it
+	               // (k_decode_idx_lk took over); kept because the bench ran slower without the arm
+	K_FUSED = 3,   // K_PASS2 after pass 1 of the same block by the same wave
+};
+
+// Independent blocks (K_PASS2, K_FUSED): one wave per block.  Linked frames
+// in contiguous slots (K_SERIAL, launched as one workgroup): the blocks in
+// order, each reading the previous ones' output as history while every
+// block so far is full (its slot then continues the previous one); a
+// declined or short block leaves every later block DS_RETRY for the exact
+// path.  (Linked frames in the history layout of lz4ada_linked.hip have the
+// two kernels below.)  Pinned to two waves per SIMD (at most 256 registers,
+// so the allocator never reaches for AGPRs): LDS allows 8 waves per CU, and
+// the bench's 2048 blocks are all resident.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx(const uint8_t* __restrict__ frame,
                                                     uint64_t frame_len,
                                                     const lz4ada_block_desc* __restrict__ desc,
                                                     uint32_t nblocks, uint8_t* __restrict__ tab_all,
                                                     uint8_t* __restrict__ out,
                                                     lz4ada_block_status* __restrict__ status,
-                                                    int linked)
+                                                    int mode)
 {
 	__shared__ union {
 		DecLds d;
-		IdxLds x;
+		IdxLds<1> x;
 	} U;
 	DecLds& D = U.d;
-	if (linked == 3) {
-		// fused: pass 1 of this block first (its table and status, read
+	if (mode == K_FUSED) {
+		// pass 1 of this block first (its table and status, read
 		// below by this same wave, made visible to it first), so a block's pass 2
 		// starts when its own pass 1 is done, not when every block's is
 		if (blockIdx.x < nblocks)
-			index_block(U.x, frame, frame_len, desc, blockIdx.x, tab_all, status);
+			index_block<1>(U.x, frame, frame_len, desc, blockIdx.x, tab_all, status);
 		// workgroup scope is enough (the same wave reads it back); an agent
 		// fence here wrote the whole L2 back once per block
 		vm_wait();
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 		__syncthreads();
-		linked = 0;
+		mode = K_PASS2;
 	}
 	// one call site of decode_block for every mode (code size)
-	int64_t hist = linked == 2 ? LINK_HIST : 0;
-	uint32_t b = linked == 1 ? 0u : blockIdx.x;
-	const uint32_t bend = linked == 1 ? nblocks : min(blockIdx.x + 1u, nblocks);
+	const bool serial = mode == K_SERIAL;
+	int64_t hist = mode == K_HIST ? LINK_HIST : 0;
+	uint32_t b = serial ? 0u : blockIdx.x;
+	const uint32_t bend = serial ? nblocks : min(blockIdx.x + 1u, nblocks);
 	for (; b < bend; ++b) {
 		int32_t len;
 		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status,
 		                                  hist, len);
-		if (linked != 1)
+		if (!serial)
 			return;
 		vm_wait();  // the next block reads this output as history
 		__syncthreads();
@@ -2353,7 +2405,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 		}
 		hist += len;
 	}
-	if (linked != 1)
+	if (!serial)
 		return;
 	for (uint32_t r = b + lane_id(); r < nblocks; r += 64)
 		if (status[r].code == DS_OK || r > b)
@@ -2377,8 +2429,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 
 // The linked path's byte planes (x, and y / h when a block needs them):
 // pass 2 of every block in the history layout with quirk D1 emulated under
-// the host's predicted round state (decode_block's D1E; k_decode_idx's
-// linked 2 mode without it).
+// the host's predicted round state (decode_block's D1E).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_lk(
         const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
         uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
@@ -2389,197 +2440,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 		return;
 	int32_t len;
 	decode_block(D, frame, frame_len, desc, blockIdx.x, tab_all, out, status, LINK_HIST, len, false, true);
-}
-
-// ============================================================ two waves
-// Pass 1 by the two waves of a 128-lane workgroup (k_decode_pp2's): 128
-// lanes walk one 16 KiB chunk, 128 bytes each; wave 0's lane 0 enters at
-// the exact chain position, wave 1's lane 0 at its lead-in guess until wave
-// 0's exit is known (one exchange per chunk).  (Round 4's k_decode_idx2,
-// which also split each pass-2 batch between the two waves, was retired in
-// round 6: k_decode_pp2 pipelining whole batches replaced it where two
-// waves per block pay, docs/DESIGN_LOG.md §3.)
-
-constexpr int SEG2 = 128;          // pass-1 segment per lane: 128 lanes per 16 KiB chunk
-constexpr int NSUB2 = SEG2 / SUB;  // records per segment
-static_assert(128 * SEG2 == CHUNK, "two waves walk one pass-1 chunk");
-#ifndef LZ4ADA_LEAD_SEQ2
-#define LZ4ADA_LEAD_SEQ2 60
-#endif
-constexpr int32_t LEAD_SEQ2 = LZ4ADA_LEAD_SEQ2;
-
-struct alignas(16) IdxLds2 {
-	uint8_t buf[CHUNK + 16];
-	uint32_t rbm[128][NSUB2 + 1];
-	cnt32 rcnt[128][NSUB2 / 2 + 1];
-	int32_t xa;        // wave 0's largest exit (wave 1's lane-0 entry)
-	int32_t xs[2][4];  // per wave: largest exit, sequence starts, bad, used sub-segments
-};
-
-__device__ __forceinline__ int32_t lead_in_bytes2(int32_t starts)
-{
-	const int32_t l = LEAD_SEQ2 * (CHUNK / max(starts, 1));
-	return __builtin_amdgcn_readfirstlane(min(max(l, LEAD_MIN), LEAD_MAX));
-}
-
-// Pass 1 of block b by both waves of the workgroup (index_block's rules).
-__device__ __forceinline__ void index_block2(IdxLds2& X, const uint8_t* __restrict__ frame,
-                                             uint64_t frame_len,
-                                             const lz4ada_block_desc* __restrict__ desc, uint32_t b,
-                                             uint8_t* __restrict__ tab_all,
-                                             lz4ada_block_status* __restrict__ status)
-{
-	const int32_t tid = int32_t(threadIdx.x), w = tid >> 6, lane = tid & 63;
-	const lz4ada_block_desc d = desc[b];
-	if (d.flags & LZ4ADA_BLOCK_STORED) {
-		if (tid == 0)
-			status[b].code = DS_OK;
-		return;
-	}
-	if (d.in_len >= RLE_MIN_IN && uint64_t(d.in_len) * RLE_RATIO < uint64_t(d.out_cap)) {
-		if (tid == 0)
-			status[b].code = DS_SPARSE;
-		return;
-	}
-	cg8* in = gptr(frame) + d.in_off;
-	const int32_t n = int32_t(d.in_len);
-	const uintptr_t lim = reinterpret_cast<uintptr_t>(frame) + frame_len;
-	const int32_t mis = int32_t(reinterpret_cast<uintptr_t>(in) & 15u);
-	uint64_t* tab = reinterpret_cast<uint64_t*>(tab_all) + (((d.in_off >> 8) + b) << 3);
-
-	Src S;
-	S.lds = X.buf;
-	S.mask = CHUNK - 1;
-	S.mis = mis;
-	S.in = in;
-	S.lim = lim;
-	constexpr int PF = CHUNK / 2048;  // 16-byte loads per thread per chunk
-	auto load16k = [&](uintptr_t a, u32x4 (&v)[PF]) {
-		if (a + CHUNK <= lim) {
-#pragma unroll
-			for (int r = 0; r < PF; ++r)
-				__builtin_memcpy(&v[r], reinterpret_cast<cg8*>(a + uintptr_t(2048 * r + 16 * tid)), 16);
-		} else {
-#pragma unroll
-			for (int r = 0; r < PF; ++r)
-				v[r] = gload16(a + uintptr_t(2048 * r + 16 * tid), lim);
-		}
-	};
-	const uintptr_t abase = reinterpret_cast<uintptr_t>(in) - uintptr_t(mis);
-	u32x4 pf[PF];
-	if (n > 0)
-		load16k(abase, pf);
-
-	int32_t E = 0, lead = LEAD_IN0;
-	bool bad = false, sparse = false;
-	for (int32_t C = 0; C < n && !bad; C += CHUNK) {
-#pragma unroll
-		for (int r = 0; r < PF; ++r)
-			*reinterpret_cast<u32x4*>(&X.buf[2048 * r + 16 * tid]) = pf[r];
-		if (tid == 0)
-			*reinterpret_cast<u32x4*>(&X.buf[CHUNK]) = pf[0];
-		__syncthreads();
-		if (C + CHUNK < n)
-			load16k(abase + uintptr_t(C + CHUNK), pf);
-		S.lo = C - mis;
-		S.hi = C - mis + CHUNK;
-
-		const int32_t s = C + SEG2 * tid;
-		const int32_t seg_end = min(s + SEG2, n);
-		int32_t ein = (tid == 0) ? E : s;
-		if (tid > 0 && s < n) {  // lead-in (index_block)
-			ein = lead_in_walk(S, C, s, lead);
-		}
-		uint32_t* ghi = reinterpret_cast<uint32_t*>(tab + (C >> 5) + NSUB2 * tid) + 1;
-		int32_t epos = INT32_MAX;
-		bool err = false;
-		int32_t nst = 0;
-#ifdef LZ4ADA_IDX_OLD_FIRST_WALK
-		int32_t y = (s < n) ? walk_segment<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], halves(X.rcnt[tid]), ghi,
-		                                          err, epos, 0, false, nst)
-		                    : ein;
-#else
-		int32_t y = (s < n) ? walk_first<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], X.rcnt[tid], ghi, err,
-		                                        epos, nst)
-		                    : ein;
-#endif
-		// this wave's lane-0 entry: exact for wave 0, wave 1's lead-in guess
-		// until wave 0's largest exit is known
-		int32_t e0 = __shfl(ein, 0);
-		auto converge = [&]() {
-			for (int it = 0; it < 64; ++it) {
-				int32_t prev = __shfl_up(wave_incl_max(y), 1);
-				if (lane == 0)
-					prev = e0;
-				const bool changed = prev != ein;
-				if (!__any(changed))
-					break;
-				if (changed) {
-					ein = prev;
-					if (s < n) {
-						y = walk_segment<NSUB2>(S, ein, s, seg_end, n, X.rbm[tid], halves(X.rcnt[tid]), ghi,
-						                        err, epos, y, !err, nst);
-					} else {
-						y = ein;
-						err = false;
-					}
-				}
-			}
-		};
-		converge();
-		{
-			const int32_t mx = __shfl(wave_incl_max(y), 63);
-			if (tid == 0)
-				X.xa = mx;
-		}
-		__syncthreads();
-		if (w == 1) {
-			const int32_t ea = X.xa;
-			if (ea != e0) {  // the guess missed: the lanes it reached walk again
-				e0 = ea;
-				converge();
-			}
-		}
-		// converged: every lane's records are its last walk's, to HBM
-		bad = __any(s < n && err);
-		wave_lds_fence();
-		int32_t starts = 0;
-#pragma unroll
-		for (int i = 0; i < NSUB2; ++i) {
-			const int32_t r = 64 * i + lane, sg = 64 * w + r / NSUB2, sb = r & (NSUB2 - 1);
-			if (C + SEG2 * sg < n) {
-				const uint32_t bmv = X.rbm[sg][sb], c16 = halves(X.rcnt[sg])[sb];
-				starts += __popc(bmv);
-				if (c16 != 0xFFFFu)
-					tab[(C >> 5) + 256 * w + r] = uint64_t(bmv) | (uint64_t(c16) << 32);
-				else
-					*reinterpret_cast<uint32_t*>(tab + (C >> 5) + 256 * w + r) = bmv;
-			}
-		}
-		int32_t used = 0;
-		if (C == 0 && s < n)
-			for (int k = 0; k < NSUB2; ++k)
-				used += X.rbm[tid][k] ? 1 : 0;
-		starts = __shfl(wave_incl_scan(starts), 63);
-		used = __shfl(wave_incl_scan(used), 63);
-		const int32_t mx = __shfl(wave_incl_max(y), 63);
-		if (lane == 0) {
-			X.xs[w][0] = mx;
-			X.xs[w][1] = starts;
-			X.xs[w][2] = bad ? 1 : 0;
-			X.xs[w][3] = used;
-		}
-		__syncthreads();  // also: every read of this chunk's staging is done
-		E = max(X.xs[0][0], X.xs[1][0]);
-		bad = (X.xs[0][2] | X.xs[1][2]) != 0;
-		lead = lead_in_bytes2(X.xs[0][1] + X.xs[1][1]);
-		if (C == 0 && n >= 4 * CHUNK && !bad && X.xs[0][3] + X.xs[1][3] < CHUNK / SUB / 4)
-			bad = sparse = true;  // literal-heavy (index_block)
-	}
-	if (E != n)
-		bad = true;
-	if (tid == 0)
-		status[b].code = bad ? (sparse ? DS_SPARSE : DS_RETRY) : DS_OK;
 }
 
 // ============================================================ pipelined pair
@@ -3134,7 +2994,7 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 }
 
 // Independent blocks, both passes, two waves per block pipelining batches
-// (pass 1: index_block2, both waves walking each chunk).  Two waves per SIMD
+// (pass 1: index_block<2>, both waves walking each chunk).  Two waves per SIMD
 // (<= 256 VGPRs; the block checksum kernel's 118 still fit beside them at
 // one block per SIMD).
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_pp2(
@@ -3144,13 +3004,13 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
 {
 	__shared__ union {
 		PpLds2 d;
-		IdxLds2 x;
+		IdxLds<2> x;
 	} U;
 	if (blockIdx.x >= nblocks)
 		return;
 	const uint32_t b = blockIdx.x;
 	const int32_t tid = int32_t(threadIdx.x), w = tid >> 6;
-	index_block2(U.x, frame, frame_len, desc, b, tab_all, status);
+	index_block<2>(U.x, frame, frame_len, desc, b, tab_all, status);
 	// the table and status this block's pass 1 wrote are read back by both waves
 	vm_wait();
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -3174,13 +3034,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
 			else
 				wave_literal<LZ4ADA_STORED_NT>(gptr(out) + d.out_off, c0, S0, c0, c1 - c0);
 		}
-		if (tid == 0) {
-			status[b].code = c;
-			status[b].aux = 0;
-			status[b].detail = 0;
-			status[b].err_out_pos = 0;
-			status[b].out_len = c == DS_OK ? uint32_t(n) : 0u;
-		}
+		if (tid == 0)
+			put_status(status[b], c, n);
 		return;
 	}
 	PpLds2& L = U.d;
@@ -3193,15 +3048,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k
 	__syncthreads();
 	const int32_t len = decode_block_pp2(L, frame, frame_len, desc, b, tab_all, out);
 	if (tid == 0) {
-		if (len < 0) {
+		if (len < 0)
 			status[b].code = DS_RETRY;
-		} else {
-			status[b].code = DS_OK;
-			status[b].aux = 0;
-			status[b].detail = 0;
-			status[b].err_out_pos = 0;
-			status[b].out_len = uint32_t(len);
-		}
+		else
+			put_status(status[b], DS_OK, len);
 	}
 }
 
@@ -3245,72 +3095,70 @@ size_t index_table_bytes(uint64_t frame_len, uint32_t nblocks)
 
 hipError_t launch_index(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
                         uint32_t nblocks, uint8_t* d_tab, lz4ada_block_status* d_status,
-                        hipStream_t stream)
+                        hipStream_t stream, int waves)
 {
+	if (waves != 1 && waves != 2)
+		return hipErrorInvalidValue;
 	if (nblocks == 0)
 		return hipSuccess;
-	hipLaunchKernelGGL(idx::k_index, dim3(nblocks), dim3(64), 0, stream, d_frame, frame_len, d_desc,
-	                   nblocks, d_tab, d_status);
+	hipLaunchKernelGGL(waves == 2 ? idx::k_index<2> : idx::k_index<1>, dim3(nblocks), dim3(64 * waves), 0,
+	                   stream, d_frame, frame_len, d_desc, nblocks, d_tab, d_status);
 	return hipGetLastError();
 }
 
 hipError_t launch_decode_idx_tab(const uint8_t* d_frame, uint64_t frame_len,
                                  const lz4ada_block_desc* d_desc, uint32_t nblocks,
                                  const uint8_t* d_tab, uint8_t* d_out,
-                                 lz4ada_block_status* d_status, int mode, hipStream_t stream)
+                                 lz4ada_block_status* d_status, IdxMode mode, hipStream_t stream)
 {
 	if (nblocks == 0)
 		return hipSuccess;
-	if (mode == 6) {  // pass 2, linked layout, literals as zeros (k_decode_idx_zl)
-		hipLaunchKernelGGL(idx::k_decode_idx_zl, dim3(nblocks), dim3(64), 0, stream, d_frame, frame_len,
-		                   d_desc, nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status);
-		return hipGetLastError();
+	uint8_t* tab = const_cast<uint8_t*>(d_tab);
+	if (mode == IdxMode::PASS2 || mode == IdxMode::LINKED_SERIAL || mode == IdxMode::FUSED_ONE) {
+		const bool serial = mode == IdxMode::LINKED_SERIAL;  // one workgroup, the blocks in order
+		hipLaunchKernelGGL(idx::k_decode_idx, dim3(serial ? 1 : nblocks), dim3(64), 0, stream, d_frame,
+		                   frame_len, d_desc, nblocks, tab, d_out, d_status,
+		                   int(serial ? idx::K_SERIAL : (mode == IdxMode::PASS2 ? idx::K_PASS2 : idx::K_FUSED)));
+	} else {
+		const auto k = mode == IdxMode::LINKED_LK   ? idx::k_decode_idx_lk
+		               : mode == IdxMode::LINKED_ZL ? idx::k_decode_idx_zl
+		                                            : idx::k_decode_pp2;
+		hipLaunchKernelGGL(k, dim3(nblocks), dim3(mode == IdxMode::FUSED_PAIR ? 128 : 64), 0, stream, d_frame,
+		                   frame_len, d_desc, nblocks, tab, d_out, d_status);
 	}
-	if (mode == 2) {  // pass 2, linked layout (k_decode_idx_lk: quirk D1 emulated)
-		hipLaunchKernelGGL(idx::k_decode_idx_lk, dim3(nblocks), dim3(64), 0, stream, d_frame, frame_len,
-		                   d_desc, nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status);
-		return hipGetLastError();
-	}
-	if (mode == 5 || mode == 4) {  // both passes, two waves per block pipelining batches (k_decode_pp2;
-		                           // 4: round 4's k_decode_idx2, retired -- its callers get pp2)
-		hipLaunchKernelGGL(idx::k_decode_pp2, dim3(nblocks), dim3(128), 0, stream, d_frame, frame_len,
-		                   d_desc, nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status);
-		return hipGetLastError();
-	}
-	hipLaunchKernelGGL(idx::k_decode_idx, dim3(mode == 1 ? 1 : nblocks), dim3(64), 0, stream, d_frame,
-	                   frame_len, d_desc, nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, mode);
 	return hipGetLastError();
 }
 
 // The fused launch for independent blocks.  One wave per block
-// (k_decode_idx, mode 3) while the blocks fill the chip's SIMDs twice; two
-// waves per block pipelining batches (k_decode_pp2, mode 5) for at most 4
-// blocks per CU (measured, docs/DESIGN_LOG.md §3: 1,024 x 4 MiB mixed 12.0
-// -> 8.7 ms, but at 2,048 blocks 13.3 -> 18.0 ms).  LZ4ADA_IDX_WAVES=1 / p
-// (or 2, which meant the retired k_decode_idx2) forces one or the other.
-int idx_fused_mode(uint32_t nblocks)
+// (k_decode_idx) while the blocks fill the chip's SIMDs twice; two waves per
+// block pipelining batches (k_decode_pp2) for at most 4 blocks per CU
+// (measured, docs/DESIGN_LOG.md §3: 1,024 x 4 MiB mixed 12.0 -> 8.7 ms, but
+// at 2,048 blocks 13.3 -> 18.0 ms).  LZ4ADA_IDX_WAVES=1 / p (or 2) forces
+// one or the other.
+IdxMode idx_fused_mode(uint32_t nblocks)
 {
-	static const int forced = [] {
+	static const char forced = [] {
 		const char* e = getenv("LZ4ADA_IDX_WAVES");
-		return e ? (e[0] == '1' ? 3 : ((e[0] == '2' || e[0] == 'p') ? 5 : 0)) : 0;
+		return e ? e[0] : '\0';
 	}();
-	if (forced)
-		return forced;
+	if (forced == '1')
+		return IdxMode::FUSED_ONE;
+	if (forced == '2' || forced == 'p')
+		return IdxMode::FUSED_PAIR;
 	int dev = 0, cus = 256;
 	if (hipGetDevice(&dev) == hipSuccess)
 		(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-	return nblocks <= uint32_t(4 * cus) ? 5 : 3;
+	return nblocks <= uint32_t(4 * cus) ? IdxMode::FUSED_PAIR : IdxMode::FUSED_ONE;
 }
 
 const char* idx_fused_kernel_name(uint32_t nblocks)
 {
-	const int m = idx_fused_mode(nblocks);
-	return m == 5 ? "k_decode_pp2" : "k_decode_idx";
+	return idx_fused_mode(nblocks) == IdxMode::FUSED_PAIR ? "k_decode_pp2" : "k_decode_idx";
 }
 
 hipError_t launch_decode_idx(const uint8_t* d_frame, uint64_t frame_len,
                              const lz4ada_block_desc* d_desc, uint32_t nblocks, uint8_t* d_out,
-                             lz4ada_block_status* d_status, hipStream_t stream, int linked)
+                             lz4ada_block_status* d_status, hipStream_t stream, IdxRun run)
 {
 	if (nblocks == 0)
 		return hipSuccess;
@@ -3318,19 +3166,19 @@ hipError_t launch_decode_idx(const uint8_t* d_frame, uint64_t frame_len,
 	hipError_t err = hipMallocAsync(&tab, index_table_bytes(frame_len, nblocks), stream);
 	if (err != hipSuccess)
 		return err;
-	const bool split = linked == -4;  // the two passes as two launches (diagnostic: per-pass counters)
-	if (linked <= 0 && !split) {  // both passes in one launch (-1: one wave per block, -2: two, -3: pipelined pair)
-		const int mode = linked == -1 ? 3 : (linked == -2 ? 4 : (linked == -3 ? 5 : idx_fused_mode(nblocks)));
-		err = launch_decode_idx_tab(d_frame, frame_len, d_desc, nblocks,
-		                            static_cast<const uint8_t*>(tab), d_out, d_status, mode, stream);
-	} else {
+	// pass 1 as a launch of its own, or inside the FUSED modes' one launch
+	const bool two = run == IdxRun::SPLIT || run == IdxRun::LINKED_SERIAL;
+	const IdxMode mode = run == IdxRun::SPLIT           ? IdxMode::PASS2
+	                     : run == IdxRun::LINKED_SERIAL ? IdxMode::LINKED_SERIAL
+	                     : run == IdxRun::FUSED_ONE     ? IdxMode::FUSED_ONE
+	                     : run == IdxRun::FUSED_PAIR    ? IdxMode::FUSED_PAIR
+	                                                    : idx_fused_mode(nblocks);
+	if (two)
 		err = launch_index(d_frame, frame_len, d_desc, nblocks, static_cast<uint8_t*>(tab), d_status,
 		                   stream);
-		if (err == hipSuccess)
-			err = launch_decode_idx_tab(d_frame, frame_len, d_desc, nblocks,
-			                            static_cast<const uint8_t*>(tab), d_out, d_status, split ? 0 : linked,
-			                            stream);
-	}
+	if (err == hipSuccess)
+		err = launch_decode_idx_tab(d_frame, frame_len, d_desc, nblocks, static_cast<const uint8_t*>(tab),
+		                            d_out, d_status, mode, stream);
 	const hipError_t e2 = hipFreeAsync(tab, stream);
 	return err != hipSuccess ? err : e2;
 }

@@ -95,7 +95,26 @@ enum DecVariant : int { DEC_PC = 0, DEC_IDX = 3, DEC_IDX_ALONE = 4,
                         DEC_PP2_ALONE = 9,
                         // k_index then k_decode_idx's pass 2, two launches (per-pass counters)
                         DEC_IDX_SPLIT = 10 };
-int idx_fused_mode(uint32_t nblocks);  // 3: k_decode_idx, 5: k_decode_pp2 (4, round 4's k_decode_idx2, is retired) (lz4ada_idx.hip)
+// What launch_decode_idx_tab launches (lz4ada_idx.hip).
+enum class IdxMode {
+	PASS2,          // k_decode_idx: pass 2 of independent blocks over a table from launch_index
+	LINKED_SERIAL,  // k_decode_idx as one workgroup: a linked frame's blocks in order (contiguous slots)
+	LINKED_LK,      // k_decode_idx_lk: pass 2 of every block at once, LINK_HIST readable history
+	                // bytes before each slot, quirk D1 emulated
+	LINKED_ZL,      // k_decode_idx_zl: the same layout, literals as zeros
+	FUSED_ONE,      // k_decode_idx: both passes of independent blocks, one wave per block (d_tab
+	                // is written: no launch_index needed)
+	FUSED_PAIR,     // k_decode_pp2: both passes, two waves per block pipelining batches
+};
+// What a caller of launch_decode_idx asks for.
+enum class IdxRun {
+	AUTO,           // both passes in one launch, the kernel idx_fused_mode picks
+	FUSED_ONE,      // ... k_decode_idx whatever the launch size
+	FUSED_PAIR,     // ... k_decode_pp2 whatever the launch size
+	SPLIT,          // k_index, then pass 2: two launches (diagnostic: per-pass counters)
+	LINKED_SERIAL,  // k_index, then the serial linked workgroup
+};
+IdxMode idx_fused_mode(uint32_t nblocks);  // FUSED_ONE or FUSED_PAIR, by launch size (lz4ada_idx.hip)
 const char* idx_fused_kernel_name(uint32_t nblocks);  // the kernel idx_fused_mode picks
 
 hipError_t launch_decode_variant(const uint8_t* d_frame, uint64_t frame_len,
@@ -104,21 +123,22 @@ hipError_t launch_decode_variant(const uint8_t* d_frame, uint64_t frame_len,
                                  hipStream_t stream);
 
 // The default decoder: the index-driven decoder, then the literal-heavy and
-// two-wave decoders for the blocks it declines; LZ4ADA_DECODER=pc / wg
-// select the others.
+// two-wave decoders for the blocks it declines; LZ4ADA_DECODER=pc selects
+// k_decode_pc alone.
 hipError_t launch_decode_blocks(const uint8_t* d_frame, uint64_t frame_len,
                                 const lz4ada_block_desc* d_desc, uint32_t nblocks,
                                 uint8_t* d_out, lz4ada_block_status* d_status,
                                 hipStream_t stream);
 
 // Index-driven decoder alone (lz4ada_idx.hip): k_index + k_decode_idx;
-// declined blocks keep status DS_RETRY and are not decoded.  linked: the
-// blocks of one linked frame (slots contiguous), decoded in order with the
-// earlier output as history; from the first declined or short block on,
-// every block is left DS_RETRY.
+// declined blocks keep status DS_RETRY and are not decoded.
+// IdxRun::LINKED_SERIAL: the blocks of one linked frame (slots contiguous),
+// decoded in order with the earlier output as history; from the first
+// declined or short block on, every block is left DS_RETRY.
 hipError_t launch_decode_idx(const uint8_t* d_frame, uint64_t frame_len,
                              const lz4ada_block_desc* d_desc, uint32_t nblocks, uint8_t* d_out,
-                             lz4ada_block_status* d_status, hipStream_t stream, int linked = 0);
+                             lz4ada_block_status* d_status, hipStream_t stream,
+                             IdxRun run = IdxRun::AUTO);
 
 // Two-wave decoder alone (k_decode_pc).  retry_only: only blocks whose
 // status is DS_RETRY.  hist: output bytes readable right before every slot
@@ -130,20 +150,19 @@ hipError_t launch_decode_pc(const uint8_t* d_frame, uint64_t frame_len,
 
 // Pass 1 of the index-driven decoder alone: the sequence-index table of
 // every block (index_table_bytes() of device memory at d_tab); declined
-// blocks get status DS_RETRY.
+// blocks get status DS_RETRY.  waves: 1 (the product's k_index) or 2 (the
+// pass 1 k_decode_pp2 runs, for the table test); anything else is
+// hipErrorInvalidValue.
 size_t index_table_bytes(uint64_t frame_len, uint32_t nblocks);
 hipError_t launch_index(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
                         uint32_t nblocks, uint8_t* d_tab, lz4ada_block_status* d_status,
-                        hipStream_t stream);
-// Pass 2 over a table from launch_index.  mode 0: independent blocks; 1:
-// the serial linked decoder (one workgroup, blocks in order); 2: every
-// block at once with LINK_HIST readable history bytes before its slot; 3:
-// independent blocks, each wave running pass 1 of its block first (d_tab
-// is written: no launch_index needed).
+                        hipStream_t stream, int waves = 1);
+// One launch of the index decoder over the table at d_tab: pass 2 over a
+// table from launch_index, or (the FUSED modes) both passes.
 hipError_t launch_decode_idx_tab(const uint8_t* d_frame, uint64_t frame_len,
                                  const lz4ada_block_desc* d_desc, uint32_t nblocks,
                                  const uint8_t* d_tab, uint8_t* d_out,
-                                 lz4ada_block_status* d_status, int mode, hipStream_t stream);
+                                 lz4ada_block_status* d_status, IdxMode mode, hipStream_t stream);
 
 // Literal-heavy blocks pass 1 declined (status DS_SPARSE; lz4ada_sparse.hip):
 // decoded straight to HBM, one wave per block; anything unusual leaves the

@@ -1371,12 +1371,17 @@ hipError_t launch_decode_variant(const uint8_t* d_frame, uint64_t frame_len,
 		return hipGetLastError();
 	}
 	if (variant == DEC_IDX_LINKED)
-		return launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream, 1);
-	if (variant == DEC_IDX_SPLIT)
-		return launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream, -4);
-	if (variant == DEC_IDX1_ALONE || variant == DEC_IDX2_ALONE || variant == DEC_PP2_ALONE)
 		return launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream,
-		                         variant == DEC_IDX1_ALONE ? -1 : (variant == DEC_IDX2_ALONE ? -2 : -3));
+		                         IdxRun::LINKED_SERIAL);
+	if (variant == DEC_IDX_SPLIT)
+		return launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream, IdxRun::SPLIT);
+	if (variant == DEC_IDX1_ALONE)
+		return launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream,
+		                         IdxRun::FUSED_ONE);
+	// (DEC_IDX2_ALONE meant k_decode_idx2, retired: k_decode_pp2 replaced it)
+	if (variant == DEC_IDX2_ALONE || variant == DEC_PP2_ALONE)
+		return launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream,
+		                         IdxRun::FUSED_PAIR);
 	if (variant == DEC_IDX || variant == DEC_IDX_ALONE || variant == DEC_IDX_SPARSE) {
 		const hipError_t err = launch_decode_idx(d_frame, frame_len, d_desc, nblocks, d_out,
 		                                         d_status, stream);
@@ -1571,7 +1576,7 @@ hipError_t launch_decode_checked(const uint8_t* d_frame, uint64_t frame_len,
 	err = hipEventRecord(side->fork, stream);
 	if (err == hipSuccess)
 		err = hipStreamWaitEvent(side->s, side->fork, 0);
-	// pass 1 and pass 2 in one launch (k_decode_idx mode 3), or as two
+	// pass 1 and pass 2 in one launch (idx_fused_mode's kernel), or as two
 	// (LZ4ADA_NO_FUSE, for A/B)
 	static const bool fuse = getenv("LZ4ADA_NO_FUSE") == nullptr;
 	if (err == hipSuccess)
@@ -1586,7 +1591,8 @@ hipError_t launch_decode_checked(const uint8_t* d_frame, uint64_t frame_len,
 		err = hipEventRecord(side->join, side->s);
 	if (err == hipSuccess && !fuse)
 		err = launch_decode_idx_tab(d_frame, frame_len, d_desc, nblocks,
-		                            static_cast<const uint8_t*>(tab), d_out, d_status, 0, stream);
+		                            static_cast<const uint8_t*>(tab), d_out, d_status, IdxMode::PASS2,
+		                            stream);
 	// literal-heavy blocks pass 1 declined, then every other declined block
 	if (err == hipSuccess)
 		err = launch_decode_sparse(d_frame, frame_len, d_desc, nblocks, d_out, d_status, stream);

@@ -9,7 +9,7 @@
 //
 //  * layout: every block's output slot is preceded by a 64 KiB history
 //    region (desc.out_off - 65536), so the decoders read "before the block
-//    start" like any other output byte (k_decode_idx mode 2, k_decode_pc
+//    start" like any other output byte (k_decode_idx_lk / _zl, k_decode_pc
 //    with hist = LINK_HIST);
 //  * two decodes of the whole batch with different history patterns at
 //    position k of the region: plane X holds k & 255 there; plane Z has

@@ -203,7 +203,8 @@ _sig = {
     "lz4ada_launch_decode": ([_vp, ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp], ctypes.c_int),
     "lz4ada_launch_decode_variant": ([_vp, ctypes.c_uint64, _vp, _i64, _vp, _vp, ctypes.c_int, _vp],
                                      ctypes.c_int),
-    "lz4ada_index_table_debug": ([_vp, ctypes.c_uint64, _vp, _i64, _vp, _i64, _vp, _vp], ctypes.c_int),
+    "lz4ada_index_table_debug": ([_vp, ctypes.c_uint64, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.c_int],
+                                 ctypes.c_int),
     "lz4ada_launch_block_checksums": ([_vp, _vp, _i64, _vp, _vp], ctypes.c_int),
     "lz4ada_output_checksums_device": ([_vp, _vp, _vp, _i64, _vp, _vp], ctypes.c_int),
     "lz4ada_decode_frame": ([_vp, _i64, _vp, _i64, _pi64, _pi64], ctypes.c_int),
@@ -570,14 +571,15 @@ def launch_decode_variant(d_frame, frame_len, d_descs, nblocks, d_out, d_status,
                                              d_status, variant, stream), _thread_error())
 
 
-def index_table_debug(d_frame, frame_len, d_descs, nblocks, d_status, stream=0) -> bytes:
-    """Test-only: pass 1 (k_index) alone; the sequence-index table as bytes.
+def index_table_debug(d_frame, frame_len, d_descs, nblocks, d_status, stream=0, waves=1) -> bytes:
+    """Test-only: pass 1 (k_index) alone, by 1 or 2 waves per block (the pass 1
+    of k_decode_idx / k_decode_pp2); the sequence-index table as bytes.
     Block b's 8-byte records (bitmap | count << 32, one per 32 payload bytes)
     start at byte 64 * ((in_off >> 8) + b); d_status gets pass 1's verdicts."""
     cap = ((frame_len >> 8) + nblocks + 2) * 64
     buf = (ctypes.c_uint8 * cap)()
     _check(_lib.lz4ada_index_table_debug(d_frame, frame_len, d_descs, nblocks, buf, cap, d_status,
-                                         stream), _thread_error())
+                                         stream, waves), _thread_error())
     return bytes(buf)
 
 

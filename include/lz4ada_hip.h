@@ -269,7 +269,9 @@ int lz4ada_launch_decode_variant(const void *d_frame, uint64_t frame_len,
                                  const lz4ada_block_desc *d_descs, int64_t nblocks, void *d_out,
                                  lz4ada_block_status *d_status, int variant, void *stream);
 /* Test-only, like the variants above: pass 1 of the index decoder alone
- * (k_index) into a scratch table, which is copied to host_out (host_cap
+ * (k_index, by `waves` = 1 or 2 waves per block: the pass 1 that
+ * k_decode_idx and k_decode_pp2 run; any other value is a constraint error)
+ * into a scratch table, which is copied to host_out (host_cap
  * bytes; the call fails when the table is larger).  Block b's records
  * start at byte 64 * ((in_off >> 8) + b) of the table: one 8-byte record
  * per 32-byte sub-segment of its payload, start bitmap | output bytes << 32
@@ -279,7 +281,8 @@ int lz4ada_launch_decode_variant(const void *d_frame, uint64_t frame_len,
  * drained; the table's size in bytes is ((frame_len >> 8) + nblocks + 2) * 64. */
 int lz4ada_index_table_debug(const void *d_frame, uint64_t frame_len,
                              const lz4ada_block_desc *d_descs, int64_t nblocks, void *host_out,
-                             int64_t host_cap, lz4ada_block_status *d_status, void *stream);
+                             int64_t host_cap, lz4ada_block_status *d_status, void *stream,
+                             int waves);
 /* The name of the kernel the fused bulk decode (LZ4ADA_DECODE_IDX, the
  * product call lz4ada_decode_blocks_device) launches for nblocks blocks --
  * it depends on how the block count fills the chip (for benches and

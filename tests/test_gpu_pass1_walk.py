@@ -1,19 +1,21 @@
-"""Pass 1 of the index decoder (k_index; index_block / index_block2 in
-csrc/lz4ada_idx.hip) on the shapes where a lane's first walk of a chunk can
+"""Pass 1 of the index decoder (k_index; index_block<W> in
+csrc/lz4ada_idx.hip, by one wave or two) on the shapes where a lane's first walk of a chunk can
 go wrong: a sequence start at every bit of a record and at every boundary
 (32-byte sub-segment, 256-byte segment, 16 KiB chunk), fields straddling a
 boundary, the densest sub-segments next to the largest sequences the
 branch-free parse accepts, output counts that saturate the records' 16-bit
 field, rare shapes beside ordinary lanes, segments and chunks without a
 start, literal bytes that read as tokens (so lead-in guesses miss and the
-fixed-point loop re-walks), ragged sizes, and malformed data on the
+fixed-point loop re-walks), ragged sizes, payloads that end around the
+half chunk where the second wave's lanes begin, and malformed data on the
 converged chain.
 
 Every well-formed block must be ACCEPTED (status 0, not DS_RETRY) by the
 one-wave decoder, the two-launch split and the pipelined pair, each alone,
 with the oracle's bytes: a pass 1 that silently declined would still give
 right bytes through the retry decoder.  The pass-1 table itself
-(lz4ada_index_table_debug) must equal a serial parse in Python.  Small
+(lz4ada_index_table_debug), written by one wave per block and by two, must
+equal a serial parse in Python.  Small
 frames: blocks of at most ~100 KiB in 256 KiB slots."""
 import random
 
@@ -88,6 +90,9 @@ def _sized(seed, n):
     return Blk(seed).fill_to(n - 6).done(b"tail!")
 
 
+HALF_SIZES = (CHUNK // 2 - 1, CHUNK // 2, CHUNK // 2 + 1, CHUNK + CHUNK // 2 + 1)
+
+
 def _cases():
     c = {}
     # a 3-byte sequence's token at every bit of a record, and at the last /
@@ -149,6 +154,18 @@ def _cases():
         rw.append(b.fill_to(2 * CHUNK + 3000).done())
     c["rewalk"] = rw
     c["sizes"] = [_sized(1000 + n, n) for n in (6, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 32773)]
+    # two waves per block (128 lanes of 128 bytes; the second wave's begin at
+    # CHUNK / 2): payloads in which it has no lane, exactly one lane, and one
+    # lane in the second chunk; and a token-like literal run (the rewalk
+    # recipe) over CHUNK / 2 - 400 .. CHUNK / 2 + 400, so the lead-in guess of
+    # the second wave's lane 0 misses and it converges a second time
+    hf = [_sized(2000 + n, n) for n in HALF_SIZES]
+    b = Blk(990).fill_to(CHUNK // 2 - 410)
+    lit0 = b.n + 1 + _extlen(830)  # the run's first literal byte
+    assert lit0 <= CHUNK // 2 - 400 and lit0 + 830 > CHUNK // 2 + 400
+    b.add(bytes(b.rng.choice(bytes(range(0xF0, 0x100))) for _ in range(830))).fill_to(b.n + 1500)
+    hf.append(b.fill_to(CHUNK + 3000).done())
+    c["half"] = hf
     return c
 
 
@@ -172,6 +189,7 @@ def frames():
 
 def test_sizes_are_the_issues():
     assert [len(c) for c, _ in CASES["sizes"]] == [6, 255, 256, 257, CHUNK - 1, CHUNK, CHUNK + 1, 32773]
+    assert [len(c) for c, _ in CASES["half"][:4]] == [8191, 8192, 8193, 24577]
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
@@ -225,8 +243,10 @@ def model_records(c):
     return [b | (k << 32) for b, k in zip(bm, cnt)]
 
 
-@pytest.mark.parametrize("name", list(CASES))
-def test_table_equals_serial_parse(frames, name):
+# (waves = 1 keeps the case's name as its id)
+@pytest.mark.parametrize("name,waves", [(n, w) for w in (1, 2) for n in CASES],
+                         ids=[n if w == 1 else n + "-waves2" for w in (1, 2) for n in CASES])
+def test_table_equals_serial_parse(frames, name, waves):
     import torch
     frame, payloads, _ = frames[name]
     info, descs = lz4ada.frame_index(frame)
@@ -236,16 +256,16 @@ def test_table_equals_serial_parse(frames, name):
     d_desc = torch.frombuffer(bytearray(bytes(descs)[:nb * 32]), dtype=torch.uint8).to(dev)
     d_st = torch.zeros(nb * 32, dtype=torch.uint8, device=dev)
     tab = lz4ada.index_table_debug(d_frame.data_ptr(), len(frame), d_desc.data_ptr(), nb,
-                                   d_st.data_ptr(), torch.cuda.current_stream().cuda_stream)
+                                   d_st.data_ptr(), torch.cuda.current_stream().cuda_stream, waves=waves)
     st = (lz4ada.BlockStatus * nb).from_buffer_copy(d_st.cpu().numpy().tobytes())
     for i, c in enumerate(payloads):
-        assert st[i].code == 0, (name, i, st[i].code)
+        assert st[i].code == 0, (name, waves, i, st[i].code)
         assert frame[descs[i].in_off:descs[i].in_off + descs[i].in_len] == c
         want = model_records(c)
         base = 64 * ((descs[i].in_off >> 8) + i)
         got = [int.from_bytes(tab[base + 8 * k:base + 8 * k + 8], "little") for k in range(len(want))]
         bad = [(k, hex(got[k]), hex(want[k])) for k in range(len(want)) if got[k] != want[k]]
-        assert not bad, (name, i, len(c), bad[:4])
+        assert not bad, (name, waves, i, len(c), bad[:4])
 
 
 # ---- malformed data on the converged chain
@@ -276,7 +296,7 @@ def good_block():
 def test_malformed_is_declined(good_block, kind, place):
     bad = _malformed(kind, PLACES[place])
     frame, _ = lz4frame.build_frame([good_block + (False,), (bad, b"", False)], BMAX, indep=True)
-    for variant in ("idx1", "split"):
+    for variant in ("idx1", "split", "pp2"):
         descs, st, out = _run_variant_alone(frame, VARIANTS[variant])
         assert st[0].code == 0 and out[:st[0].out_len] == good_block[1], (variant, st[0].code)
         assert st[1].code == lz4ada.DS_RETRY, (variant, st[1].code)
