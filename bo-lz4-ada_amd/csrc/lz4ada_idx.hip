@@ -89,7 +89,11 @@ __device__ __forceinline__ void vm_wait()
 // waves (each stamp drains the wave's memory counters: read shares).
 enum IdxPhase { I_STAGE, I_WALK0, I_ITER, I_CHUNKS, I_ITERS,
 	            D_STAGE, D_WALK1, D_WALK2, D_TLDS, D_LIT, D_MFAR, D_NEAR, D_FLUSH, D_GLOBAL,
-	            D_BATCHES, D_GBATCHES, D_ROUNDS, D_TASKS, D_LANES, I_STEPS, I_MAXST, I_LEAD, IDX_NST };
+	            D_BATCHES, D_GBATCHES, D_ROUNDS, D_TASKS, D_LANES, I_STEPS, I_MAXST, I_LEAD,
+	            // pieces dealt past the wave's 64 lanes: batches whose dealt HBM pieces exceed 64, those
+	            // pieces, the batches left to M's load-and-wait path and their pieces; ring_pieces calls
+	            // with more than 64 pieces, the pieces beyond, and its 64-piece chunk passes
+	            D_HOVF_B, D_HOVF_P, D_HSLOW_B, D_HSLOW_P, D_ROVF_B, D_ROVF_P, D_RCHUNKS, IDX_NST };
 #ifdef LZ4ADA_IDX_STAMPS
 __device__ unsigned long long g_idx_stamps[IDX_NST];
 #define ISTAMP_DECL uint64_t ist[IDX_NST] = {}; uint64_t ist_t = __builtin_amdgcn_s_memtime()
@@ -1445,6 +1449,14 @@ __device__ __forceinline__ int32_t match_pieces(int32_t off, int32_t ml)
 	return stp == 16 ? (ml + 15) >> 4 : div_small(ml + stp - 1, stp, rr);
 }
 
+// Rounds whose idle own-piece slots take dealt HBM pieces beyond the 64th
+// (decode_block's P; 0: none, every such piece loads in M)
+#ifndef LZ4ADA_BORROW_SLOTS
+#define LZ4ADA_BORROW_SLOTS 2
+#endif
+constexpr int BORROW_SLOTS = LZ4ADA_BORROW_SLOTS;
+static_assert(BORROW_SLOTS >= 0 && BORROW_SLOTS <= 2, "round 0's slots, or both rounds'");
+
 #ifndef LZ4ADA_FWD_ROUNDS
 #define LZ4ADA_FWD_ROUNDS 5
 #endif
@@ -2072,14 +2084,24 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		// HBM-sourced matches: every load in flight before the first use.  A
 		// match's first GC pieces load in its own lane; the pieces beyond
 		// (long matches) of both rounds are dealt over the wave, one per
-		// lane, through the LDS match descriptors (more than 64: the rest
-		// load in M, rare).
+		// lane, through the LDS match descriptors.  More than 64 is common
+		// where matches are long and far (over a third of the mixed class's
+		// batches, by about 7 pieces): the pieces beyond load here too, in
+		// lanes whose own slot vg[r][0] is idle because their match is not
+		// HBM-sourced (BORROW rounds' slots; off under quirk D1's prediction
+		// and in the zero plane).  Only what finds no idle slot loads in M.
+		const int BORROW = (D1E || ZL) ? 0 : BORROW_SLOTS;
 		u32x4 vg[RMAX][GC], vr = u32x4{0u, 0u, 0u, 0u};
 		int32_t rtot[RMAX], rfirst[RMAX];  // pieces beyond GC per round; the first not dealt here
 		int32_t rpd = 0, rpn = 0;          // this lane's dealt piece
+		// a piece beyond the 64 dealt ones, loaded into this lane's idle
+		// vg[r][0]: batch-relative output position (12 bits: a batch is at
+		// most OW bytes), length << 12 (0: none)
+		static_assert(OW <= 4096, "a borrowed piece's position takes 12 bits");
+		int32_t bpc[RMAX];
 #pragma unroll
 		for (int r = 0; r < RMAX; ++r)
-			rtot[r] = rfirst[r] = 0;
+			rtot[r] = rfirst[r] = bpc[r] = 0;
 		if (__any(anyg)) {
 			// the previous batch's flush (FLUSH_ST store instructions) and
 			// the input and record prefetch (3 loads, when this batch
@@ -2134,6 +2156,40 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 					rpd = od + 16 * k;
 					rpn = min(16, oml - 16 * k);
 					__builtin_memcpy(&vr, ob + (od - ooff) + 16 * k, 16);
+				}
+				if (tot > 64) {
+					ICOUNT(D_HOVF_B, 1);
+					ICOUNT(D_HOVF_P, tot - 64);
+				}
+				if (BORROW && tot > 64) {
+					// pieces 64 ..: one each to the lanes whose own-piece slot
+					// vg[r][0] is idle (the round's match is not HBM-sourced),
+					// round 0's idle lanes first, in lane order.  The idle lane
+					// of rank i takes piece first + i; its owner is entry i -
+					// 64 + first of the second chunk's owners.
+					const int32_t own2 = min(chunk_owner2(D, inc0, nc[0], inc1, nc[1], 64), 127);
+					int32_t first = 64;
+#pragma unroll
+					for (int r = 0; r < RMAX; ++r) {
+						if (r >= BORROW)
+							break;
+						const bool idle = 64 * r < N && !(rml[r] > 0 && rdst[r] + rL[r] - roff[r] < glo);
+						const uint64_t im = __ballot(idle);
+						const int32_t t = first + int32_t(__builtin_amdgcn_mbcnt_hi(
+						                              uint32_t(im >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(im), 0u)));
+						const int32_t bo = __shfl(own2, (t - 64) & 63);
+						if (idle && t < min(tot, 128)) {
+							const uint64_t bd = D.ldesc[bo];
+							const int32_t brel = int32_t(bd & 0xffffu), bml = int32_t((bd >> 32) & 0xffffu);
+							const int32_t bk = GC + t - int32_t(bd >> 48);
+							bpc[r] = (brel + 16 * bk) | (min(16, bml - 16 * bk) << 12);
+							__builtin_memcpy(&vg[r][0], ob + (o_batch + brel - int32_t((bd >> 16) & 0xffffu)) + 16 * bk,
+							                 16);
+						}
+						first = min(first + __popcll(im), min(tot, 128));
+					}
+					rfirst[0] = first;
+					rfirst[1] = max(first - tot0, 0);
 				}
 				wave_lds_fence();  // ldesc / own[] are written again later
 			}
@@ -2209,7 +2265,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				const int32_t mdst = rdst[r] + rL[r], off = roff[r], ml = rml[r];
 				const bool hbm = ml > 0 && mdst - off < glo;
 				static_assert(GC == 1, "one own HBM piece per match");
-				ostore(D, mdst, vg[r][0], hbm ? min(16, ml) : 0);
+				// (the slot of a match that is not HBM-sourced may hold a
+				// borrowed piece of another match instead: bpc, set in P)
+				ostore(D, hbm ? mdst : o_batch + (bpc[r] & 0xfff), vg[r][0], hbm ? min(16, ml) : bpc[r] >> 12);
 				int32_t xoff = off, xml = (ml > 0 && !hbm) ? ml : 0;  // its ring copy, if any
 				if (d1p) {
 					// quirk D1 (d1_emulable): the match's first k1 bytes are
@@ -2248,7 +2306,12 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 						__builtin_memcpy(&v, ob + gq, 16);
 					ostore(D, mdst, v, k1);
 				}
-				if (rtot[r] > rfirst[r]) {  // rare: more than 64 dealt pieces; the rest now
+				// dealt pieces that found no lane in P load now and are waited
+				// for on the spot (over a third of the mixed class's batches
+				// without BORROW)
+				if (rtot[r] > rfirst[r]) {
+					ICOUNT(D_HSLOW_B, r == 0 || rtot[0] <= rfirst[0]);
+					ICOUNT(D_HSLOW_P, rtot[r] - rfirst[r]);
 					const int32_t nc = hbm ? max(((ml + 15) >> 4) - GC, 0) : 0;
 					const int32_t inc = wave_incl_scan(nc);
 					for (int32_t t0 = rfirst[r]; t0 < rtot[r]; t0 += 64) {
@@ -2285,6 +2348,15 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			const int32_t st = ring_pieces(D, mring, oring, lring, o_batch, glo);
 			ICOUNT(D_TASKS, 1);
 			ICOUNT(D_ROUNDS, st);
+#ifdef LZ4ADA_IDX_STAMPS
+			{
+				const int32_t tot = __shfl(wave_incl_scan(match_pieces(oring[0], lring[0]) +
+				                                          match_pieces(oring[1], lring[1])), 63);
+				ICOUNT(D_RCHUNKS, (tot + 63) >> 6);
+				ICOUNT(D_ROVF_B, tot > 64);
+				ICOUNT(D_ROVF_P, max(tot - 64, 0));
+			}
+#endif
 			(void)st;
 		} else {
 #pragma unroll
@@ -2926,7 +2998,7 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 				const int32_t mdst = rdst[r] + rL[r];
 				if (hml[r] > 0)
 					ostore(V, mdst, vg[r], min(16, hml[r]));
-				if (rtot[r] > rfirst[r]) {  // rare: more than 64 dealt pieces; the rest now
+				if (rtot[r] > rfirst[r]) {  // more than 64 dealt pieces (common on mixed data); the rest now
 					const int32_t nc = hml[r] > 0 ? max(((hml[r] + 15) >> 4) - 1, 0) : 0;
 					const int32_t inc = wave_incl_scan(nc);
 					for (int32_t t0 = rfirst[r]; t0 < rtot[r]; t0 += 64) {

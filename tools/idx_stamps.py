@@ -22,9 +22,12 @@ import lz4ada  # noqa: E402
 
 NAMES = ["I_STAGE", "I_WALK0", "I_ITER", "I_CHUNKS", "I_ITERS",
          "D_STAGE", "D_WALK1", "D_WALK2", "D_TLDS", "D_LIT", "D_MFAR", "D_NEAR", "D_FLUSH", "D_GLOBAL",
-         "D_BATCHES", "D_GBATCHES", "D_ROUNDS", "D_TASKS", "D_LANES", "I_STEPS", "I_MAXST", "I_LEAD"]
+         "D_BATCHES", "D_GBATCHES", "D_ROUNDS", "D_TASKS", "D_LANES", "I_STEPS", "I_MAXST", "I_LEAD",
+         # pieces dealt past the wave's 64 lanes (IdxPhase, lz4ada_idx.hip)
+         "D_HOVF_B", "D_HOVF_P", "D_HSLOW_B", "D_HSLOW_P", "D_ROVF_B", "D_ROVF_P", "D_RCHUNKS"]
 COUNTS = {"I_CHUNKS", "I_ITERS", "D_BATCHES", "D_GBATCHES", "D_ROUNDS", "D_TASKS", "D_LANES",
-          "I_STEPS", "I_MAXST"}
+          "I_STEPS", "I_MAXST",
+          "D_HOVF_B", "D_HOVF_P", "D_HSLOW_B", "D_HSLOW_P", "D_ROVF_B", "D_ROVF_P", "D_RCHUNKS"}
 
 
 def main():
@@ -65,6 +68,14 @@ def main():
                         print(f"   {k:10s} {v[k] / nb:14.1f}")
                     else:
                         print(f"   {k:10s} {v[k] / nb:14.0f}  {100 * v[k] / max(tot, 1):5.1f}%")
+        nbat, ntask = max(v["D_BATCHES"], 1), max(v["D_TASKS"], 1)
+        print(f"   HBM-dealt pieces over 64: {100 * v['D_HOVF_B'] / nbat:.1f}% of batches, "
+              f"{v['D_HOVF_P'] / max(v['D_HOVF_B'], 1):.1f} pieces beyond each; "
+              f"loaded in M: {100 * v['D_HSLOW_B'] / nbat:.1f}% of batches, "
+              f"{v['D_HSLOW_P'] / max(v['D_HSLOW_B'], 1):.1f} pieces each")
+        print(f"   ring_pieces over 64: {100 * v['D_ROVF_B'] / ntask:.1f}% of calls, "
+              f"{v['D_ROVF_P'] / max(v['D_ROVF_B'], 1):.1f} pieces beyond each; "
+              f"{v['D_RCHUNKS'] / ntask:.2f} chunk passes per call")
         del fr, out
 
 
