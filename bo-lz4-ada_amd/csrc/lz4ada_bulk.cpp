@@ -211,14 +211,6 @@ static BulkResult bulk_independent(const uint8_t* d_frame, const uint8_t* host_f
 }
 
 
-// Which paths the last lz4ada_decode_* call on this thread took
-// (LZ4ADA_PATH_* bits; tests and diagnostics).
-static thread_local int g_last_path = 0;
-
-// for lz4ada_multi.cpp (lz4ada_internal.h)
-void set_thread_error(const std::string& msg) { g_thread_error = msg; }
-void set_last_path(int bits) { g_last_path = bits; }
-
 // The stream state before block `fail`, the first one the bulk path could
 // not take (its predecessors are committed): Output_Pos and
 // Output_Pos_History as lz4ada.adb:678-690 and 785-787 leave them.
@@ -326,8 +318,8 @@ static void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& 
 				rs.lens = &lens;
 				rs.at = int64_t(descs[size_t(fail)].in_off) - BLOCK_SIZE_BYTES;
 				rs.checksum_first = info.block_checksum != 0;
-				g_last_path |= LZ4ADA_PATH_EXACT |
-				               (linked ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT);
+				add_last_path(LZ4ADA_PATH_EXACT |
+				              (linked ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT));
 				phase("state");
 				try {
 					exact_frame(f, len, out, consumed, &rs);
@@ -345,7 +337,7 @@ static void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& 
 			if (r == BULK_OK && (!info.has_content_size || total == info.content_size) &&
 			    (!h || (total == 0 ? 0x02cc5d05u : hs.hash) == info.content_checksum_declared)) {
 				consumed = info.frame_len;
-				g_last_path |= linked ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT;
+				add_last_path(linked ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT);
 				return;
 			}
 			out.len = base;
@@ -355,7 +347,7 @@ static void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& 
 	// (what tool_unlz4ada's per-frame re-init achieves), so hand the exact
 	// path only this frame's bytes.
 	const int64_t flen = (indexed && info.format == LZ4ADA_FORMAT_LEGACY) ? info.frame_len : len;
-	g_last_path |= LZ4ADA_PATH_EXACT;
+	add_last_path(LZ4ADA_PATH_EXACT);
 	exact_frame(f, flen, out, consumed);
 }
 }  // namespace lz4ada
@@ -487,7 +479,7 @@ int lz4ada_decode_frame(const uint8_t* frame, int64_t len, uint8_t* out, int64_t
 {
 	*out_len = 0;
 	*frame_consumed = 0;
-	g_last_path = 0;
+	set_last_path(0);
 	return guarded(nullptr, [&] {
 		Sink s;
 		s.p = out;
@@ -501,7 +493,7 @@ int lz4ada_decode_stream(const uint8_t* input, int64_t len, uint8_t* out, int64_
                          int64_t* out_len)
 {
 	*out_len = 0;
-	g_last_path = 0;
+	set_last_path(0);
 	return guarded(nullptr, [&] {
 		Sink s;
 		s.p = out;
@@ -530,7 +522,7 @@ static int decode_alloc(const uint8_t* input, int64_t len, bool stream, uint8_t*
 		*consumed = 0;
 	Sink s;
 	s.growable = true;
-	g_last_path = 0;
+	set_last_path(0);
 	const int st = guarded(nullptr, [&] {
 		int64_t pos = 0;
 		do {
@@ -606,33 +598,9 @@ int lz4ada_decode_linked_device(const void* d_frame, uint64_t frame_len,
 	});
 }
 
-int lz4ada_last_path(void) { return g_last_path; }
-
 const char* lz4ada_bulk_decoder_kernel(int64_t nblocks)
 {
 	return idx_fused_kernel_name(uint32_t(std::max<int64_t>(nblocks, 0)));
-}
-
-void lz4ada_release_device_cache(void)
-{
-	scratch_release();
-	dev_pool().release_all();
-	pin_pool().release_all();
-	// the facade's pooled streams and events too
-	std::vector<StreamSet> sets;
-	{
-		std::lock_guard<std::mutex> l(g_stream_mu);
-		sets.swap(stream_pool());
-	}
-	int cur = 0;
-	(void)hipGetDevice(&cur);
-	for (auto& x : sets) {
-		(void)hipSetDevice(x.device);
-		(void)hipStreamDestroy(x.side);
-		(void)hipEventDestroy(x.ev);
-		(void)hipStreamDestroy(x.stream);
-	}
-	(void)hipSetDevice(cur);
 }
 
 int64_t lz4ada_decoded_bound(const uint8_t* input, int64_t len)

@@ -58,7 +58,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 	             o_ctr = o_mode + al(nmax), link_bytes = o_ctr + 256;
 	uint8_t* const lk = scratch(SC_LINK, link_bytes);
 	if (!lk)
-		return why(BULK_EXACT, "exit at line 61");
+		return why(BULK_EXACT, "scratch LINK alloc");
 	PinBuf& pin = scratch_cache().pin;
 	pin.reserve(link_bytes);
 	uint8_t* const hp = pin.p;  // host twin of lk: hp + o is the host side of lk + o
@@ -127,7 +127,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 				budget /= 2;
 				continue;
 			}
-			return why(BULK_EXACT, "exit at line 130");
+			return why(BULK_EXACT, "scratch X/Z/TAB alloc");
 		}
 		// planes x's and z's statuses side by side: one copy back
 		struct {
@@ -215,7 +215,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 			fail = int64_t(lo) + ok_n;
 			nb = ok_n;
 			if (nb == 0)
-				return why(BULK_FAIL_AT, "fail-at exit at line 211");
+				return why(BULK_FAIL_AT, "the batch's first block fails");
 		}
 		if (n >= (int64_t(1) << 31) - HISTORY_SIZE) {  // words hold positions + 65536 in 31 bits
 			if (nb > 1) {
@@ -227,7 +227,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 				oph = oph0;
 				continue;
 			}
-			return why(BULK_EXACT, "exit at line 223");
+			return why(BULK_EXACT, "positions overflow 31 bits");
 		}
 		// blocks plane z cannot serve alone: one that reads history positions
 		// below 256 (AUX_DEEP_HIST: their high byte is 0, like a literal's)
@@ -254,7 +254,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 			py = scratch(SC_Y, size_t(bytes));
 			ph = py && nh ? scratch(SC_H, size_t(bytes)) : nullptr;
 			if (!py || (nh && !ph))
-				return why(BULK_EXACT, "exit at line 250");
+				return why(BULK_EXACT, "plane Y/H alloc");
 			HIP_OK(hipMemcpyAsync(d_mode.p, mode, nb, hipMemcpyHostToDevice, stream));
 			HIP_OK(launch_link_fill(nullptr, py, ph, d_desc.p, nb, stream));
 			std::vector<lz4ada_block_status> s_plane[2];
@@ -293,7 +293,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 			uint32_t* p;
 		} d_P{ reinterpret_cast<uint32_t*>(scratch(SC_P, size_t(std::max<int64_t>(n, 1)) * 4)) };
 		if (!d_P.p)
-			return why(BULK_EXACT, "exit at line 289");
+			return why(BULK_EXACT, "scratch P alloc");
 		HIP_OK(hipMemcpyAsync(d_A.p, A, nb * sizeof(int64_t), hipMemcpyHostToDevice, stream));
 		const int64_t tail_valid = std::min<int64_t>(int64_t(total) + hist0, HISTORY_SIZE);
 		uint8_t* F = nullptr;
@@ -305,7 +305,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 			// bytes it resolves: the last round leaves the output
 			F = sink.dst(n);
 			if (!F)
-				return why(BULK_EXACT, "exit at line 301");
+				return why(BULK_EXACT, "sink has no room");
 			// span activity flags, double-buffered across rounds (an init that
 			// also stepped every history-derived byte one pointer forward was
 			// measured and dropped: mixed 10.32 vs 10.35 ms, chain 13.5 vs
@@ -315,7 +315,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 			uint8_t* act = scratch(SC_U, size_t(2 * ns + 64));
 			uint8_t* M = act ? scratch(SC_M, size_t(n) + 64) : nullptr;
 			if (!M)
-				return why(BULK_EXACT, "exit at line 311");
+				return why(BULK_EXACT, "scratch U/M alloc");
 			// init flags the spans that hold a history-derived byte: the
 			// first round reads only those
 			HIP_OK(hipMemsetAsync(act + ns, 0, size_t(ns), stream));
@@ -387,7 +387,7 @@ BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block
 		for (uint32_t i = 0; i < nb; ++i)
 			lens.push_back(st[i].out_len);
 		if (fail >= 0)
-			return why(BULK_FAIL_AT, "fail-at exit at line 383");
+			return why(BULK_FAIL_AT, "a block fails, the ones before it committed");
 		lo = hi;
 	}
 	return BULK_OK;

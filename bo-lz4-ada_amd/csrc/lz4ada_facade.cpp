@@ -81,18 +81,8 @@ struct lz4ada_decompressor {
 	~lz4ada_decompressor()
 	{
 		hash_wait();
-		if (!stream)
-			return;
-		// idle streams go back to the pool for the next context
-		const bool idle = hipStreamSynchronize(side) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess;
-		if (idle) {
-			std::lock_guard<std::mutex> l(g_stream_mu);
-			stream_pool().push_back(StreamSet{ device, stream, side, ev_in });
-		} else {
-			(void)hipStreamDestroy(side);
-			(void)hipEventDestroy(ev_in);
-			(void)hipStreamDestroy(stream);
-		}
+		if (stream)
+			give_streams(StreamSet{ device, stream, side, ev_in });
 	}
 
 	void ensure_device()
@@ -101,24 +91,12 @@ struct lz4ada_decompressor {
 			return;
 		device_check_or_raise();
 		HIP_OK(hipGetDevice(&device));
-		{
-			std::lock_guard<std::mutex> l(g_stream_mu);
-			auto& pool = stream_pool();
-			for (size_t i = 0; i < pool.size(); ++i)
-				if (pool[i].device == device) {
-					stream = pool[i].stream;
-					side = pool[i].side;
-					ev_in = pool[i].ev;
-					pool[i] = pool.back();
-					pool.pop_back();
-					break;
-				}
-		}
-		if (!stream) {
-			HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-			HIP_OK(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-			HIP_OK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
-		}
+		StreamSet s;
+		if (!take_streams(device, s))
+			raise(LZ4ADA_DEVICE_ERROR, "HIP error: the context's streams could not be created");
+		stream = s.stream;
+		side = s.side;
+		ev_in = s.ev;
 		d_tmp_hash.reserve(1);
 		d_serial.reserve(1);
 		d_desc.reserve(1);
@@ -934,8 +912,6 @@ const char* lz4ada_error_name(int status)
 	return names[status];
 }
 
-const char* lz4ada_thread_last_error(void) { return g_thread_error.c_str(); }
-
 const char* lz4ada_last_error(const lz4ada_decompressor* ctx) { return ctx ? ctx->err.c_str() : ""; }
 
 int64_t lz4ada_exact_blocks(const lz4ada_decompressor* ctx) { return ctx ? ctx->exact_blocks : -1; }
@@ -1205,7 +1181,7 @@ void lz4ada::exact_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& cons
 	lz4ada_decompressor* raw = nullptr;
 	int st = lz4ada_init_with_header(f, len, LZ4ADA_SINGLE_FRAME, &consumed, &mbs, &raw);
 	if (st)
-		raise(st, g_thread_error);
+		raise(st, lz4ada_thread_last_error());
 	std::unique_ptr<lz4ada_decompressor> ctx(raw);
 	std::vector<uint8_t> buf(size_t(mbs), 0);
 	int eof = LZ4ADA_EOF_NO;

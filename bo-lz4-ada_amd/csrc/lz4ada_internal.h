@@ -1,5 +1,8 @@
-// lz4ada_internal.h -- types shared by the host units (lz4ada_host_common.h, lz4ada_facade.cpp, lz4ada_bulk.cpp, lz4ada_bulk_linked.cpp)
-// and the gfx950 kernels (lz4ada_kernels.hip).  Not part of the public C-ABI.
+// lz4ada_internal.h -- what the host units (lz4ada_host_common.h/.cpp,
+// lz4ada_facade.cpp, lz4ada_bulk.cpp, lz4ada_bulk_linked.cpp,
+// lz4ada_multi.cpp) share with the gfx950 kernel files (lz4ada_*.hip): the
+// device status codes and the launchers' declarations.  Not part of the
+// public C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -286,10 +289,12 @@ hipError_t lone_scratch_init(void* d_scratch, hipStream_t stream);
 hipError_t launch_decode_lone_emit(int64_t n, uint8_t* d_out, int64_t cap, lz4ada_block_status* d_st,
                                    void* d_scratch, hipStream_t stream, int32_t H, uint8_t* h_out = nullptr);
 
-// host side (lz4ada_bulk.cpp): the calling thread's message for
-// lz4ada_thread_last_error() and its lz4ada_last_path() bits
+// host side (lz4ada_host_common.cpp): the calling thread's message for
+// lz4ada_thread_last_error() and its lz4ada_last_path() bits (set, or
+// added to what the call has set so far)
 void set_thread_error(const std::string& msg);
 void set_last_path(int bits);
+void add_last_path(int bits);
 
 hipError_t launch_compact(const uint8_t* d_src, const lz4ada_block_desc* d_desc,
                           const uint64_t* d_dst_off, const lz4ada_block_status* d_status,

@@ -216,6 +216,7 @@ _sig = {
     "lz4ada_last_path": ([], ctypes.c_int),
     "lz4ada_bulk_decoder_kernel": ([ctypes.c_int64], ctypes.c_char_p),
     "lz4ada_release_device_cache": ([], None),
+    "lz4ada_device_cache_stats": ([_vp], None),
     "lz4ada_decode_linked_device": ([_vp, ctypes.c_uint64, _vp, _i64, _i64, _vp, _i64, _pi64, _vp],
                                     ctypes.c_int),
     "lz4ada_decoded_bound": ([_vp, _i64], _i64),
@@ -529,8 +530,20 @@ def last_path() -> int:
 
 
 def release_device_cache():
-    """Free the bulk path's cached device scratch of the calling thread."""
+    """Free the bulk path's cached device scratch of the calling thread and
+    empty the process-wide memory pools and the stream pool."""
     _lib.lz4ada_release_device_cache()
+
+
+class CacheStats(ctypes.Structure):
+    _fields_ = [("device_idle_bytes", _i64), ("pinned_idle_bytes", _i64), ("idle_streams", _i64)]
+
+
+def device_cache_stats() -> CacheStats:
+    """What the pools hold idle: device bytes, pinned bytes, stream sets."""
+    s = CacheStats()
+    _lib.lz4ada_device_cache_stats(ctypes.byref(s))
+    return s
 
 
 def decode_blocks_device(d_frame: int, frame_len: int, d_descs: int, nblocks: int, d_out: int,

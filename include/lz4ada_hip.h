@@ -367,8 +367,18 @@ int lz4ada_decode_linked_device(const void *d_frame, uint64_t frame_len,
 int lz4ada_last_path(void);
 
 /* The bulk path keeps its large device scratch (output slots, linked-frame
- * decode copies) per thread between calls; this frees the calling thread's. */
+ * decode copies) per thread between calls; this frees the calling thread's,
+ * and empties the process-wide device / pinned memory pools and the stream
+ * pool that the streaming contexts and the bulk paths draw from. */
 void lz4ada_release_device_cache(void);
+
+/* What those pools hold idle right now (the per-thread scratch is not
+ * counted): bytes of device and of pinned host memory, and pooled sets of
+ * a context's two streams and event.  Reads counters only: no HIP call. */
+typedef struct {
+	int64_t device_idle_bytes, pinned_idle_bytes, idle_streams;
+} lz4ada_cache_stats;
+void lz4ada_device_cache_stats(lz4ada_cache_stats *out);
 
 /* Upper bound of the decoded size of a stream (sum of block maxima); -1 if
  * some frame does not index (then use the _alloc calls). */

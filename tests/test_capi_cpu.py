@@ -144,6 +144,22 @@ def test_decode_without_gpu_fails_loudly():
             pos += c
 
 
+def test_cache_stats_zero_in_a_fresh_process():
+    """device_cache_stats() reads the pools' counters without a HIP call: three
+    zeros before anything ran, and again after release_device_cache()."""
+    import subprocess
+    import sys
+    from conftest import PKG
+    code = ("import sys; sys.path.insert(0, %r); import lz4ada\n"
+            "for _ in range(2):\n"
+            "    s = lz4ada.device_cache_stats()\n"
+            "    print(s.device_idle_bytes, s.pinned_idle_bytes, s.idle_streams)\n"
+            "    lz4ada.release_device_cache()\n" % PKG)
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.split() == ["0"] * 6
+
+
 def test_cli_counterparts_built_and_fail_loudly_without_gpu():
     """unlz4ada / xxhash32ada (the reference's CLIs over the C-ABI) exist;
     without a GPU they report the device error instead of decoding on the
