@@ -1166,7 +1166,9 @@ __device__ __forceinline__ const uint32_t* plut_of(const LD&) { return nullptr; 
 // the window's size - 1 (a power of two) for a layout: ORING unless the
 // layout says otherwise (the pipelined pair's 16 KiB window)
 template <class LD>
-__device__ __forceinline__ constexpr uint32_t omask_of(const LD&) { return OMASK; }
+constexpr uint32_t omask_v = OMASK;
+template <class LD>
+__device__ __forceinline__ constexpr uint32_t omask_of(const LD&) { return omask_v<LD>; }
 
 // Exact store of n (0..16) bytes of v at p, without branches: each of the
 // five stores (16, 8, 4, 2, 1 bytes) goes to its place or, when n does not
@@ -1213,6 +1215,7 @@ __device__ __forceinline__ void ostore(LD& L, int32_t x, u32x4 v, int32_t n)
 	}
 	const uint64_t lo = uint64_t(v.x) | (uint64_t(v.y) << 32);
 	const uint64_t hi = uint64_t(v.z) | (uint64_t(v.w) << 32);
+#pragma clang loop vectorize(disable) unroll(disable)
 	for (int32_t i = 0; i < n; ++i) {
 		const uint64_t w = i < 8 ? lo : hi;
 		oring_of(L)[(a + uint32_t(i)) & omask_of(L)] = uint8_t(w >> (8 * (i & 7)));
@@ -1409,20 +1412,20 @@ __device__ __forceinline__ int32_t chunk_owner(LD& D, int32_t inc, int32_t np, i
 	return wave_incl_max(v);
 }
 
-// chunk_owner over two rounds' entries (round 0's lanes, then round 1's:
-// entry 64 r + lane holds pieces [inc_r - np_r, inc_r)), owner 0..127.
+// chunk_owner over two rounds' entries (round 0's lanes, then round 1's),
+// from each entry's first piece e and whether it has any (nz): entry
+// 64 r + lane holds pieces [e_r, e_r + its count), owner 0..127; seed is the
+// owner of piece t0.
 template <class LD>
-__device__ __forceinline__ int32_t chunk_owner2(LD& D, int32_t inc0, int32_t np0, int32_t inc1,
-                                                int32_t np1, int32_t t0)
+__device__ __forceinline__ int32_t chunk_owner_marks(LD& D, int32_t seed, int32_t e0, bool nz0, int32_t e1,
+                                                     bool nz1, int32_t t0)
 {
 	const int32_t lane = int32_t(lane_id());
-	const int32_t seed = __popcll(__ballot(inc0 <= t0)) + __popcll(__ballot(inc1 <= t0));
 	uint8_t* own = own_of(D);
 	own[lane] = uint8_t(lane == 0 ? seed : 0);
-	const int32_t e0 = inc0 - np0, e1 = inc1 - np1;
-	if (np0 > 0 && e0 >= t0 && e0 < t0 + 64)
+	if (nz0 && e0 >= t0 && e0 < t0 + 64)
 		own[e0 - t0] = uint8_t(lane);
-	if (np1 > 0 && e1 >= t0 && e1 < t0 + 64)
+	if (nz1 && e1 >= t0 && e1 < t0 + 64)
 		own[e1 - t0] = uint8_t(64 + lane);
 	wave_lds_fence();
 	const int32_t v = own[lane];
@@ -1430,13 +1433,24 @@ __device__ __forceinline__ int32_t chunk_owner2(LD& D, int32_t inc0, int32_t np0
 	return wave_incl_max(v);
 }
 
+// ... from the inclusive prefix sums and the counts (entry 64 r + lane holds
+// pieces [inc_r - np_r, inc_r))
+template <class LD>
+__device__ __forceinline__ int32_t chunk_owner2(LD& D, int32_t inc0, int32_t np0, int32_t inc1,
+                                                int32_t np1, int32_t t0)
+{
+	const int32_t seed = __popcll(__ballot(inc0 <= t0)) + __popcll(__ballot(inc1 <= t0));
+	return chunk_owner_marks(D, seed, inc0 - np0, np0 > 0, inc1 - np1, np1 > 0, t0);
+}
+
 // Every lane's match (dst, off, ml; ml = 0: none) with a source in the LDS
-// ring, cut into pieces dealt over the wave: 16 output bytes each, or stp
-// bytes of a period-off pattern (off < 16 < ml would overlap: match byte i
-// is source byte i mod off, so a piece never reads its own match's output).
-// Pieces are in output order; one reading output of a lower lane of its
-// chunk waits until that lane has stored (ballot per step).
-// Pieces of one match: 16-byte pieces, or stp-byte steps of a period-off
+// ring, cut into units of which ring_pieces deals two per piece over the
+// wave: 16 output bytes each, or stp bytes of a period-off pattern (off <
+// 16 < ml would overlap: match byte i is source byte i mod off, so a unit
+// never reads its own match's output).  Pieces are in output order; one
+// reading output of a lower lane of its chunk waits until that lane has
+// stored (ballot per step).
+// Units of one match: 16 bytes each, or stp-byte steps of a period-off
 // pattern (off < 16 < ml overlaps).
 __device__ __forceinline__ int32_t match_pieces(int32_t off, int32_t ml)
 {
@@ -1461,58 +1475,98 @@ static_assert(BORROW_SLOTS >= 0 && BORROW_SLOTS <= 2, "round 0's slots, or both 
 #define LZ4ADA_FWD_ROUNDS 5
 #endif
 constexpr int FWD_ROUNDS = LZ4ADA_FWD_ROUNDS;  // forwarding rounds of ring_lanes (0: none)
-// ... and of ring_pieces: off (mixed 13.17 -> 13.41 ms with it, dense
-// 37.07 -> 37.38: its dealt pieces rarely sit inside one producer piece,
-// and the set-up runs for every 64-piece chunk; profiles/r06i_ab.txt)
-#ifndef LZ4ADA_FWD_PIECES
-#define LZ4ADA_FWD_PIECES 0
-#endif
-constexpr int FWD_PIECES = LZ4ADA_FWD_PIECES;
+// (forwarding over ring_pieces' dealt pieces was measured and is gone: mixed
+// 13.17 -> 13.41 ms with it, dense 37.07 -> 37.38; profiles/r06i_ab.txt)
+
+// Dealt pieces of a ring-sourced match: two of match_pieces' units each
+// (32 output bytes, or two steps of a period-off pattern), so a batch of
+// mixed data deals ~48 pieces instead of ~71 and nearly always fits one
+// 64-piece chunk (ring_pieces' set-up runs once per chunk).
+__device__ __forceinline__ int32_t ring_piece_count(int32_t off, int32_t ml)
+{
+	return (match_pieces(off, ml) + 1) >> 1;
+}
+
+// chunk_owner2 from the entries' first pieces alone (e: exclusive prefix sum
+// of the piece counts, 16 bits per round in ee; nz: the entry has pieces):
+// the entries with inc <= t0 are those after the first with e <= t0 (entry
+// 0's e is 0, and piece t0 exists).
+template <class LD>
+__device__ __forceinline__ int32_t chunk_owner_e(LD& D, uint32_t ee, bool nz0, bool nz1, int32_t t0)
+{
+	const int32_t e0 = int32_t(ee & 0xffffu), e1 = int32_t(ee >> 16);
+	const int32_t seed = __popcll(__ballot(e0 <= t0)) + __popcll(__ballot(e1 <= t0)) - 1;
+	return chunk_owner_marks(D, seed, e0, nz0, e1, nz1, t0);
+}
+
+// Marks two registers as changed (no instruction): what is computed from
+// them after this point stays after it, instead of being hoisted out of the
+// loop around it and held in registers across it.
+__device__ __forceinline__ void step_state(uint32_t& a, uint32_t& b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
 // Both rounds' ring-sourced matches (round r: mdst[r], off[r], ml[r]; ml 0:
 // none), dealt together in output order; a piece finds its match in an LDS
 // descriptor (D.ldesc, free after the literals) instead of by shuffles.
+// Piece k of a match is its units 2k and 2k + 1 (match_pieces' units: 16
+// output bytes, or stp bytes' step of a period-off pattern).  With more
+// than 16 bytes left at its start it stores 16 whole bytes there and an
+// exact-length second unit ostp further on; else one exact-length unit.
+// Neither unit reads its own match's output (ring_match's rule), so a
+// piece waits only for the lower pieces of its chunk that write into the
+// source of either unit.
 template <class LD>
 __device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX],
                                                const int32_t (&off)[RMAX], const int32_t (&ml)[RMAX],
-                                               int32_t o_batch, int32_t glo = INT32_MIN)
+                                               int32_t o_batch)
 {
 	int32_t steps = 0;  // store steps (diagnostic count)
 	const int32_t lane = int32_t(lane_id());
-	const int32_t np0 = match_pieces(off[0], ml[0]), np1 = match_pieces(off[1], ml[1]);
-	const int32_t inc0 = wave_incl_scan(np0);
-	const int32_t tot0 = __shfl(inc0, 63);
-	const int32_t inc1 = tot0 + wave_incl_scan(np1);
-	const int32_t tot = __shfl(inc1, 63);
-	auto pack = [&](int32_t md, int32_t of, int32_t m, int32_t excl) -> uint64_t {
-		return uint64_t(uint16_t(md - o_batch)) | (uint64_t(uint16_t(of)) << 16) |
-		       (uint64_t(uint16_t(m)) << 32) | (uint64_t(uint16_t(excl)) << 48);
-	};
-	uint64_t* ldesc = ldesc_of(D);
-	ldesc[lane] = pack(mdst[0], off[0], ml[0], inc0 - np0);
-	ldesc[64 + lane] = pack(mdst[1], off[1], ml[1], inc1 - np1);
+	const bool nz0 = ml[0] > 0, nz1 = ml[1] > 0;
+	int32_t tot;
+	uint32_t ee;  // the entries' first pieces, both rounds (inc* / np* end here)
+	{
+		const int32_t np0 = ring_piece_count(off[0], ml[0]), np1 = ring_piece_count(off[1], ml[1]);
+		const int32_t inc0 = wave_incl_scan(np0);
+		const int32_t tot0 = __shfl(inc0, 63);
+		const int32_t inc1 = tot0 + wave_incl_scan(np1);
+		tot = __shfl(inc1, 63);
+		auto pack = [&](int32_t md, int32_t of, int32_t m, int32_t excl) -> uint64_t {
+			return uint64_t(uint16_t(md - o_batch)) | (uint64_t(uint16_t(of)) << 16) |
+			       (uint64_t(uint16_t(m)) << 32) | (uint64_t(uint16_t(excl)) << 48);
+		};
+		uint64_t* ldesc = ldesc_of(D);
+		ldesc[lane] = pack(mdst[0], off[0], ml[0], inc0 - np0);
+		ldesc[64 + lane] = pack(mdst[1], off[1], ml[1], inc1 - np1);
+		ee = uint32_t(inc0 - np0) | (uint32_t(inc1 - np1) << 16);
+	}
 	for (int32_t t0 = 0; t0 < tot; t0 += 64) {
 		const int32_t t = t0 + lane;
 		const bool act = t < tot;
-		const int32_t lo = min(chunk_owner2(D, inc0, np0, inc1, np1, t0), 127);
-		const uint64_t dd = ldesc[lo];
+		const int32_t lo = min(chunk_owner_e(D, ee, nz0, nz1, t0), 127);
+		const uint64_t dd = ldesc_of(D)[lo];
 		const int32_t od = o_batch + int32_t(dd & 0xffffu);
 		const int32_t ooff = int32_t((dd >> 16) & 0xffffu), oml = int32_t((dd >> 32) & 0xffffu);
 		const int32_t k = t - int32_t(dd >> 48);
 		const bool opat = ooff < 16 && ooff < oml;
 		const int32_t ostp = opat ? pattern_step(ooff) : 16;
 		const bool wide = !opat && oml > ooff;  // overlap with off >= 16
-		const int32_t pd = od + k * ostp;
-		const int32_t pn = min(16, oml - k * ostp);
+		const int32_t base = 2 * k * ostp;       // the piece's first output byte in its match
+		const int32_t pd = od + base;
+		const int32_t left = oml - base;
+		const bool two = left > 16;
+		// the exact-length store: the second unit's bytes, or the whole piece
+		const int32_t pd2 = two ? pd + ostp : pd;
+		const int32_t n2 = two ? min(16, left - ostp) : left;
+		const int32_t pe_ = pd2 + n2;  // the piece writes [pd, pe_)
 		// source bytes read: the whole period for patterns and overlaps
-		const int32_t s_lo = (opat || wide) ? od - ooff : od - ooff + 16 * k;
-		const int32_t s_hi = (opat || wide) ? od : s_lo + pn;
-		// lanes of this chunk whose piece [pd, pd + pn) meets [s_lo, s_hi):
+		const int32_t s_lo = (opat || wide) ? od - ooff : od - ooff + base;
+		const int32_t s_hi = (opat || wide) ? od : s_lo + (pe_ - pd);
+		// lanes of this chunk whose piece [pd, pe_) meets [s_lo, s_hi):
 		// pd is monotone over the lanes, so two binary searches -- skipped
 		// when every source ends before the chunk's first piece
-		// a piece writes [pd, pd + pn): its end, not pd + 16 (a short last piece
-		// must not hold back a source that only starts after it)
-		const int32_t pe = act ? pd + pn : INT32_MAX, ps = act ? pd : INT32_MAX;
+		// (a piece's real end, not pd + 32: a short last piece must not hold
+		// back a source that only starts after it)
+		const int32_t pe = act ? pe_ : INT32_MAX, ps = act ? pd : INT32_MAX;
 		int32_t fj1 = 64, fj2 = -1;  // the chunk's pieces that write this one's source (none)
 		if (!__all(!act || s_hi <= __shfl(ps, 0))) {
 			int32_t j1 = 0, c2 = 0;
@@ -1526,70 +1580,87 @@ __device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX
 			fj1 = j1;
 			fj2 = min(c2 - 1, lane - 1);
 		}
-		// Forwarding (ring_lanes' pointer jumping, per piece): a piece whose
-		// source [s_lo, s_hi) lies inside ONE earlier piece P of the chunk, P
-		// a plain copy (out[y] = out[y - sh_P] over its bytes, sh_P = its
-		// offset plus its own forwarding), reads F bytes further back
-		// instead and waits for P's producers; every read form shifts as a
-		// whole (a pattern's period, an overlap's two reads)
-		int32_t F = 0;
-		if (FWD_PIECES > 0 && glo != INT32_MIN) {
-			const bool plain = act && !opat && !wide;
-			int32_t sh = ooff;
-			const int32_t q0 = __shfl(ps, fj1), qe = __shfl(pe, fj1);
-			bool fw = act && fj1 == fj2 && q0 <= s_lo && s_hi <= qe && __shfl(int32_t(plain), fj1) != 0;
-			for (int r = 0; r < FWD_PIECES && __any(fw); ++r) {
-				const int32_t p = fj1;
-				const int32_t qs = __shfl(sh, p), q1 = __shfl(fj1, p), q2 = __shfl(fj2, p);
-				const bool qf = __shfl(int32_t(fw), p) != 0;
-				if (fw && s_lo - F - qs >= glo) {
-					F += qs;
-					sh = ooff + F;
-					fj1 = q1;  // P's producers (none: q1 > q2, the source is final)
-					fj2 = q2;
-					fw = qf;
-				} else {
-					fw = false;
-				}
-			}
-		}
 		uint64_t dep = 0;
 		if (act && fj1 <= fj2)
 			dep = (fj2 == 63 ? ~uint64_t(0) : ((uint64_t(2) << fj2) - 1)) & ~((uint64_t(1) << fj1) - 1);
-		// the piece's reads, fixed before the steps: 16 bytes at a1 and, for
-		// an overlap with off >= 16 whose unit wraps the period, the bytes
-		// from cut on at a1 - off (one load for every form: divergent
-		// per-form loads made a step run up to three of them in turn)
-		int32_t rem = 0;
-		if (wide)
-			div_small(16 * k, ooff, rem);
-		const int32_t a1 = (opat ? od - ooff : (wide ? od - ooff + rem : s_lo)) - F;
-		const int32_t cut = (wide && ooff - rem < 16) ? ooff - rem : 16;
+		// the piece's reads, fixed before the steps: per unit 16 bytes at a
+		// and, for an overlap with off >= 16 whose unit wraps the period, the
+		// bytes from cut on at a - off.  The second unit begins 16 bytes on
+		// in the period: at a1 + 16, or off before that once past its end.
+		// The step loop is the kernel's register peak, and every address,
+		// select and mask the loads and stores derive from these values
+		// would be hoisted out of it, so they cross it packed in two
+		// registers the compiler must take as changing (step_state): a step
+		// unpacks what it needs.
+		//   sa: a1 (ring address, 14 bits) | pd (ring address) << 14 | (ostp - 1) << 28
+		//   sb: off | cut1 << 16 | cut2 << 21 | n2 << 26 | (the second unit wraps) << 31
+		static_assert(omask_v<LD> < (1u << 14), "ring addresses pack into 14 bits");
+		uint32_t sa, sb;
+		{
+			int32_t rem = 0;
+			if (wide)
+				div_small(base, ooff, rem);
+			const int32_t a1 = opat ? od - ooff : (wide ? od - ooff + rem : s_lo);
+			const int32_t cut1 = (wide && ooff - rem < 16) ? ooff - rem : 16;
+			const bool wrap2 = wide && rem + 16 >= ooff;
+			const int32_t rem2 = rem + 16 - (wrap2 ? ooff : 0);
+			const int32_t cut2 = (wide && ooff - rem2 < 16) ? ooff - rem2 : 16;
+			sa = (uint32_t(a1) & omask_of(D)) | ((uint32_t(pd) & omask_of(D)) << 14) | (uint32_t(ostp - 1) << 28);
+			sb = uint32_t(ooff) | (uint32_t(cut1) << 16) | (uint32_t(cut2) << 21) | (uint32_t(max(n2, 0)) << 26) |
+			     (uint32_t(wrap2) << 31);
+		}
+		const bool ld2 = two && !opat;  // a pattern's second unit is its first
 		bool pend = act;
 		for (;;) {
 			const uint64_t pm = __ballot(pend);
 			if (pm == 0)
 				break;
 			const bool ready = pend && (dep & pm) == 0;
+			step_state(sa, sb);
+			const int32_t xa1 = int32_t(sa & 0x3fffu), xpd = int32_t((sa >> 14) & 0x3fffu);
+			const int32_t xoff = int32_t(sb & 0xffffu), xcut1 = int32_t((sb >> 16) & 31u);
+			const int32_t xcut2 = int32_t((sb >> 21) & 31u), xn2 = int32_t((sb >> 26) & 31u);
+			const int32_t xa2 = xa1 + 16 - (int32_t(sb) < 0 ? xoff : 0);
+			const int32_t xpd2 = two ? xpd + int32_t(sa >> 28) + 1 : xpd;
 			if constexpr (lds_fast<LD>::value) {
 				// every lane loads and stores (a lane not ready stores
-				// nothing: n = 0 sends its stores to the junk bytes)
-				u32x4 v = oload16(D, a1);
-				if (ready && cut < 16)
-					v = merge_at(v, oload16(D, a1 - ooff), cut);
+				// nothing: its stores go to the junk bytes)
+				u32x4 v = oload16(D, xa1);
+				if (ready && xcut1 < 16)
+					v = merge_at(v, oload16(D, xa1 - xoff), xcut1);
 				if (ready && opat)
-					v = pattern_perm(v, ooff, plut_of(D));
-				ostore(D, pd, v, ready ? pn : 0);
+					v = pattern_perm(v, xoff, plut_of(D));
+				// the first unit of two: 16 whole bytes in one store (one wrapping
+				// the ring's end takes ostore's byte loop)
+				if (__builtin_expect(!__any(ready && two && uint32_t(xpd) + 16u > omask_of(D) + 1), 1))
+					__builtin_memcpy((ready && two) ? &oring_of(D)[xpd] : junk_of(D), &v, 16);
+				else
+					ostore(D, xpd, v, (ready && two) ? 16 : 0);
+				if (__any(ready && ld2)) {
+					u32x4 w = oload16(D, xa2);
+					if (ready && ld2 && xcut2 < 16)
+						w = merge_at(w, oload16(D, xa2 - xoff), xcut2);
+					if (ld2)
+						v = w;
+				}
+				ostore(D, xpd2, v, ready ? xn2 : 0);
 			} else if (ready) {
-				u32x4 v = oload16(D, a1);
-				if (cut < 16)
-					v = merge_at(v, oload16(D, a1 - ooff), cut);
+				u32x4 v = oload16(D, xa1);
+				if (xcut1 < 16)
+					v = merge_at(v, oload16(D, xa1 - xoff), xcut1);
 				if (opat) {
 					int32_t sstp;
 					make_pattern16(uint64_t(v.x) | (uint64_t(v.y) << 32),
-					               uint64_t(v.z) | (uint64_t(v.w) << 32), ooff, v, sstp);
+					               uint64_t(v.z) | (uint64_t(v.w) << 32), xoff, v, sstp);
 				}
-				ostore(D, pd, v, pn);
+				if (two)
+					ostore(D, xpd, v, 16);
+				if (ld2) {
+					v = oload16(D, xa2);
+					if (xcut2 < 16)
+						v = merge_at(v, oload16(D, xa2 - xoff), xcut2);
+				}
+				ostore(D, xpd2, v, xn2);
 			}
 			pend = pend && !ready;
 			wave_lds_fence();
@@ -2345,13 +2416,13 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		// masks) would dominate there
 		static_assert(RMAX == 2, "ring dealing pairs two rounds");
 		if (__any(lring[0] > RING_LANE_MAX || lring[1] > RING_LANE_MAX)) {
-			const int32_t st = ring_pieces(D, mring, oring, lring, o_batch, glo);
+			const int32_t st = ring_pieces(D, mring, oring, lring, o_batch);
 			ICOUNT(D_TASKS, 1);
 			ICOUNT(D_ROUNDS, st);
 #ifdef LZ4ADA_IDX_STAMPS
 			{
-				const int32_t tot = __shfl(wave_incl_scan(match_pieces(oring[0], lring[0]) +
-				                                          match_pieces(oring[1], lring[1])), 63);
+				const int32_t tot = __shfl(wave_incl_scan(ring_piece_count(oring[0], lring[0]) +
+				                                          ring_piece_count(oring[1], lring[1])), 63);
 				ICOUNT(D_RCHUNKS, (tot + 63) >> 6);
 				ICOUNT(D_ROVF_B, tot > 64);
 				ICOUNT(D_ROVF_P, max(tot - 64, 0));
@@ -2571,7 +2642,8 @@ __device__ __forceinline__ uint8_t* oring_of(WP2& V) { return V.L.oring; }
 __device__ __forceinline__ const uint8_t* oring_of(const WP2& V) { return V.L.oring; }
 __device__ __forceinline__ uint8_t* own_of(WP2& V) { return V.L.own[V.w]; }
 __device__ __forceinline__ uint64_t* ldesc_of(WP2& V) { return V.L.ldesc[V.w]; }
-__device__ __forceinline__ constexpr uint32_t omask_of(const WP2&) { return ORING2 - 1; }
+template <>
+constexpr uint32_t omask_v<WP2> = ORING2 - 1;
 
 __device__ __forceinline__ int32_t lds_peek(const int32_t* p)
 {
@@ -3030,7 +3102,7 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 		}
 		static_assert(RMAX == 2, "ring dealing pairs two rounds");
 		if (__any(lring[0] > RING_LANE_MAX || lring[1] > RING_LANE_MAX)) {
-			ring_pieces(V, mring, oring, lring, ob0, ob0 - RFLOOR2);
+			ring_pieces(V, mring, oring, lring, ob0);
 		} else {
 #pragma unroll
 			for (int r = 0; r < RMAX; ++r)
