@@ -66,4 +66,24 @@ package body LZ4Ada.GPU is
 		Frame_Consumed := C;
 	end Decode_Frame_Multi;
 
+	procedure Decode_Frames(Jobs:          in out Frame_Jobs;
+				Output:        out    System.Address;
+				Output_Length: out    Interfaces.Integer_64) is
+		P: aliased System.Address;
+		L: aliased Interfaces.Integer_64;
+	begin
+		Check(C_Decode_Frames(Jobs'Address, Jobs'Length, P'Access, L'Access));
+		Output        := P;
+		Output_Length := L;
+	end Decode_Frames;
+
+	function Frames_Error(Jobs: in Frame_Jobs; I: in Positive) return String is
+		function C_Frames_Error(J: Interfaces.Integer_64)
+				return Interfaces.C.Strings.chars_ptr;
+		pragma Import(C, C_Frames_Error, "lz4ada_frames_error");
+	begin
+		return Interfaces.C.Strings.Value(C_Frames_Error(
+				Interfaces.Integer_64(I - Jobs'First)));
+	end Frames_Error;
+
 end LZ4Ada.GPU;

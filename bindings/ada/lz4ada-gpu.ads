@@ -31,6 +31,37 @@ package LZ4Ada.GPU is
 				Output_Length:  out    Interfaces.Integer_64;
 				Frame_Consumed: out    Interfaces.Integer_64);
 
+	-- lz4ada_decode_frames: many independent frames in as few device
+	-- passes as the byte budget allows, a result per frame (lz4ada_frame_job
+	-- of include/lz4ada_hip.h).  The caller fills Frame and Len; every
+	-- other component is output.  Status is the lz4ada_status of that frame
+	-- alone (0: decoded; Frames_Error gives the reference's message
+	-- otherwise), so one bad frame does not cost the others.
+	type Frame_Job is record
+		Frame:    System.Address;
+		Len:      Interfaces.Integer_64;
+		Out_Off:  Interfaces.Integer_64;
+		Out_Len:  Interfaces.Integer_64;
+		Consumed: Interfaces.Integer_64;
+		Status:   Interfaces.Integer_32;
+		Path:     Interfaces.Integer_32;
+	end record;
+	pragma Convention(C, Frame_Job);
+	type Frame_Jobs is array(Positive range <>) of aliased Frame_Job;
+	pragma Convention(C, Frame_Jobs);
+
+	-- Raises only when the call itself failed.  Output is allocated by the
+	-- library (Output_Length bytes, every job's bytes at its Out_Off);
+	-- release it with Buffer_Free.
+	procedure Decode_Frames(Jobs:          in out Frame_Jobs;
+				Output:        out    System.Address;
+				Output_Length: out    Interfaces.Integer_64);
+	-- lz4ada_frames_error: the message of job I (Jobs'First based) of the
+	-- last Decode_Frames call of this task's thread.
+	function Frames_Error(Jobs: in Frame_Jobs; I: in Positive) return String;
+	procedure Buffer_Free(P: in System.Address);
+	pragma Import(C, Buffer_Free, "lz4ada_buffer_free");
+
 	-- lz4ada_rccl_version: the RCCL this process bound (22606 = 2.26.6).
 	function RCCL_Version return Interfaces.Integer_32;
 	pragma Import(C, RCCL_Version, "lz4ada_rccl_version");
@@ -59,5 +90,11 @@ private
 			Out_Len, Consumed: access Interfaces.Integer_64)
 			return Interfaces.Integer_32;
 	pragma Import(C, C_Decode_Frame_Multi, "lz4ada_decode_frame_multi");
+
+	function C_Decode_Frames(Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Out_Buf: access System.Address;
+			Out_Len: access Interfaces.Integer_64)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Decode_Frames, "lz4ada_decode_frames");
 
 end LZ4Ada.GPU;

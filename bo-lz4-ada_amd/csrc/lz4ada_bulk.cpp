@@ -16,8 +16,8 @@ namespace lz4ada {
 
 // Walk one frame's block size words (Try_Detect_Input_Length semantics,
 // lz4ada.adb:525-585, under Init_With_Header(Single_Frame)).
-static void index_frame(const uint8_t* f, int64_t len, lz4ada_frame_info& info,
-                        std::vector<lz4ada_block_desc>* descs)
+void index_frame(const uint8_t* f, int64_t len, lz4ada_frame_info& info,
+                 std::vector<lz4ada_block_desc>* descs)
 {
 	memset(&info, 0, sizeof info);
 	if (len < 7)
@@ -232,7 +232,7 @@ static void resume_state(const std::vector<uint32_t>& lens, Resume& rs)
 // the frame indexes cleanly, else -- or when the bulk path finds anything
 // the reference would report or treat differently -- the exact path, which
 // raises the reference's exception in the reference's order.
-static void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consumed)
+void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consumed)
 {
 	lz4ada_frame_info info;
 	std::vector<lz4ada_block_desc> descs;
@@ -350,6 +350,15 @@ static void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& 
 	add_last_path(LZ4ADA_PATH_EXACT);
 	exact_frame(f, flen, out, consumed);
 }
+
+// A stream's next frame starts with fewer than 7 bytes left: what the
+// reference CLI raises there (tool_unlz4ada/unlz4ada.adb:65-76), before
+// Init_With_Header's precondition (lz4ada.ads:243) would.
+void partial_frame_check(int64_t left)
+{
+	if (left < 7)
+		raise(LZ4ADA_CONSTRAINT_ERROR, "Partial frame detected. Unable to process all data");
+}
 }  // namespace lz4ada
 
 extern "C" {
@@ -465,15 +474,6 @@ int lz4ada_output_checksums_device(const void* d_out, const lz4ada_block_desc* d
 	});
 }
 
-// A stream's next frame starts with fewer than 7 bytes left: what the
-// reference CLI raises there (tool_unlz4ada/unlz4ada.adb:65-76), before
-// Init_With_Header's precondition (lz4ada.ads:243) would.
-static void partial_frame_check(int64_t left)
-{
-	if (left < 7)
-		raise(LZ4ADA_CONSTRAINT_ERROR, "Partial frame detected. Unable to process all data");
-}
-
 int lz4ada_decode_frame(const uint8_t* frame, int64_t len, uint8_t* out, int64_t out_cap,
                         int64_t* out_len, int64_t* frame_consumed)
 {
@@ -498,16 +498,7 @@ int lz4ada_decode_stream(const uint8_t* input, int64_t len, uint8_t* out, int64_
 		Sink s;
 		s.p = out;
 		s.cap = out_cap;
-		int64_t pos = 0;
-		while (pos < len) {
-			int64_t c = 0;
-			partial_frame_check(len - pos);
-			decode_one_frame(input + pos, len - pos, s, c);
-			*out_len = s.len;
-			if (c <= 0)
-				raise(LZ4ADA_CONSTRAINT_ERROR, "decoder made no progress");
-			pos += c;
-		}
+		decode_stream_frames(input, len, s, out_len);
 	});
 }
 
@@ -524,18 +515,18 @@ static int decode_alloc(const uint8_t* input, int64_t len, bool stream, uint8_t*
 	s.growable = true;
 	set_last_path(0);
 	const int st = guarded(nullptr, [&] {
-		int64_t pos = 0;
-		do {
-			int64_t c = 0;
-			if (stream)
-				partial_frame_check(len - pos);
-			decode_one_frame(input + pos, len - pos, s, c);
-			if (c <= 0)
-				raise(LZ4ADA_CONSTRAINT_ERROR, "decoder made no progress");
-			pos += c;
-		} while (stream && pos < len);
+		if (stream) {
+			if (len <= 0)  // this entry has always looked for a first frame
+				partial_frame_check(len);
+			decode_stream_frames(input, len, s, nullptr);
+			return;
+		}
+		int64_t c = 0;
+		decode_one_frame(input, len, s, c);
+		if (c <= 0)
+			raise(LZ4ADA_CONSTRAINT_ERROR, "decoder made no progress");
 		if (consumed)
-			*consumed = pos;
+			*consumed = c;
 	});
 	if (st != LZ4ADA_OK) {
 		if (keep_partial) {  // what the reference had output before it raised

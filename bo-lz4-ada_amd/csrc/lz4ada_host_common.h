@@ -7,7 +7,8 @@
 // instance of the shared state and every non-template body.  Units that
 // include it: lz4ada_facade.cpp (the streaming Update facade and the
 // XXHash32 C-ABI), lz4ada_bulk.cpp (the bulk frame paths and their C-ABI),
-// lz4ada_bulk_linked.cpp (the linked-frame bulk path).  lz4ada_multi.cpp
+// lz4ada_bulk_linked.cpp (the linked-frame bulk path), lz4ada_bulk_frames.cpp
+// (many frames in one device pass).  lz4ada_multi.cpp
 // (the multi-GPU entry) keeps a per-device cache of its own and includes
 // only lz4ada_internal.h.
 //
@@ -379,8 +380,11 @@ inline bool try_reserve(DevBuf<T>& b, size_t count)
 // and a first-touch each time otherwise -- more than the decode itself on a
 // 1 GiB linked frame.  lz4ada_release_device_cache() frees them.  The
 // cache is never destroyed at thread exit (the HIP runtime may be gone).
+// SC_BATCH / SC_BATCH_META: a many-frame pass's compacted output and its
+// per-block / per-frame arrays (lz4ada_bulk_frames.cpp), which outlive the
+// single-frame decodes of the frames the pass did not find good.
 enum ScratchRole { SC_FRAME, SC_OUT, SC_COMPACT, SC_X, SC_Y, SC_H, SC_Z, SC_TAB, SC_P, SC_F, SC_LONE, SC_U,
-	           SC_LINK, SC_M, SC_N };
+	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_N };
 struct ScratchCache {
 	DevBuf<uint8_t> b[SC_N];
 	PinBuf pin;  // the linked path's small host transfers (pinned: no staging copy)
@@ -420,6 +424,24 @@ void exact_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consumed_tot
 // (lz4ada_facade.cpp); host_out gets the bytes on the way (may be null).
 void content_xxh32_d2h(lz4ada_xxh32_state& h, const uint8_t* d_data, int64_t len, uint8_t* host_out,
                        hipStream_t stream);
+
+// ------------------------------------------ frames, one at a time or many
+
+// Walk one frame's block size words (lz4ada_bulk.cpp); descs may be null.
+void index_frame(const uint8_t* f, int64_t len, lz4ada_frame_info& info,
+                 std::vector<lz4ada_block_desc>* descs);
+// One frame from host memory (Single_Frame semantics) through the bulk
+// paths or the exact path: the reference's output or exception
+// (lz4ada_bulk.cpp).
+void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consumed);
+// A stream's next frame starts with fewer than 7 bytes left.
+void partial_frame_check(int64_t left);
+// Every frame of a concatenated stream into `out`, committed in order
+// (lz4ada_bulk_frames.cpp): runs of batchable frames in one device pass
+// each, every other frame by decode_one_frame.  *committed (may be null)
+// follows out.len after each frame or run that succeeded; the first failing
+// frame's exception propagates.
+void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t* committed);
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

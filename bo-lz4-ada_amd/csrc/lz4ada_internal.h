@@ -1,8 +1,8 @@
 // lz4ada_internal.h -- what the host units (lz4ada_host_common.h/.cpp,
 // lz4ada_facade.cpp, lz4ada_bulk.cpp, lz4ada_bulk_linked.cpp,
-// lz4ada_multi.cpp) share with the gfx950 kernel files (lz4ada_*.hip): the
-// device status codes and the launchers' declarations.  Not part of the
-// public C-ABI.
+// lz4ada_bulk_frames.cpp, lz4ada_multi.cpp) share with the gfx950 kernel
+// files (lz4ada_*.hip): the device status codes and the launchers'
+// declarations.  Not part of the public C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -299,5 +299,47 @@ void add_last_path(int bits);
 hipError_t launch_compact(const uint8_t* d_src, const lz4ada_block_desc* d_desc,
                           const uint64_t* d_dst_off, const lz4ada_block_status* d_status,
                           uint32_t nblocks, uint8_t* d_dst, hipStream_t stream);
+
+// ---- many frames in one pass (lz4ada_frames.hip, lz4ada_xxh32.hip) ----
+// One frame of a pass.  The host fills first / nblocks / flags /
+// content_size; k_frames_plan fills out_off / out_len / fail / verdict from
+// the block statuses, k_xxh32_spans fills hash.
+constexpr uint32_t FRAME_HAS_SIZE = 1u;   // content_size is declared
+constexpr uint32_t FRAME_HAS_CKSUM = 2u;  // C.Checksum
+constexpr int32_t FRAME_SIZE_BAD = 1;     // verdict: out_len != content_size
+constexpr int32_t FRAME_GPU_HASHED = 2;   // verdict: hash holds XXH32 of the frame's output
+struct FrameRec {
+	uint32_t first, nblocks;  // its blocks among the pass's
+	uint32_t flags;           // FRAME_HAS_*
+	uint32_t hash;
+	uint64_t content_size;
+	uint64_t out_off, out_len;  // its bytes in the compacted output
+	int32_t fail;               // first failing block (frame-relative), -1: none
+	int32_t verdict;            // FRAME_SIZE_BAD | FRAME_GPU_HASHED
+};
+// Blocks per workgroup of the scan's first level.
+constexpr uint32_t PLAN_TILE = 1024;
+__host__ __device__ inline uint32_t plan_tiles(uint32_t nblocks)
+{
+	return (nblocks + PLAN_TILE - 1) / PLAN_TILE;
+}
+// The pass's layout, from the device-resident statuses: d_dst_off[0 ..
+// nblocks] gets the exclusive prefix sum of the blocks' decoded lengths
+// (entry nblocks: the total) -- what launch_compact reads -- and every
+// frame record its span, first failing block and content-size verdict.  A
+// block with a non-zero code, a length over its slot or a block checksum
+// unequal to the declared one counts as failing and as 0 bytes (its
+// out_len is set to 0, so launch_compact copies nothing of it; the host sets
+// every record's fail to -1 beforehand).  Scratch: d_loc, nblocks words, and
+// d_part, plan_tiles(nblocks) + 1 words.  nblocks may be 0.
+hipError_t launch_frames_plan(const lz4ada_block_desc* d_desc, lz4ada_block_status* d_status,
+                              uint32_t nblocks, FrameRec* d_frames, uint32_t nframes,
+                              uint64_t* d_dst_off, uint64_t* d_loc, uint64_t* d_part,
+                              hipStream_t stream);
+// XXH32 of every frame's compacted output that has C.Checksum, no failing
+// block and at most hash_max bytes, into its record (FRAME_GPU_HASHED set);
+// four frames per wave.
+hipError_t launch_xxh32_spans(const uint8_t* d_buf, FrameRec* d_frames, uint32_t nframes,
+                              uint64_t hash_max, hipStream_t stream);
 
 }  // namespace lz4ada

@@ -329,6 +329,34 @@ __global__ __launch_bounds__(64) void k_xxh32_rows(const uint8_t* __restrict__ f
 	}
 }
 
+// Content checksums of a pass of many frames (lz4ada_bulk_frames.cpp): N
+// frames are N independent chains, so each 16-lane row hashes one frame's
+// span of the compacted output -- any start alignment, any length.  A frame
+// is hashed when it has C.Checksum, no failing block and at most hash_max
+// bytes (longer ones: the host chain while their bytes are copied out).
+__global__ __launch_bounds__(64) void k_xxh32_spans(const uint8_t* __restrict__ buf, FrameRec* fr,
+                                                    uint32_t nframes, uint64_t hash_max)
+{
+	const uint32_t lane = lane_id();
+	const uint32_t f = blockIdx.x * XG + (lane >> 4);
+	cg8* p = nullptr;
+	uint64_t n = 0;
+	bool want = false;
+	if (f < nframes) {
+		const FrameRec r = fr[f];
+		if ((r.flags & FRAME_HAS_CKSUM) && r.fail < 0 && r.out_len <= hash_max) {
+			p = gptr(buf) + r.out_off;
+			n = r.out_len;
+			want = true;
+		}
+	}
+	const uint32_t h = xxh32_rows(p, n, reinterpret_cast<cg32*>(gptr(fr)));
+	if (want && (lane & 15u) == 0) {
+		fr[f].hash = h;
+		fr[f].verdict |= FRAME_GPU_HASHED;
+	}
+}
+
 // Streaming XXHash32.Update (lz4ada.adb:942-977) on a device-resident state.
 __global__ __launch_bounds__(64) void k_xxh32_update(lz4ada_xxh32_state* __restrict__ s,
                                                       const uint8_t* __restrict__ data,
@@ -398,6 +426,16 @@ hipError_t launch_output_checksums(const uint8_t* d_out, const lz4ada_block_desc
 	hipLaunchKernelGGL(k_xxh32_rows, dim3((nblocks + XG - 1) / XG), dim3(64), 0, stream,
 	                   (const uint8_t*)nullptr, d_out, d_desc, nblocks,
 	                   const_cast<lz4ada_block_status*>(d_status), d_hash);
+	return hipGetLastError();
+}
+
+hipError_t launch_xxh32_spans(const uint8_t* d_buf, FrameRec* d_frames, uint32_t nframes,
+                              uint64_t hash_max, hipStream_t stream)
+{
+	if (nframes == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_xxh32_spans, dim3((nframes + XG - 1) / XG), dim3(64), 0, stream, d_buf,
+	                   d_frames, nframes, hash_max);
 	return hipGetLastError();
 }
 

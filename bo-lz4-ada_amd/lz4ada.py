@@ -170,12 +170,42 @@ class XXH32State(ctypes.Structure):
                 ("total_length", ctypes.c_uint64)]
 
 
+class StreamEntry(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_int64), ("frame_len", ctypes.c_int64), ("info", FrameInfo),
+                ("batchable", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
+class FrameJob(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_void_p), ("len", ctypes.c_int64), ("out_off", ctypes.c_int64),
+                ("out_len", ctypes.c_int64), ("consumed", ctypes.c_int64),
+                ("status", ctypes.c_int32), ("path", ctypes.c_int32)]
+
+
+class BatchStats(ctypes.Structure):
+    _fields_ = [("frames_batched", ctypes.c_int64), ("frames_single", ctypes.c_int64),
+                ("passes", ctypes.c_int64), ("gpu_hashed", ctypes.c_int64),
+                ("host_hashed", ctypes.c_int64)]
+
+
 BLOCK_STORED = 1
 BLOCK_HAS_CKSUM = 2
 FORMAT_MODERN, FORMAT_LEGACY, FORMAT_SKIPPABLE = 1, 2, 3
+# StreamEntry.batchable: why a frame does not take the many-frame pass
+BATCH_OK, BATCH_LINKED, BATCH_BIG_BLOCK, BATCH_OVER_BUDGET, BATCH_NOT_INDEXED = 0, 1, 2, 3, 4
 
 _P = ctypes.POINTER
 _sig = {
+    "lz4ada_stream_index": ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                             ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "lz4ada_decode_frames": ([ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p),
+                              ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
+    "lz4ada_frames_error": ([ctypes.c_int64], ctypes.c_char_p),
+    "lz4ada_last_batch_stats": ([ctypes.POINTER(BatchStats)], None),
+    "lz4ada_batch_hash_max": ([], ctypes.c_int64),
+    "lz4ada_xxh32_spans_device": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                   ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
+                                   ctypes.POINTER(ctypes.c_uint32),
+                                   ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
     "lz4ada_abi_version": ([], ctypes.c_int),
     "lz4ada_device_check": ([], ctypes.c_int),
     "lz4ada_error_name": ([ctypes.c_int], ctypes.c_char_p),
@@ -457,6 +487,80 @@ def decode_stream(data) -> bytes:
     return _take(p, olen.value)
 
 
+def stream_index(data):
+    """Host walk of every frame of a concatenated stream -> list of
+    StreamEntry (offset, frame_len, info, batchable: a BATCH_* reason code).
+    Raises the exception of the first frame that does not index or is cut
+    short; the frames before it are in the exception's `entries`."""
+    n = _i64()
+    st = _lib.lz4ada_stream_index(_addr(data), len(data), None, 0, ctypes.byref(n))
+    msg = _thread_error() if st else ""
+    entries = (StreamEntry * max(n.value, 1))()
+    m = _i64()
+    _lib.lz4ada_stream_index(_addr(data), len(data), entries, n.value, ctypes.byref(m))
+    out = [entries[i] for i in range(n.value)]
+    if st:
+        exc = _ERRORS.get(st, LZ4AdaError)(msg)
+        exc.entries = out
+        raise exc
+    return out
+
+
+def decode_frames_jobs(frames):
+    """lz4ada_decode_frames as it is -> (the output buffer as bytes, the
+    FrameJob array: out_off, out_len, consumed, status, path per frame)."""
+    frames = [f if isinstance(f, bytes) else bytes(f) for f in frames]
+    jobs = (FrameJob * max(len(frames), 1))()
+    for j, f in zip(jobs, frames):
+        j.frame = _addr(f)
+        j.len = len(f)
+    p, olen = _vp(), _i64()
+    _check(_lib.lz4ada_decode_frames(jobs, len(frames), ctypes.byref(p), ctypes.byref(olen)),
+           _thread_error())
+    return _take(p, olen.value), jobs
+
+
+def decode_frames(frames):
+    """Many independent frames (each with Single_Frame semantics) in as few
+    device passes as the byte budget allows -> list of (decoded bytes, bytes
+    consumed, exception or None), one per frame.  One bad frame does not
+    cost the others: a failed frame holds what the reference had output
+    before raising, as decode_frame_partial gives it."""
+    out, jobs = decode_frames_jobs(frames)
+    res = []
+    for i in range(len(frames)):
+        j = jobs[i]
+        exc = _ERRORS.get(j.status, LZ4AdaError)(_lib.lz4ada_frames_error(i).decode()) \
+            if j.status else None
+        res.append((out[j.out_off:j.out_off + j.out_len], j.consumed, exc))
+    return res
+
+
+def last_batch_stats() -> BatchStats:
+    """Counters of the last decode_frames / decode_stream call on this thread."""
+    s = BatchStats()
+    _lib.lz4ada_last_batch_stats(ctypes.byref(s))
+    return s
+
+
+def batch_hash_max() -> int:
+    """G: the decoded length up to which a pass hashes a frame's content
+    checksum on the GPU (LZ4ADA_BATCH_HASH_MAX overrides the default)."""
+    return int(_lib.lz4ada_batch_hash_max())
+
+
+def xxh32_spans_device(d_buf: int, spans):
+    """k_xxh32_spans alone over spans [(offset, length)] of device memory ->
+    (list of XXH32 values, kernel milliseconds)."""
+    n = len(spans)
+    off = (_i64 * max(n, 1))(*[s[0] for s in spans])
+    ln = (_i64 * max(n, 1))(*[s[1] for s in spans])
+    h = (ctypes.c_uint32 * max(n, 1))()
+    ms = ctypes.c_float()
+    _check(_lib.lz4ada_xxh32_spans_device(d_buf, off, ln, n, h, ctypes.byref(ms)), _thread_error())
+    return list(h[:n]), ms.value
+
+
 def _devices(n_gpus: int, devices):
     if devices is None:
         return None
@@ -505,6 +609,7 @@ def plan_shards(descs, nblocks: int, n_gpus: int):
 
 
 PATH_INDEPENDENT, PATH_LINKED, PATH_EXACT, PATH_MULTI = 1, 2, 4, 8
+PATH_BATCH = 16  # the frame was committed from a many-frame pass
 
 
 def multi_device_allocs(device: int) -> int:

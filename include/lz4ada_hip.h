@@ -364,7 +364,87 @@ int lz4ada_decode_linked_device(const void *d_frame, uint64_t frame_len,
 #define LZ4ADA_PATH_LINKED 2
 #define LZ4ADA_PATH_EXACT 4
 #define LZ4ADA_PATH_MULTI 8 /* lz4ada_decode_frame_multi* took the call */
+#define LZ4ADA_PATH_BATCH 16 /* the frame was committed from a multi-frame pass */
 int lz4ada_last_path(void);
+
+/* ------------------------------------------- many frames in one device pass */
+/*
+ * A caller with many small frames (concatenated .lz4 files, one frame per
+ * flush or per page) gets one device pass per budgetful of frames instead
+ * of one per frame: the frames' blocks are decoded by one launch, a device
+ * scan (k_frames_plan) lays the output out back to back and judges every
+ * frame, content checksums are hashed side by side on the GPU
+ * (k_xxh32_spans), and one small copy of the per-frame records plus one
+ * copy of the bytes bring the results back.  No
+ * reference twin: the calls replace the caller's per-frame
+ * Init_With_Header / Update loop (tool_unlz4ada/unlz4ada.adb:84-103).  A
+ * frame the pass does not find good in every respect is decoded again on
+ * its own by the path lz4ada_decode_frame takes, which gives the
+ * reference's output, exception and message.
+ */
+
+/* Why a frame does not take the batch path (lz4ada_stream_entry.batchable). */
+#define LZ4ADA_BATCH_OK 0
+#define LZ4ADA_BATCH_LINKED 1      /* modern with B.Indep clear */
+#define LZ4ADA_BATCH_BIG_BLOCK 2   /* a block slot over 4 MiB, or blocks the lone-block decoder takes */
+#define LZ4ADA_BATCH_OVER_BUDGET 3 /* its slots alone exceed LZ4ADA_BATCH_BYTES */
+#define LZ4ADA_BATCH_NOT_INDEXED 4 /* does not index, or is cut short */
+
+typedef struct {
+	int64_t offset, frame_len; /* where the frame lies in the input */
+	lz4ada_frame_info info;    /* as lz4ada_frame_index gives it */
+	int32_t batchable;         /* LZ4ADA_BATCH_* reason code, 0 = takes the batch path */
+	int32_t pad;
+} lz4ada_stream_entry;
+
+/* Walk every frame of a concatenated stream (host only, no HIP call).
+ * entries may be NULL to count.  Stops at the first frame that does not
+ * index or is cut short: *nframes counts the frames before it and the
+ * return value is that frame's status (message in
+ * lz4ada_thread_last_error()). */
+int lz4ada_stream_index(const uint8_t *input, int64_t len, lz4ada_stream_entry *entries,
+                        int64_t cap, int64_t *nframes);
+
+typedef struct {
+	const uint8_t *frame; /* in: one frame (Single_Frame semantics) */
+	int64_t len;
+	int64_t out_off, out_len; /* out: its bytes inside *out */
+	int64_t consumed;         /* out: bytes of the frame */
+	int32_t status;           /* out: lz4ada_status of THIS frame */
+	int32_t path;             /* out: LZ4ADA_PATH_* bits this frame took */
+} lz4ada_frame_job;
+
+/* Decode njobs independent frames.  Returns LZ4ADA_OK when the call itself
+ * worked, whatever the per-job statuses; a failed job holds what the
+ * reference had output before raising (as lz4ada_decode_frame_partial).
+ * *out is library-allocated (lz4ada_buffer_free). */
+int lz4ada_decode_frames(lz4ada_frame_job *jobs, int64_t njobs, uint8_t **out, int64_t *out_len);
+/* Message of job i of the last lz4ada_decode_frames call on this thread
+ * ("" for a job that succeeded or an index out of range). */
+const char *lz4ada_frames_error(int64_t i);
+
+/* lz4ada_decode_stream / _alloc take the same engine when the stream holds
+ * at least two batchable frames (LZ4ADA_NO_BATCH=1: never); the frames are
+ * committed in order and the first failing frame's exception is returned
+ * after the frames before it, as the per-frame loop does. */
+
+typedef struct {
+	int64_t frames_batched, frames_single, passes, gpu_hashed, host_hashed;
+} lz4ada_batch_stats;
+/* Counters of the last lz4ada_decode_frames / _stream call on this thread:
+ * frames committed from a pass, frames decoded on their own, passes, content
+ * checksums hashed by k_xxh32_spans and by the host chain.  No HIP call. */
+void lz4ada_last_batch_stats(lz4ada_batch_stats *out);
+/* The decoded length up to which a pass hashes a frame's content checksum
+ * on the GPU (longer frames: the host chain while their bytes are copied
+ * out): the built-in default, or LZ4ADA_BATCH_HASH_MAX, read per call. */
+int64_t lz4ada_batch_hash_max(void);
+/* k_xxh32_spans alone (tools/frames_batch_xxh.py, tests): XXH32, seed 0, of
+ * the nspans spans (off[i], len[i]) -- host arrays -- of the device buffer
+ * d_buf into the host array hash[i]; four spans per wave.  Synchronous;
+ * *kernel_ms (may be NULL) gets the kernel's time between device events. */
+int lz4ada_xxh32_spans_device(const void *d_buf, const int64_t *off, const int64_t *len,
+                              int64_t nspans, uint32_t *hash, float *kernel_ms);
 
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,

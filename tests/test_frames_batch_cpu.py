@@ -1,0 +1,157 @@
+"""Host side of the many-frame pass (no GPU needed): the stream index --
+which frames a concatenated stream holds, where, and whether each can share
+a device pass -- and the argument checks of lz4ada_decode_frames, which run
+before any device call.  Streams here hold stored blocks only."""
+import ctypes
+import random
+import struct
+
+import pytest
+
+from conftest import read_vector
+
+import lz4ada
+import lz4frame
+
+SIZES = [0, 1, 2, 3, 15, 16, 17, 4095, 65536, 65537]
+BMAX = [64 << 10, 256 << 10, 4 << 20]
+SKIP_AT, LINKED_AT = 41, 123
+
+
+def stored_frame(rng, n, bmax, **kw):
+    raw = rng.randbytes(n)
+    blocks = [(raw[i:i + 65536], raw[i:i + 65536], True) for i in range(0, n, 65536)]
+    return lz4frame.build_frame(blocks, bmax, **kw)[0]
+
+
+def skippable(payload: bytes, nibble=3) -> bytes:
+    return struct.pack("<II", 0x184D2A50 + nibble, len(payload)) + payload
+
+
+def synthetic_stream():
+    """300 frames -> [(frame bytes, format, blocks, expected reason)]."""
+    rng = random.Random(20260101)
+    out = []
+    for i in range(300):
+        if i == SKIP_AT:
+            out.append((skippable(rng.randbytes(33)), lz4ada.FORMAT_SKIPPABLE, 0, lz4ada.BATCH_OK))
+            continue
+        n = SIZES[i % len(SIZES)]
+        f = stored_frame(rng, n, BMAX[i % 3], indep=i != LINKED_AT, block_cksum=bool(i & 1),
+                         content_cksum=bool(i & 2), with_content_size=bool(i & 4))
+        out.append((f, lz4ada.FORMAT_MODERN, (n + 65535) // 65536,
+                    lz4ada.BATCH_LINKED if i == LINKED_AT else lz4ada.BATCH_OK))
+    return out
+
+
+def same_info(a, b):
+    return bytes(a) == bytes(b)
+
+
+# concatenated modern / skippable + modern / legacy + modern / legacy + legacy
+VECTOR_FORMATS = {
+    "concat390": [lz4ada.FORMAT_MODERN, lz4ada.FORMAT_MODERN],
+    "skipz100": [lz4ada.FORMAT_SKIPPABLE, lz4ada.FORMAT_MODERN],
+    "z101legacyplus": [lz4ada.FORMAT_LEGACY, lz4ada.FORMAT_MODERN],
+    "concatlegacy": [lz4ada.FORMAT_LEGACY, lz4ada.FORMAT_LEGACY],
+}
+
+
+@pytest.mark.parametrize("name", sorted(VECTOR_FORMATS))
+def test_stream_index_vectors(name):
+    data = read_vector(name, "lz4")
+    entries = lz4ada.stream_index(data)
+    assert [e.info.format for e in entries] == VECTOR_FORMATS[name]
+    pos = 0
+    for e in entries:
+        assert e.offset == pos and e.frame_len > 0
+        info, _ = lz4ada.frame_index(data, e.offset)
+        assert same_info(e.info, info) and e.frame_len == info.frame_len
+        assert e.batchable == lz4ada.BATCH_OK
+        pos += e.frame_len
+    assert pos == len(data)
+
+
+def test_stream_index_synthetic_300():
+    frames = synthetic_stream()
+    data = b"".join(f for f, *_ in frames)
+    entries = lz4ada.stream_index(data)
+    assert len(entries) == 300
+    pos = 0
+    for e, (f, fmt, nblocks, reason) in zip(entries, frames):
+        assert (e.offset, e.frame_len) == (pos, len(f))
+        assert (e.info.format, e.info.nblocks, e.batchable) == (fmt, nblocks, reason)
+        pos += len(f)
+    assert pos == len(data)
+    info, _ = lz4ada.frame_index(data, entries[LINKED_AT].offset)
+    assert same_info(entries[LINKED_AT].info, info) and not info.independent
+
+
+def test_stream_index_reasons_big_block_and_budget(monkeypatch):
+    rng = random.Random(7)
+    small = stored_frame(rng, 1000, 64 << 10)
+    big = stored_frame(rng, 65537, 64 << 10)  # slots: 65536 + 256
+    # a legacy frame whose block may decode to over 4 MiB (255 bytes per payload byte)
+    comp, _ = lz4ada.gen_block(lz4ada.GEN_LITERAL, 5, 20000)
+    assert 255 * len(comp) + 64 > 4 << 20
+    legacy = struct.pack("<II", 0x184C2102, len(comp)) + comp
+    entries = lz4ada.stream_index(small + big + legacy)
+    assert [e.batchable for e in entries] == [lz4ada.BATCH_OK, lz4ada.BATCH_OK,
+                                              lz4ada.BATCH_BIG_BLOCK]
+    assert entries[2].info.format == lz4ada.FORMAT_LEGACY
+    monkeypatch.setenv("LZ4ADA_BATCH_BYTES", "65536")  # read per call
+    entries = lz4ada.stream_index(small + big)
+    assert [e.batchable for e in entries] == [lz4ada.BATCH_OK, lz4ada.BATCH_OVER_BUDGET]
+
+
+def frame_index_error(data, offset):
+    with pytest.raises(lz4ada.LZ4AdaError) as ei:
+        lz4ada.frame_index(data, offset)
+    return type(ei.value), ei.value.message
+
+
+def test_stream_index_cut_inside_frame_7():
+    frames = [f for f, *_ in synthetic_stream()[:10]]
+    assert len(frames[7]) > 4000  # the 4095-byte frame
+    cut = b"".join(frames[:7]) + frames[7][:len(frames[7]) // 2]
+    with pytest.raises(lz4ada.LZ4AdaError) as ei:
+        lz4ada.stream_index(cut)
+    assert len(ei.value.entries) == 7
+    assert [e.frame_len for e in ei.value.entries] == [len(f) for f in frames[:7]]
+    assert (type(ei.value), ei.value.message) == frame_index_error(cut, sum(map(len, frames[:7])))
+
+
+def test_stream_index_trailing_bytes():
+    frames = [f for f, *_ in synthetic_stream()[:10]]
+    data = b"".join(frames) + b"\x04\x22\x4d\x18\x60"
+    with pytest.raises(lz4ada.LZ4AdaError) as ei:
+        lz4ada.stream_index(data)
+    assert len(ei.value.entries) == 10
+    assert (type(ei.value), ei.value.message) == frame_index_error(data, len(data) - 5)
+    assert isinstance(ei.value, lz4ada.AssertionFailure)
+
+
+def test_decode_frames_argument_checks():
+    """Before any device call: these pass on a machine without a GPU."""
+    assert lz4ada.decode_frames([]) == []
+    jobs = (lz4ada.FrameJob * 1)()
+    p, n = ctypes.c_void_p(), ctypes.c_int64(-1)
+    assert lz4ada._lib.lz4ada_decode_frames(jobs, 0, ctypes.byref(p), ctypes.byref(n)) == 0
+    assert n.value == 0 and p.value
+    lz4ada._lib.lz4ada_buffer_free(p)
+    st = lz4ada._lib.lz4ada_decode_frames(jobs, -1, ctypes.byref(p), ctypes.byref(n))
+    assert lz4ada._ERRORS[st] is lz4ada.AssertionFailure and not p.value
+    st = lz4ada._lib.lz4ada_decode_frames(None, 0, ctypes.byref(p), ctypes.byref(n))
+    assert lz4ada._ERRORS[st] is lz4ada.AssertionFailure and not p.value
+    s = lz4ada.last_batch_stats()
+    assert (s.frames_batched, s.frames_single, s.passes, s.gpu_hashed, s.host_hashed) == (0,) * 5
+    assert lz4ada.PATH_BATCH == 16
+    assert lz4ada.batch_hash_max() > 0
+
+
+def test_batch_hash_max_override(monkeypatch):
+    g = lz4ada.batch_hash_max()
+    monkeypatch.setenv("LZ4ADA_BATCH_HASH_MAX", "4096")
+    assert lz4ada.batch_hash_max() == 4096
+    monkeypatch.delenv("LZ4ADA_BATCH_HASH_MAX")
+    assert lz4ada.batch_hash_max() == g
