@@ -77,6 +77,34 @@ package body LZ4Ada.GPU is
 		Output_Length := L;
 	end Decode_Frames;
 
+	function Frames_Device_Bound(D_In:   in     System.Address;
+				In_Len: in     Interfaces.Integer_64;
+				Jobs:   in out Device_Frame_Jobs;
+				Stream: in     System.Address := System.Null_Address)
+				return Interfaces.Integer_64 is
+		B: aliased Interfaces.Integer_64;
+	begin
+		Check(C_Frames_Device_Bound(D_In, In_Len, Jobs'Address, Jobs'Length,
+			B'Access, Stream));
+		return B;
+	end Frames_Device_Bound;
+
+	procedure Decode_Frames_Device(D_In:          in     System.Address;
+				In_Len:        in     Interfaces.Integer_64;
+				Jobs:          in out Device_Frame_Jobs;
+				D_Out:         in     System.Address;
+				Out_Cap:       in     Interfaces.Integer_64;
+				Output_Length: out    Interfaces.Integer_64;
+				Stream:        in     System.Address := System.Null_Address) is
+		L:  aliased Interfaces.Integer_64;
+		St: Interfaces.Integer_32;
+	begin
+		St := C_Decode_Frames_Device(D_In, In_Len, Jobs'Address, Jobs'Length,
+			D_Out, Out_Cap, L'Access, Stream);
+		Output_Length := L;  -- the bound, when Too_Little_Memory follows
+		Check(St);
+	end Decode_Frames_Device;
+
 	function Frames_Error(Jobs: in Frame_Jobs; I: in Positive) return String is
 		function C_Frames_Error(J: Interfaces.Integer_64)
 				return Interfaces.C.Strings.chars_ptr;

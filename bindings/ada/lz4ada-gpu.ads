@@ -62,6 +62,44 @@ package LZ4Ada.GPU is
 	procedure Buffer_Free(P: in System.Address);
 	pragma Import(C, Buffer_Free, "lz4ada_buffer_free");
 
+	-- lz4ada_frames_device_bound / lz4ada_decode_frames_device: many frames
+	-- that already lie in device memory, decoded into device memory
+	-- (lz4ada_device_frame_job of include/lz4ada_hip.h).  D_In and D_Out
+	-- are device addresses, Stream a hipStream_t (Null_Address: the default
+	-- stream).  The caller fills In_Off and In_Len; every other component
+	-- is output.  Status is 0, or 9 (LZ4ADA_EXACT_PATH) with a Reason
+	-- (LZ4ADA_DEVFRAME_*) for a frame the pass did not decode: Decode_Frame
+	-- on that frame's host bytes gives the reference's result.
+	type Device_Frame_Job is record
+		In_Off:   Interfaces.Integer_64;
+		In_Len:   Interfaces.Integer_64;
+		Out_Off:  Interfaces.Integer_64;
+		Out_Len:  Interfaces.Integer_64;
+		Consumed: Interfaces.Integer_64;
+		Status:   Interfaces.Integer_32;
+		Reason:   Interfaces.Integer_32;
+	end record;
+	pragma Convention(C, Device_Frame_Job);
+	type Device_Frame_Jobs is array(Positive range <>) of aliased Device_Frame_Job;
+	pragma Convention(C, Device_Frame_Jobs);
+
+	-- An output capacity that always suffices.  Raises only when the call
+	-- itself failed (Program_Error: ranges that overlap or leave the input).
+	function Frames_Device_Bound(D_In:   in     System.Address;
+				In_Len: in     Interfaces.Integer_64;
+				Jobs:   in out Device_Frame_Jobs;
+				Stream: in     System.Address := System.Null_Address)
+				return Interfaces.Integer_64;
+	-- Too_Little_Memory when Out_Cap is below the bound (Output_Length then
+	-- holds the bound and D_Out is untouched).
+	procedure Decode_Frames_Device(D_In:          in     System.Address;
+				In_Len:        in     Interfaces.Integer_64;
+				Jobs:          in out Device_Frame_Jobs;
+				D_Out:         in     System.Address;
+				Out_Cap:       in     Interfaces.Integer_64;
+				Output_Length: out    Interfaces.Integer_64;
+				Stream:        in     System.Address := System.Null_Address);
+
 	-- lz4ada_rccl_version: the RCCL this process bound (22606 = 2.26.6).
 	function RCCL_Version return Interfaces.Integer_32;
 	pragma Import(C, RCCL_Version, "lz4ada_rccl_version");
@@ -96,5 +134,18 @@ private
 			Out_Len: access Interfaces.Integer_64)
 			return Interfaces.Integer_32;
 	pragma Import(C, C_Decode_Frames, "lz4ada_decode_frames");
+
+	function C_Frames_Device_Bound(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Bound: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Frames_Device_Bound, "lz4ada_frames_device_bound");
+
+	function C_Decode_Frames_Device(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			D_Out: System.Address; Out_Cap: Interfaces.Integer_64;
+			Out_Len: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Decode_Frames_Device, "lz4ada_decode_frames_device");
 
 end LZ4Ada.GPU;

@@ -13,6 +13,9 @@
 using namespace lz4ada;
 
 namespace lz4ada {
+
+int64_t batch_budget() { return env_bytes("LZ4ADA_BATCH_BYTES", int64_t(4) << 30); }
+
 namespace {
 
 // The bulk decoders take blocks whose slot is at most this (MAX_RUN,
@@ -41,9 +44,6 @@ struct Frame {
 	uint64_t caps = 0;   // sum of slot_cap: what it can decode to
 	bool skippable() const { return info.format == LZ4ADA_FORMAT_SKIPPABLE; }
 };
-
-int64_t batch_budget() { return env_bytes("LZ4ADA_BATCH_BYTES", int64_t(4) << 30); }
-int64_t batch_hash_max() { return env_bytes("LZ4ADA_BATCH_HASH_MAX", BATCH_HASH_MAX); }
 
 // The switches that pin a frame to one of the single-frame paths pin the
 // stream to the per-frame loop too.
@@ -349,6 +349,9 @@ void run_frames(const std::vector<Frame>& fs, bool contiguous, Sink& out, const 
 }
 
 }  // namespace
+
+int64_t batch_hash_max() { return env_bytes("LZ4ADA_BATCH_HASH_MAX", BATCH_HASH_MAX); }
+lz4ada_batch_stats& batch_stats() { return g_stats; }
 
 void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t* committed)
 {

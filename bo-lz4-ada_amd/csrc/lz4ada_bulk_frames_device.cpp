@@ -1,0 +1,346 @@
+// lz4ada_bulk_frames_device.cpp -- many frames that already lie in device
+// memory, decoded into device memory.  The pass is the one of
+// lz4ada_bulk_frames.cpp (one decode launch over every block of every frame,
+// k_frames_plan, k_compact, k_xxh32_spans); what differs is where its index
+// comes from and where its bytes go: the frames are indexed where they lie by
+// k_frames_walk / k_frames_scan / k_frames_fill (lz4ada_frames_index.hip), the
+// decoders read the caller's d_in itself, and the compaction writes into the
+// caller's d_out.  The host sees the per-frame walk records (one D2H per
+// call: verdicts and sizes, from which it sizes the scratch and splits the
+// passes by the byte budget) and the per-frame pass records (one D2H per
+// pass); no payload byte crosses, except that a content checksum over more
+// than lz4ada_batch_hash_max() bytes is hashed by the host chain
+// (content_xxh32_d2h with no host destination).  A frame the pass does not
+// find good in every respect gets LZ4ADA_EXACT_PATH and a reason; this unit
+// invents no exception text.
+#include "lz4ada_frame_walk.h"
+#include "lz4ada_host_common.h"
+
+using namespace lz4ada;
+
+namespace lz4ada {
+namespace {
+
+static_assert(WALK_LONE_MAX_IN == LONE_MAX_IN, "the walk states the lone-block rule a second time");
+
+// The jobs in rising in_off, indexed on the device.  The device arrays live
+// in this thread's SC_FRAME scratch (a device pass stages nothing there).
+struct Index {
+	std::vector<uint32_t> order;     // sorted position -> job
+	std::vector<FrameWalkRec> walk;  // by sorted position
+	std::vector<FrameSpan> span;     // by sorted position
+	FrameSpan* d_span = nullptr;
+	FrameWalkRec* d_walk = nullptr;
+	uint64_t *d_first = nullptr, *d_slot = nullptr;  // n + 1 entries each
+	bool taken(size_t k) const { return walk[k].verdict == LZ4ADA_BATCH_OK; }
+	bool skippable(size_t k) const { return walk[k].format == LZ4ADA_FORMAT_SKIPPABLE; }
+};
+
+[[noreturn]] void misuse(const char* entry, const std::string& what)
+{
+	raise(LZ4ADA_ASSERTION_ERROR, std::string(entry) + ": " + what);
+}
+
+// The argument checks (nothing is launched before they pass), the sort, and
+// the walk of every job's frame with its one host synchronisation.
+void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ada_device_frame_job* jobs,
+                int64_t njobs, hipStream_t stream, Index& ix)
+{
+	if (njobs < 0 || (njobs > 0 && !jobs) || in_len < 0 || (in_len > 0 && !d_in) ||
+	    njobs >= (int64_t(1) << 31))
+		misuse(entry, "jobs or d_in is NULL, or a count is out of range");
+	const size_t n = size_t(njobs);
+	for (size_t i = 0; i < n; ++i)
+		if (jobs[i].in_off < 0 || jobs[i].in_len < 0 || jobs[i].in_off > in_len ||
+		    jobs[i].in_len > in_len - jobs[i].in_off)
+			misuse(entry, "job" + img(int64_t(i)) + " lies outside the input");
+	ix.order.resize(n);
+	for (size_t i = 0; i < n; ++i)
+		ix.order[i] = uint32_t(i);
+	std::stable_sort(ix.order.begin(), ix.order.end(),
+	                 [&](uint32_t a, uint32_t b) { return jobs[a].in_off < jobs[b].in_off; });
+	// Two jobs' ranges may share bytes only when the earlier one runs to the
+	// end of the input (the frame and whatever follows it); its frame is
+	// checked against the next job once the walk has found its length.
+	for (size_t k = 0; k + 1 < n; ++k) {
+		const auto &a = jobs[ix.order[k]], &b = jobs[ix.order[k + 1]];
+		if (a.in_off + a.in_len > b.in_off && a.in_off + a.in_len != in_len)
+			misuse(entry, "jobs" + img(int64_t(ix.order[k])) + " and" + img(int64_t(ix.order[k + 1])) +
+			                      " overlap");
+	}
+	ix.walk.assign(n, FrameWalkRec{});
+	ix.span.resize(n);
+	if (n == 0)
+		return;
+	device_check_or_raise();
+	const size_t span_b = n * sizeof(FrameSpan), walk_b = n * sizeof(FrameWalkRec), scan_b = (n + 1) * 8;
+	uint8_t* const d = scratch(SC_FRAME, span_b + walk_b + 2 * scan_b);
+	if (!d)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the frame index");
+	ix.d_span = reinterpret_cast<FrameSpan*>(d);
+	ix.d_walk = reinterpret_cast<FrameWalkRec*>(d + span_b);
+	ix.d_first = reinterpret_cast<uint64_t*>(d + span_b + walk_b);
+	ix.d_slot = reinterpret_cast<uint64_t*>(d + span_b + walk_b + scan_b);
+	PinBuf& h = scratch_cache().pin;  // this thread's small pinned transfers
+	h.reserve(std::max(span_b, walk_b));
+	for (size_t k = 0; k < n; ++k)
+		ix.span[k] = FrameSpan{ uint64_t(jobs[ix.order[k]].in_off), uint64_t(jobs[ix.order[k]].in_len) };
+	memcpy(h.p, ix.span.data(), span_b);
+	HIP_OK(hipMemcpyAsync(ix.d_span, h.p, span_b, hipMemcpyHostToDevice, stream));
+	HIP_OK(launch_frames_walk(static_cast<const uint8_t*>(d_in), ix.d_span, uint32_t(n), lone_blocks_disabled(),
+	                          uint64_t(batch_budget()), ix.d_walk, stream));
+	// the index's host synchronisation: verdicts and sizes, no frame byte
+	HIP_OK(hipMemcpyAsync(h.p, ix.d_walk, walk_b, hipMemcpyDeviceToHost, stream));
+	HIP_OK(hipStreamSynchronize(stream));
+	memcpy(ix.walk.data(), h.p, walk_b);
+	for (size_t k = 0; k + 1 < n; ++k)
+		if (ix.taken(k) && ix.span[k].off + uint64_t(ix.walk[k].frame_len) > ix.span[k + 1].off)
+			misuse(entry, "the frame of job" + img(int64_t(ix.order[k])) + " reaches into job" +
+			                      img(int64_t(ix.order[k + 1])));
+}
+
+// What the index alone says about every job, and the bound: what the frames
+// a pass takes can decode to.
+int64_t report_index(const Index& ix, lz4ada_device_frame_job* jobs)
+{
+	uint64_t bound = 0;
+	for (size_t k = 0; k < ix.order.size(); ++k) {
+		lz4ada_device_frame_job& j = jobs[ix.order[k]];
+		j.out_off = j.out_len = j.consumed = 0;
+		j.status = ix.taken(k) ? LZ4ADA_OK : LZ4ADA_EXACT_PATH;
+		j.reason = ix.walk[k].verdict;
+		if (ix.taken(k))
+			bound += ix.walk[k].caps;
+	}
+	return int64_t(bound);
+}
+
+// The pass's device arrays, in this thread's SC_BATCH_META scratch:
+// descriptors | frame records | statuses | dst_off | loc | part
+struct PassMeta {
+	size_t desc_b, rec_b, st_b, off_b, loc_b, part_b;
+	lz4ada_block_desc* d_desc = nullptr;
+	FrameRec* d_rec = nullptr;
+	lz4ada_block_status* d_st = nullptr;
+	uint64_t *d_off = nullptr, *d_loc = nullptr, *d_part = nullptr;
+	PassMeta(uint32_t nb, uint32_t nf)
+	    : desc_b(size_t(nb) * sizeof(lz4ada_block_desc)), rec_b(size_t(nf) * sizeof(FrameRec)),
+	      st_b(size_t(nb) * sizeof(lz4ada_block_status)), off_b((size_t(nb) + 1) * 8), loc_b(size_t(nb) * 8),
+	      part_b((size_t(plan_tiles(nb)) + 1) * 8)
+	{
+		uint8_t* const d = scratch(SC_BATCH_META, desc_b + rec_b + st_b + off_b + loc_b + part_b);
+		if (!d)
+			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's block arrays");
+		d_desc = reinterpret_cast<lz4ada_block_desc*>(d);
+		d_rec = reinterpret_cast<FrameRec*>(d + desc_b);
+		d_st = reinterpret_cast<lz4ada_block_status*>(d + desc_b + rec_b);
+		d_off = reinterpret_cast<uint64_t*>(d + desc_b + rec_b + st_b);
+		d_loc = reinterpret_cast<uint64_t*>(d + desc_b + rec_b + st_b + off_b);
+		d_part = reinterpret_cast<uint64_t*>(d + desc_b + rec_b + st_b + off_b + loc_b);
+	}
+};
+
+// The scan and the fill over the sorted jobs [lo, hi): descriptors and frame
+// records of a pass, on the device.
+void fill_pass(const Index& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassMeta& m,
+               hipStream_t stream)
+{
+	const uint32_t nf = uint32_t(hi - lo);
+	HIP_OK(launch_frames_scan(ix.d_walk + lo, nf, ix.d_first, ix.d_slot, stream));
+	HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, ix.d_walk + lo, ix.d_first, ix.d_slot, nf,
+	                          lone_blocks_disabled(), m.d_desc, m.d_rec, stream));
+}
+
+void job_rejected(lz4ada_device_frame_job& j, int reason)
+{
+	j.out_off = j.out_len = j.consumed = 0;
+	j.status = LZ4ADA_EXACT_PATH;
+	j.reason = reason;
+}
+
+void job_skipped(lz4ada_device_frame_job& j, const FrameWalkRec& w, uint64_t at)
+{
+	j.out_off = int64_t(at);
+	j.consumed = w.frame_len;
+	++batch_stats().frames_batched;
+	add_last_path(LZ4ADA_PATH_BATCH);
+}
+
+// One pass over the sorted jobs [lo, hi) (nb blocks, `slots` slot bytes; the
+// frames the index did not take ride along as frames without blocks): their
+// bytes go to d_out from *base on, which then moves past them.
+void run_device_pass(const Index& ix, size_t lo, size_t hi, uint32_t nb, uint64_t slots, const uint8_t* d_in,
+                     uint64_t in_len, lz4ada_device_frame_job* jobs, uint8_t* d_out, uint64_t* base,
+                     uint64_t hash_max, hipStream_t stream)
+{
+	const uint32_t nf = uint32_t(hi - lo);
+	const PassMeta m(nb, nf);
+	uint8_t* const d_slots = scratch(SC_OUT, size_t(std::max<uint64_t>(slots, 1)));
+	if (!d_slots)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's slots");
+	uint8_t* const dst = d_out + *base;
+	fill_pass(ix, lo, hi, d_in, m, stream);
+	if (nb)
+		HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
+	// in_off rises strictly over the pass (the jobs are sorted and their frames
+	// disjoint) and in_len covers every block: what the index decoder's table
+	// relies on (lz4ada_bulk_frames.cpp, run_pass)
+	HIP_OK(launch_decode_checked(d_in, in_len, m.d_desc, nb, d_slots, m.d_st, stream));
+	HIP_OK(launch_frames_plan(m.d_desc, m.d_st, nb, m.d_rec, nf, m.d_off, m.d_loc, m.d_part, stream));
+	HIP_OK(launch_compact(d_slots, m.d_desc, m.d_off, m.d_st, nb, dst, stream));
+	HIP_OK(launch_xxh32_spans(dst, m.d_rec, nf, hash_max, stream));
+	PinBuf& h = scratch_cache().pin;  // this thread's small pinned transfers
+	h.reserve(m.rec_b);
+	// the pass's host synchronisation: the per-frame records
+	HIP_OK(hipMemcpyAsync(h.p, m.d_rec, m.rec_b, hipMemcpyDeviceToHost, stream));
+	HIP_OK(hipStreamSynchronize(stream));
+	const FrameRec* const rec = reinterpret_cast<const FrameRec*>(h.p);
+	lz4ada_batch_stats& stats = batch_stats();
+	++stats.passes;
+	for (size_t k = lo; k < hi; ++k) {
+		if (!ix.taken(k))
+			continue;
+		const FrameRec& r = rec[k - lo];
+		lz4ada_device_frame_job& j = jobs[ix.order[k]];
+		if (ix.skippable(k)) {  // consumed, no output: its place among the others'
+			job_skipped(j, ix.walk[k], *base + r.out_off);
+			continue;
+		}
+		int reason = LZ4ADA_DEVFRAME_OK;
+		if (r.fail >= 0) {
+			reason = LZ4ADA_DEVFRAME_BLOCK;
+		} else if (r.verdict & FRAME_SIZE_BAD) {
+			reason = LZ4ADA_DEVFRAME_SIZE;
+		} else if (r.verdict & FRAME_GPU_HASHED) {
+			++stats.gpu_hashed;
+			if (r.hash != ix.walk[k].cksum)
+				reason = LZ4ADA_DEVFRAME_CHECKSUM;
+		} else if (r.flags & FRAME_HAS_CKSUM) {
+			// over hash_max: the host chain, the one place where decoded bytes
+			// visit the host, and only to be hashed
+			lz4ada_xxh32_state hs;
+			lz4ada_xxh32_reset(&hs, 0);
+			content_xxh32_d2h(hs, dst + r.out_off, int64_t(r.out_len), nullptr, stream);
+			++stats.host_hashed;
+			if (host_xxh32_final(hs) != ix.walk[k].cksum)
+				reason = LZ4ADA_DEVFRAME_CHECKSUM;
+		}
+		if (reason != LZ4ADA_DEVFRAME_OK) {
+			job_rejected(j, reason);
+			continue;
+		}
+		j.out_off = int64_t(*base + r.out_off);
+		j.out_len = int64_t(r.out_len);
+		j.consumed = ix.walk[k].frame_len;
+		j.status = LZ4ADA_OK;
+		j.reason = LZ4ADA_DEVFRAME_OK;
+		++stats.frames_batched;
+		add_last_path(LZ4ADA_PATH_BATCH | LZ4ADA_PATH_INDEPENDENT);
+	}
+	*base += rec[nf - 1].out_off + rec[nf - 1].out_len;
+}
+
+}  // namespace
+}  // namespace lz4ada
+
+extern "C" {
+
+int lz4ada_frame_walk_host(const uint8_t* frame, int64_t len, lz4ada_frame_info* info, lz4ada_block_desc* descs,
+                           int64_t desc_cap)
+{
+	WalkSums sums;
+	WalkEmit e{};
+	e.descs = descs;
+	e.cap = desc_cap;
+	return frame_walk(frame, len, lone_blocks_disabled(), info, &sums, descs ? &e : nullptr);
+}
+
+int lz4ada_frames_device_bound(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                               int64_t* bound, void* stream)
+{
+	*bound = 0;
+	batch_stats() = lz4ada_batch_stats{};
+	return guarded(nullptr, [&] {
+		Index ix;
+		index_jobs("lz4ada_frames_device_bound", d_in, in_len, jobs, njobs, static_cast<hipStream_t>(stream),
+		           ix);
+		*bound = report_index(ix, jobs);
+	});
+}
+
+int lz4ada_decode_frames_device(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                                void* d_out, int64_t out_cap, int64_t* out_len, void* stream)
+{
+	*out_len = 0;
+	batch_stats() = lz4ada_batch_stats{};
+	set_last_path(0);
+	return guarded(nullptr, [&] {
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		Index ix;
+		index_jobs("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, s, ix);
+		const int64_t bound = report_index(ix, jobs);
+		if (out_cap < bound || (bound > 0 && !d_out)) {
+			*out_len = bound;
+			raise(LZ4ADA_TOO_LITTLE_MEMORY, "lz4ada_decode_frames_device: the output holds" + img(out_cap) +
+			                                        " bytes, the frames may decode to" + img(bound));
+		}
+		const uint64_t budget = uint64_t(batch_budget()), hash_max = uint64_t(batch_hash_max());
+		uint64_t base = 0;
+		const size_t n = ix.order.size();
+		size_t lo = 0;
+		while (lo < n) {
+			// the sorted jobs [lo, hi): as many frames as the budget takes
+			size_t hi = lo;
+			uint64_t acc = 0, nb = 0, real = 0;
+			for (; hi < n; ++hi) {
+				if (!ix.taken(hi))
+					continue;
+				if ((acc && acc + ix.walk[hi].slots > budget) ||
+				    nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
+					break;
+				acc += ix.walk[hi].slots;
+				nb += ix.walk[hi].nblocks;
+				real += ix.skippable(hi) ? 0 : 1;
+			}
+			if (hi == lo)  // one frame of 2^31 blocks or more
+				raise(LZ4ADA_CONSTRAINT_ERROR, "a frame holds more blocks than a pass takes");
+			if (real) {
+				run_device_pass(ix, lo, hi, uint32_t(nb), acc, static_cast<const uint8_t*>(d_in),
+				                uint64_t(in_len), jobs, static_cast<uint8_t*>(d_out), &base, hash_max, s);
+			} else {  // nothing but skippable frames, if any: no launch
+				for (size_t k = lo; k < hi; ++k)
+					if (ix.taken(k))
+						job_skipped(jobs[ix.order[k]], ix.walk[k], base);
+			}
+			lo = hi;
+		}
+		*out_len = int64_t(base);
+	});
+}
+
+int lz4ada_frames_index_device_debug(const void* d_in, int64_t in_len, const lz4ada_device_frame_job* jobs,
+                                     int64_t njobs, int32_t* verdict, int64_t* nblocks, lz4ada_block_desc* descs,
+                                     int64_t desc_cap, void* stream)
+{
+	return guarded(nullptr, [&] {
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		Index ix;
+		index_jobs("lz4ada_frames_index_device_debug", d_in, in_len, jobs, njobs, s, ix);
+		const size_t n = ix.order.size();
+		uint64_t nb = 0;
+		for (size_t k = 0; k < n; ++k) {
+			verdict[ix.order[k]] = ix.walk[k].verdict;
+			nblocks[ix.order[k]] = ix.walk[k].format ? int64_t(ix.walk[k].nblocks) : 0;
+			nb += ix.taken(k) ? ix.walk[k].nblocks : 0;
+		}
+		if (nb > uint64_t(std::max<int64_t>(desc_cap, 0)) || nb >= (uint64_t(1) << 31))
+			raise(LZ4ADA_CONSTRAINT_ERROR, "descriptor capacity exceeded");
+		if (n == 0 || nb == 0)
+			return;
+		const PassMeta m{ uint32_t(nb), uint32_t(n) };
+		fill_pass(ix, 0, n, static_cast<const uint8_t*>(d_in), m, s);
+		d2h(descs, m.d_desc, m.desc_b, s);
+	});
+}
+
+}  // extern "C"

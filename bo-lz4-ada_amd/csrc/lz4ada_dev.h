@@ -1,6 +1,7 @@
 // lz4ada_dev.h -- device helpers shared by the gfx950 kernels
 // (lz4ada_kernels.hip: per-wave decoder, XXH32, exact serial path;
-// lz4ada_wg.hip: workgroup-per-block decoder).
+// lz4ada_wg.hip: workgroup-per-block decoder; lz4ada_frames.hip and
+// lz4ada_frames_index.hip: the 64-bit scans of a many-frame pass).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -73,6 +74,50 @@ __device__ __forceinline__ int32_t wave_incl_max(int32_t v)
 	v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));  // row_bcast:15
 	v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));  // row_bcast:31
 	return v;
+}
+
+// wave_incl_scan on 64-bit sums: a tile of 4 MiB blocks already reaches 2^32
+// bytes.  The two halves move by the same DPP control.
+template <int CTRL, int ROW_MASK, bool BOUND>
+__device__ __forceinline__ uint64_t dpp64(uint64_t v)
+{
+	const uint32_t lo = uint32_t(__builtin_amdgcn_update_dpp(0, int(uint32_t(v)), CTRL, ROW_MASK, 0xf, BOUND));
+	const uint32_t hi =
+	        uint32_t(__builtin_amdgcn_update_dpp(0, int(uint32_t(v >> 32)), CTRL, ROW_MASK, 0xf, BOUND));
+	return uint64_t(lo) | (uint64_t(hi) << 32);
+}
+
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v)
+{
+	v += dpp64<0x111, 0xf, true>(v);   // row_shr:1
+	v += dpp64<0x112, 0xf, true>(v);   // row_shr:2
+	v += dpp64<0x114, 0xf, true>(v);   // row_shr:4
+	v += dpp64<0x118, 0xf, true>(v);   // row_shr:8
+	v += dpp64<0x142, 0xa, false>(v);  // row_bcast:15 into rows 1 and 3
+	v += dpp64<0x143, 0xc, false>(v);  // row_bcast:31 into rows 2 and 3
+	return v;
+}
+
+// Exclusive prefix of v over the workgroup's WG threads; *total: the
+// workgroup's sum.  wsum: one LDS word per wave.  Every thread calls it.
+template <uint32_t WG>
+__device__ __forceinline__ uint64_t wg_excl_scan(uint64_t v, uint64_t* wsum, uint64_t* total)
+{
+	const uint32_t wave = threadIdx.x >> 6;
+	const uint64_t incl = wave_incl_scan64(v);
+	__syncthreads();  // wsum's readers of an earlier call are done
+	if (lane_id() == 63)
+		wsum[wave] = incl;
+	__syncthreads();
+	uint64_t before = 0, all = 0;
+#pragma unroll
+	for (uint32_t w = 0; w < WG / 64; ++w) {
+		const uint64_t s = wsum[w];
+		before += w < wave ? s : 0;
+		all += s;
+	}
+	*total = all;
+	return before + incl - v;
 }
 
 __device__ __forceinline__ void wave_lds_fence() { asm volatile("" ::: "memory"); }

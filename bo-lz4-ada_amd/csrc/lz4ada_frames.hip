@@ -23,49 +23,6 @@ constexpr uint32_t PLAN_WG = 256;                     // threads per workgroup
 constexpr uint32_t PLAN_PER = PLAN_TILE / PLAN_WG;    // blocks per thread
 static_assert(PLAN_PER * PLAN_WG == PLAN_TILE, "a tile is a whole number of blocks per thread");
 
-// wave_incl_scan (lz4ada_dev.h) on 64-bit sums: a tile of 4 MiB blocks
-// already reaches 2^32 bytes.  The two halves move by the same DPP control.
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ uint64_t dpp64(uint64_t v)
-{
-	const uint32_t lo = uint32_t(__builtin_amdgcn_update_dpp(0, int(uint32_t(v)), CTRL, ROW_MASK, 0xf, BOUND));
-	const uint32_t hi =
-	        uint32_t(__builtin_amdgcn_update_dpp(0, int(uint32_t(v >> 32)), CTRL, ROW_MASK, 0xf, BOUND));
-	return uint64_t(lo) | (uint64_t(hi) << 32);
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v)
-{
-	v += dpp64<0x111, 0xf, true>(v);   // row_shr:1
-	v += dpp64<0x112, 0xf, true>(v);   // row_shr:2
-	v += dpp64<0x114, 0xf, true>(v);   // row_shr:4
-	v += dpp64<0x118, 0xf, true>(v);   // row_shr:8
-	v += dpp64<0x142, 0xa, false>(v);  // row_bcast:15 into rows 1 and 3
-	v += dpp64<0x143, 0xc, false>(v);  // row_bcast:31 into rows 2 and 3
-	return v;
-}
-
-// Exclusive prefix of v over the workgroup's PLAN_WG threads; *total: the
-// workgroup's sum.  wsum: one LDS word per wave.  Every thread calls it.
-__device__ __forceinline__ uint64_t wg_excl_scan(uint64_t v, uint64_t* wsum, uint64_t* total)
-{
-	const uint32_t wave = threadIdx.x >> 6;
-	const uint64_t incl = wave_incl_scan64(v);
-	__syncthreads();  // wsum's readers of an earlier call are done
-	if (lane_id() == 63)
-		wsum[wave] = incl;
-	__syncthreads();
-	uint64_t before = 0, all = 0;
-#pragma unroll
-	for (uint32_t w = 0; w < PLAN_WG / 64; ++w) {
-		const uint64_t s = wsum[w];
-		before += w < wave ? s : 0;
-		all += s;
-	}
-	*total = all;
-	return before + incl - v;
-}
-
 // The frame that holds block b: the last one whose first block is <= b
 // (frames without blocks share their `first` with the frame after them).
 __device__ __forceinline__ uint32_t frame_of_block(const FrameRec* fr, uint32_t nframes, uint32_t b)
@@ -113,7 +70,7 @@ __global__ __launch_bounds__(PLAN_WG) void k_frames_scan_tiles(
 		sum += len[k];
 	}
 	uint64_t total;
-	uint64_t off = wg_excl_scan(sum, wsum, &total);
+	uint64_t off = wg_excl_scan<PLAN_WG>(sum, wsum, &total);
 #pragma unroll
 	for (uint32_t k = 0; k < PLAN_PER; ++k) {
 		if (b0 + k < nblocks)
@@ -135,7 +92,7 @@ __global__ __launch_bounds__(PLAN_WG) void k_frames_scan_carry(uint64_t* __restr
 		const uint32_t t = t0 + threadIdx.x;
 		const uint64_t v = t < ntiles ? part[t] : 0;
 		uint64_t total;
-		const uint64_t off = wg_excl_scan(v, wsum, &total);
+		const uint64_t off = wg_excl_scan<PLAN_WG>(v, wsum, &total);
 		if (t < ntiles)
 			part[t] = carry + off;
 		carry += total;

@@ -539,10 +539,15 @@ int64_t env_bytes(const char* name, int64_t dflt)
 	return v > 0 ? int64_t(v) : dflt;
 }
 
-bool few_large_blocks(const std::vector<lz4ada_block_desc>& d)
+bool lone_blocks_disabled()
 {
 	static const bool off = getenv("LZ4ADA_NO_LONE") != nullptr;
-	if (off || d.empty() || d.size() > 24)
+	return off;
+}
+
+bool few_large_blocks(const std::vector<lz4ada_block_desc>& d)
+{
+	if (lone_blocks_disabled() || d.empty() || d.size() > 24)
 		return false;
 	uint32_t mx = 0;
 	for (const auto& x : d)

@@ -8,7 +8,8 @@
 // include it: lz4ada_facade.cpp (the streaming Update facade and the
 // XXHash32 C-ABI), lz4ada_bulk.cpp (the bulk frame paths and their C-ABI),
 // lz4ada_bulk_linked.cpp (the linked-frame bulk path), lz4ada_bulk_frames.cpp
-// (many frames in one device pass).  lz4ada_multi.cpp
+// (many frames in one device pass), lz4ada_bulk_frames_device.cpp (the same
+// pass from device memory to device memory).  lz4ada_multi.cpp
 // (the multi-GPU entry) keeps a per-device cache of its own and includes
 // only lz4ada_internal.h.
 //
@@ -278,6 +279,8 @@ uint32_t host_xxh32_final(const lz4ada_xxh32_state& h);
 // beats the bulk decoder's one wave per block (~13 ms per 4 MiB block, at
 // any count up to the chip's 2,048 resident waves) below ~30 blocks.
 bool few_large_blocks(const std::vector<lz4ada_block_desc>& d);
+// LZ4ADA_NO_LONE is set (read once per process): few_large_blocks is never true.
+bool lone_blocks_disabled();
 // decode_lone_blocks: every block of d (host descriptors, offsets into d_in
 // and d_out) through the lone-block decoder, stored ones as a copy, while
 // host threads hash the blocks' host bytes for their checksums
@@ -442,6 +445,15 @@ void partial_frame_check(int64_t left);
 // follows out.len after each frame or run that succeeded; the first failing
 // frame's exception propagates.
 void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t* committed);
+
+// What the many-frame engines share (lz4ada_bulk_frames.cpp; the device-input
+// engine is lz4ada_bulk_frames_device.cpp): a pass's slot byte budget
+// (LZ4ADA_BATCH_BYTES), the decoded length up to which a pass hashes a
+// content checksum on the GPU (LZ4ADA_BATCH_HASH_MAX), both read per call,
+// and the calling thread's counters behind lz4ada_last_batch_stats().
+int64_t batch_budget();
+int64_t batch_hash_max();
+lz4ada_batch_stats& batch_stats();
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

@@ -1,8 +1,8 @@
 // lz4ada_internal.h -- what the host units (lz4ada_host_common.h/.cpp,
 // lz4ada_facade.cpp, lz4ada_bulk.cpp, lz4ada_bulk_linked.cpp,
-// lz4ada_bulk_frames.cpp, lz4ada_multi.cpp) share with the gfx950 kernel
-// files (lz4ada_*.hip): the device status codes and the launchers'
-// declarations.  Not part of the public C-ABI.
+// lz4ada_bulk_frames.cpp, lz4ada_bulk_frames_device.cpp, lz4ada_multi.cpp)
+// share with the gfx950 kernel files (lz4ada_*.hip): the device status codes
+// and the launchers' declarations.  Not part of the public C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -341,5 +341,42 @@ hipError_t launch_frames_plan(const lz4ada_block_desc* d_desc, lz4ada_block_stat
 // four frames per wave.
 hipError_t launch_xxh32_spans(const uint8_t* d_buf, FrameRec* d_frames, uint32_t nframes,
                               uint64_t hash_max, hipStream_t stream);
+
+// ---- frames indexed on the device (lz4ada_frames_index.hip) ----
+// A job's bytes inside the device input: the frame and whatever follows it.
+struct FrameSpan {
+	uint64_t off, len;
+};
+// What k_frames_walk found out about one frame (frame_walk, lz4ada_frame_walk.h).
+struct FrameWalkRec {
+	int32_t verdict;  // LZ4ADA_BATCH_*; _OVER_BUDGET when its slots alone exceed the budget
+	uint32_t flags;   // FRAME_HAS_*
+	uint64_t nblocks;
+	uint64_t slots, caps;  // sum of round256(slot_cap), sum of slot_cap
+	int64_t frame_len;
+	uint64_t content_size;
+	uint32_t cksum;  // the declared content checksum
+	int32_t format;  // LZ4ADA_FORMAT_*, 0 when the frame does not index
+};
+// One lane per frame: d_walk[i] from the frame at d_span[i].  Reads no byte
+// outside a frame's span.
+hipError_t launch_frames_walk(const uint8_t* d_in, const FrameSpan* d_span, uint32_t nframes, bool no_lone,
+                              uint64_t budget, FrameWalkRec* d_walk, hipStream_t stream);
+// One workgroup: d_first[i] / d_slot[i] get the blocks / slot bytes of the
+// accepted frames (verdict LZ4ADA_BATCH_OK) before frame i, entry nframes the
+// totals.  Frames that are not accepted count as nothing.
+hipError_t launch_frames_scan(const FrameWalkRec* d_walk, uint32_t nframes, uint64_t* d_first,
+                              uint64_t* d_slot, hipStream_t stream);
+// One lane per frame: an accepted frame is walked again and its descriptors
+// go to d_desc[d_first[i] ..] as a pass needs them (in_off absolute in d_in,
+// out_off from d_slot[i] in steps of round256(slot_cap), out_cap = slot_cap);
+// every frame gets its record d_rec[i] (fail -1; a frame that is not accepted
+// holds no block).  Never writes past the frame's share of d_desc or of the
+// slots: should the second walk differ from the first (the input changed in
+// between), the frame's remaining descriptors are empty and its fail is 0.
+hipError_t launch_frames_fill(const uint8_t* d_in, const FrameSpan* d_span, const FrameWalkRec* d_walk,
+                              const uint64_t* d_first, const uint64_t* d_slot, uint32_t nframes,
+                              bool no_lone, lz4ada_block_desc* d_desc, FrameRec* d_rec,
+                              hipStream_t stream);
 
 }  // namespace lz4ada

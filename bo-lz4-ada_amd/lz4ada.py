@@ -187,6 +187,16 @@ class BatchStats(ctypes.Structure):
                 ("host_hashed", ctypes.c_int64)]
 
 
+class DeviceFrameJob(ctypes.Structure):
+    _fields_ = [("in_off", ctypes.c_int64), ("in_len", ctypes.c_int64), ("out_off", ctypes.c_int64),
+                ("out_len", ctypes.c_int64), ("consumed", ctypes.c_int64),
+                ("status", ctypes.c_int32), ("reason", ctypes.c_int32)]
+
+
+# DeviceFrameJob.reason: 1..4 are the BATCH_* reasons
+DEVFRAME_OK, DEVFRAME_BLOCK, DEVFRAME_SIZE, DEVFRAME_CHECKSUM = 0, 5, 6, 7
+EXACT_PATH = 9  # DeviceFrameJob.status of a frame the device pass did not decode
+
 BLOCK_STORED = 1
 BLOCK_HAS_CKSUM = 2
 FORMAT_MODERN, FORMAT_LEGACY, FORMAT_SKIPPABLE = 1, 2, 3
@@ -206,6 +216,11 @@ _sig = {
                                    ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
                                    ctypes.POINTER(ctypes.c_uint32),
                                    ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
+    "lz4ada_frames_device_bound": ([_vp, _i64, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_decode_frames_device": ([_vp, _i64, _vp, _i64, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_frame_walk_host": ([_vp, _i64, ctypes.POINTER(FrameInfo), _vp, _i64], ctypes.c_int),
+    "lz4ada_frames_index_device_debug": ([_vp, _i64, _vp, _i64, ctypes.POINTER(ctypes.c_int32), _pi64,
+                                          _vp, _i64, _vp], ctypes.c_int),
     "lz4ada_abi_version": ([], ctypes.c_int),
     "lz4ada_device_check": ([], ctypes.c_int),
     "lz4ada_error_name": ([ctypes.c_int], ctypes.c_char_p),
@@ -559,6 +574,111 @@ def xxh32_spans_device(d_buf: int, spans):
     ms = ctypes.c_float()
     _check(_lib.lz4ada_xxh32_spans_device(d_buf, off, ln, n, h, ctypes.byref(ms)), _thread_error())
     return list(h[:n]), ms.value
+
+
+# ------------------------------------- many frames, device memory to device
+
+def _device_jobs(spans):
+    """[(in_off, in_len)] -> DeviceFrameJob array (one spare entry when empty)."""
+    jobs = (DeviceFrameJob * max(len(spans), 1))()
+    for j, (off, n) in zip(jobs, spans):
+        j.in_off, j.in_len = off, n
+    return jobs
+
+
+def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0):
+    """Index the frames at spans [(in_off, in_len)] of the device buffer d_in
+    (raw pointer) on the device -> (an out_cap that always suffices, the
+    DeviceFrameJob array with the index's verdict per frame)."""
+    jobs = _device_jobs(spans)
+    bound = _i64()
+    _check(_lib.lz4ada_frames_device_bound(d_in, in_len, jobs, len(spans), ctypes.byref(bound),
+                                           stream), _thread_error())
+    return bound.value, jobs
+
+
+def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0):
+    """Decode the frames at spans [(in_off, in_len)] of the device buffer d_in
+    into the device buffer d_out (raw pointers) -> (bytes written, the
+    DeviceFrameJob array: out_off, out_len, consumed, status, reason).  A
+    frame with status EXACT_PATH was not decoded: explain_frame gives the
+    reference's verdict.  TooLittleMemory carries the needed size as .bound."""
+    jobs = _device_jobs(spans)
+    n = _i64()
+    st = _lib.lz4ada_decode_frames_device(d_in, in_len, jobs, len(spans), d_out, out_cap,
+                                          ctypes.byref(n), stream)
+    if st:
+        exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
+        exc.bound = n.value
+        raise exc
+    return n.value, jobs
+
+
+def decode_frames_tensor(t, spans, out=None):
+    """decode_frames_device for a CUDA torch.uint8 tensor holding the frames,
+    on torch's current stream -> (the decoded bytes as a uint8 tensor on the
+    same device, the DeviceFrameJob array).  out: a uint8 tensor there to
+    decode into; by default one is allocated from frames_device_bound."""
+    if torch is None:
+        raise RuntimeError("decode_frames_tensor needs torch")
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise ValueError("the frames must be a contiguous CUDA uint8 tensor")
+    with torch.cuda.device(t.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        if out is None:
+            bound, _ = frames_device_bound(t.data_ptr(), t.numel(), spans, stream)
+            out = torch.empty(max(bound, 1), dtype=torch.uint8, device=t.device)
+        elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8
+                  and out.is_contiguous()):
+            raise ValueError("out must be a contiguous CUDA uint8 tensor on the frames' device")
+        n, jobs = decode_frames_device(t.data_ptr(), t.numel(), spans, out.data_ptr(), out.numel(),
+                                       stream)
+    return out[:n], jobs
+
+
+def explain_frame(t_or_bytes, job):
+    """What the reference makes of one job's frame: its bytes are fetched to
+    the host (from a tensor or a bytes-like object holding the device input)
+    and decoded on their own -> decode_frame_partial's (decoded bytes, bytes
+    consumed, exception or None)."""
+    lo, hi = job.in_off, job.in_off + job.in_len
+    if torch is not None and isinstance(t_or_bytes, torch.Tensor):
+        data = t_or_bytes[lo:hi].cpu().numpy().tobytes()
+    else:
+        data = bytes(t_or_bytes[lo:hi])
+    return decode_frame_partial(data)
+
+
+def frame_walk_host(data, offset: int = 0):
+    """Test-only: the device index's frame walk run on the host ->
+    (verdict: a BATCH_* reason, FrameInfo, ctypes array of BlockDesc as
+    frame_index lays them out)."""
+    n = len(data) - offset
+    info = FrameInfo()
+    v = _lib.lz4ada_frame_walk_host(_addr(data, offset), n, ctypes.byref(info), None, 0)
+    descs = (BlockDesc * max(info.nblocks, 1))()
+    info2 = FrameInfo()
+    v2 = _lib.lz4ada_frame_walk_host(_addr(data, offset), n, ctypes.byref(info2), descs, info.nblocks)
+    assert v2 == v and bytes(info2) == bytes(info)
+    return v, info, descs
+
+
+def frames_index_device_debug(d_in: int, in_len: int, spans, stream: int = 0):
+    """Test-only: the index kernels alone -> (verdict per job, nblocks per
+    job, BlockDesc array of the accepted frames' blocks in rising in_off)."""
+    jobs = _device_jobs(spans)
+    n = len(spans)
+    verdict = (ctypes.c_int32 * max(n, 1))()
+    nblocks = (_i64 * max(n, 1))()
+    # without room for descriptors first: the verdicts and the block counts
+    st = _lib.lz4ada_frames_index_device_debug(d_in, in_len, jobs, n, verdict, nblocks, None, 0, stream)
+    if st and not (st == 7 and _thread_error() == "descriptor capacity exceeded"):
+        _check(st, _thread_error())
+    total = sum(nblocks[i] for i in range(n) if verdict[i] == BATCH_OK)
+    descs = (BlockDesc * max(total, 1))()
+    _check(_lib.lz4ada_frames_index_device_debug(d_in, in_len, jobs, n, verdict, nblocks, descs,
+                                                 total, stream), _thread_error())
+    return list(verdict[:n]), list(nblocks[:n]), descs
 
 
 def _devices(n_gpus: int, devices):

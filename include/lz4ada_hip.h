@@ -446,6 +446,82 @@ int64_t lz4ada_batch_hash_max(void);
 int lz4ada_xxh32_spans_device(const void *d_buf, const int64_t *off, const int64_t *len,
                               int64_t nspans, uint32_t *hash, float *kernel_ms);
 
+/* ------------------------- many frames, device memory to device memory */
+/*
+ * The same pass for frames that already lie in device memory (read there by
+ * another library, received over RCCL, produced by a kernel) and whose
+ * plaintext is wanted there: the frames are indexed where they lie (one GPU
+ * lane walks one frame's header and size words), the decoders read d_in
+ * itself, and the compaction writes into d_out.  The
+ * host sees per-frame records only -- verdicts, sizes, checksums -- with one
+ * exception: a content checksum over more than lz4ada_batch_hash_max()
+ * decoded bytes is hashed by the host chain (lz4ada_content_xxh32_d2h), so
+ * those bytes visit the host to be hashed, and go nowhere else.
+ *
+ * jobs is a host array, in any order; the engine works in rising in_off.  A
+ * job's range is the frame and whatever follows it (Single_Frame semantics),
+ * so it may run on to the end of d_in.  API misuse, LZ4ADA_ASSERTION_ERROR
+ * with nothing launched: a range outside [0, in_len), or two ranges that
+ * share bytes unless the earlier one ends with d_in.  An accepted frame that
+ * reaches into the next job's range is the same misuse, found after the
+ * index kernel alone has run.
+ *
+ * A frame the pass does not find good in every respect gets status
+ * LZ4ADA_EXACT_PATH, a reason, and out_len = consumed = 0; no exception text
+ * is invented: lz4ada_decode_frame / _partial on the frame's host bytes give
+ * the reference's result.  A skippable frame is LZ4ADA_OK with out_len 0.
+ * Both calls return LZ4ADA_OK when the call itself worked, whatever the
+ * per-job statuses.  lz4ada_last_batch_stats() counts the frames committed
+ * (frames_batched), the passes and the checksums; lz4ada_last_path() is
+ * LZ4ADA_PATH_BATCH | LZ4ADA_PATH_INDEPENDENT.  Host synchronisations on
+ * `stream`: one for the index (per call) and one per pass.
+ */
+#define LZ4ADA_DEVFRAME_OK 0
+/* 1..4 keep the LZ4ADA_BATCH_* meanings (LINKED, BIG_BLOCK, OVER_BUDGET, NOT_INDEXED) */
+#define LZ4ADA_DEVFRAME_BLOCK 5     /* a block failed: status, slot overflow, block checksum */
+#define LZ4ADA_DEVFRAME_SIZE 6      /* decoded length != declared content size */
+#define LZ4ADA_DEVFRAME_CHECKSUM 7  /* content checksum mismatch */
+
+typedef struct {
+	int64_t in_off, in_len;   /* in: the frame, and whatever follows it, inside d_in */
+	int64_t out_off, out_len; /* out: its bytes inside d_out (out_len 0 unless status is OK) */
+	int64_t consumed;         /* out: bytes of the frame (0 unless OK) */
+	int32_t status;           /* out: LZ4ADA_OK, or LZ4ADA_EXACT_PATH: not decoded here */
+	int32_t reason;           /* out: LZ4ADA_DEVFRAME_* */
+} lz4ada_device_frame_job;
+
+/* Index njobs frames on the device and return an out_cap that always suffices
+ * (sum of slot caps of the frames the pass takes).  Every job gets the index's
+ * verdict (status, reason 0..4).  Synchronous on stream (a hipStream_t). */
+int lz4ada_frames_device_bound(const void *d_in, int64_t in_len,
+                               lz4ada_device_frame_job *jobs, int64_t njobs,
+                               int64_t *bound, void *stream);
+/* Decode.  No payload byte crosses to the host.  The frames' bytes lie in
+ * d_out in rising in_off, back to back within a pass; bytes between reported
+ * spans are unspecified (a failed frame's blocks), bytes at and beyond
+ * *out_len are not written.  out_cap below the bound: LZ4ADA_TOO_LITTLE_MEMORY,
+ * *out_len = the bound, d_out untouched.  Synchronous on stream. */
+int lz4ada_decode_frames_device(const void *d_in, int64_t in_len,
+                                lz4ada_device_frame_job *jobs, int64_t njobs,
+                                void *d_out, int64_t out_cap, int64_t *out_len, void *stream);
+
+/* Test-only, in the spirit of lz4ada_index_table_debug. */
+/* The walk on the host: verdict as return value (LZ4ADA_DEVFRAME_* 0..4), info
+ * and descs as lz4ada_frame_index lays them out (descs may be NULL; at most
+ * desc_cap are written, info->nblocks counts them all).  info is complete
+ * unless the verdict is NOT_INDEXED.  Host only, no HIP call. */
+int lz4ada_frame_walk_host(const uint8_t *frame, int64_t len, lz4ada_frame_info *info,
+                           lz4ada_block_desc *descs, int64_t desc_cap);
+/* k_frames_walk + scan + k_frames_fill alone: per job the verdict and nblocks
+ * (0 for a frame that does not index), and the descriptors of all accepted
+ * frames in pass order (rising in_off), copied to the host: in_off absolute in
+ * d_in, out_off the slot layout (steps of slot capacity rounded up to 256),
+ * out_cap the slot capacity. */
+int lz4ada_frames_index_device_debug(const void *d_in, int64_t in_len,
+                                     const lz4ada_device_frame_job *jobs, int64_t njobs,
+                                     int32_t *verdict, int64_t *nblocks,
+                                     lz4ada_block_desc *descs, int64_t desc_cap, void *stream);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
