@@ -68,11 +68,17 @@ package body LZ4Ada.GPU is
 
 	procedure Decode_Frames(Jobs:          in out Frame_Jobs;
 				Output:        out    System.Address;
-				Output_Length: out    Interfaces.Integer_64) is
+				Output_Length: out    Interfaces.Integer_64;
+				Linked:        in     Boolean := False) is
 		P: aliased System.Address;
 		L: aliased Interfaces.Integer_64;
 	begin
-		Check(C_Decode_Frames(Jobs'Address, Jobs'Length, P'Access, L'Access));
+		if Linked then
+			Check(C_Decode_Frames_Opt(Jobs'Address, Jobs'Length, Frames_Linked,
+				P'Access, L'Access));
+		else
+			Check(C_Decode_Frames(Jobs'Address, Jobs'Length, P'Access, L'Access));
+		end if;
 		Output        := P;
 		Output_Length := L;
 	end Decode_Frames;
@@ -80,12 +86,18 @@ package body LZ4Ada.GPU is
 	function Frames_Device_Bound(D_In:   in     System.Address;
 				In_Len: in     Interfaces.Integer_64;
 				Jobs:   in out Device_Frame_Jobs;
-				Stream: in     System.Address := System.Null_Address)
+				Stream: in     System.Address := System.Null_Address;
+				Linked: in     Boolean := False)
 				return Interfaces.Integer_64 is
 		B: aliased Interfaces.Integer_64;
 	begin
-		Check(C_Frames_Device_Bound(D_In, In_Len, Jobs'Address, Jobs'Length,
-			B'Access, Stream));
+		if Linked then
+			Check(C_Frames_Device_Bound_Opt(D_In, In_Len, Jobs'Address, Jobs'Length,
+				Frames_Linked, B'Access, Stream));
+		else
+			Check(C_Frames_Device_Bound(D_In, In_Len, Jobs'Address, Jobs'Length,
+				B'Access, Stream));
+		end if;
 		return B;
 	end Frames_Device_Bound;
 
@@ -95,12 +107,18 @@ package body LZ4Ada.GPU is
 				D_Out:         in     System.Address;
 				Out_Cap:       in     Interfaces.Integer_64;
 				Output_Length: out    Interfaces.Integer_64;
-				Stream:        in     System.Address := System.Null_Address) is
+				Stream:        in     System.Address := System.Null_Address;
+				Linked:        in     Boolean := False) is
 		L:  aliased Interfaces.Integer_64;
 		St: Interfaces.Integer_32;
 	begin
-		St := C_Decode_Frames_Device(D_In, In_Len, Jobs'Address, Jobs'Length,
-			D_Out, Out_Cap, L'Access, Stream);
+		if Linked then
+			St := C_Decode_Frames_Device_Opt(D_In, In_Len, Jobs'Address, Jobs'Length,
+				Frames_Linked, D_Out, Out_Cap, L'Access, Stream);
+		else
+			St := C_Decode_Frames_Device(D_In, In_Len, Jobs'Address, Jobs'Length,
+				D_Out, Out_Cap, L'Access, Stream);
+		end if;
 		Output_Length := L;  -- the bound, when Too_Little_Memory follows
 		Check(St);
 	end Decode_Frames_Device;

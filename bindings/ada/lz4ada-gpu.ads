@@ -53,9 +53,16 @@ package LZ4Ada.GPU is
 	-- Raises only when the call itself failed.  Output is allocated by the
 	-- library (Output_Length bytes, every job's bytes at its Out_Off);
 	-- release it with Buffer_Free.
+	-- Linked: lz4ada_decode_frames_opt with LZ4ADA_FRAMES_LINKED -- linked
+	-- frames up to Batch_Linked_Max share the passes (one wave per frame).
 	procedure Decode_Frames(Jobs:          in out Frame_Jobs;
 				Output:        out    System.Address;
-				Output_Length: out    Interfaces.Integer_64);
+				Output_Length: out    Interfaces.Integer_64;
+				Linked:        in     Boolean := False);
+	-- lz4ada_batch_linked_max: the slot bytes up to which a linked frame
+	-- shares a pass (LZ4ADA_BATCH_LINKED_MAX overrides the default).
+	function Batch_Linked_Max return Interfaces.Integer_64;
+	pragma Import(C, Batch_Linked_Max, "lz4ada_batch_linked_max");
 	-- lz4ada_frames_error: the message of job I (Jobs'First based) of the
 	-- last Decode_Frames call of this task's thread.
 	function Frames_Error(Jobs: in Frame_Jobs; I: in Positive) return String;
@@ -88,7 +95,8 @@ package LZ4Ada.GPU is
 	function Frames_Device_Bound(D_In:   in     System.Address;
 				In_Len: in     Interfaces.Integer_64;
 				Jobs:   in out Device_Frame_Jobs;
-				Stream: in     System.Address := System.Null_Address)
+				Stream: in     System.Address := System.Null_Address;
+				Linked: in     Boolean := False)
 				return Interfaces.Integer_64;
 	-- Too_Little_Memory when Out_Cap is below the bound (Output_Length then
 	-- holds the bound and D_Out is untouched).
@@ -98,7 +106,8 @@ package LZ4Ada.GPU is
 				D_Out:         in     System.Address;
 				Out_Cap:       in     Interfaces.Integer_64;
 				Output_Length: out    Interfaces.Integer_64;
-				Stream:        in     System.Address := System.Null_Address);
+				Stream:        in     System.Address := System.Null_Address;
+				Linked:        in     Boolean := False);
 
 	-- lz4ada_rccl_version: the RCCL this process bound (22606 = 2.26.6).
 	function RCCL_Version return Interfaces.Integer_32;
@@ -147,5 +156,30 @@ private
 			Out_Len: access Interfaces.Integer_64; Stream: System.Address)
 			return Interfaces.Integer_32;
 	pragma Import(C, C_Decode_Frames_Device, "lz4ada_decode_frames_device");
+
+	-- the same three with flags (LZ4ADA_FRAMES_LINKED = 1)
+	Frames_Linked: constant Interfaces.Unsigned_32 := 1;
+
+	function C_Decode_Frames_Opt(Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Flags: Interfaces.Unsigned_32;
+			Out_Buf: access System.Address;
+			Out_Len: access Interfaces.Integer_64)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Decode_Frames_Opt, "lz4ada_decode_frames_opt");
+
+	function C_Frames_Device_Bound_Opt(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Flags: Interfaces.Unsigned_32;
+			Bound: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Frames_Device_Bound_Opt, "lz4ada_frames_device_bound_opt");
+
+	function C_Decode_Frames_Device_Opt(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Flags: Interfaces.Unsigned_32;
+			D_Out: System.Address; Out_Cap: Interfaces.Integer_64;
+			Out_Len: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Decode_Frames_Device_Opt, "lz4ada_decode_frames_device_opt");
 
 end LZ4Ada.GPU;

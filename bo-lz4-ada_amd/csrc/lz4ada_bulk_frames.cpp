@@ -8,6 +8,10 @@
 // lz4ada_decode_stream / _alloc.  A frame the pass does not find good in
 // every respect is decoded again by decode_one_frame (lz4ada_bulk.cpp), so
 // every error text is the reference's; this unit invents none for a decode.
+// With LZ4ADA_FRAMES_LINKED, linked frames up to lz4ada_batch_linked_max()
+// share the pass: the frames of a pass are cut into runs of
+// one kind, an independent run decoded as before and a linked run by one wave
+// per frame (k_decode_idx_frames).
 #include "lz4ada_host_common.h"
 
 using namespace lz4ada;
@@ -30,6 +34,14 @@ constexpr int64_t BATCH_HASH_MAX = int64_t(16) << 20;
 // lz4ada_decode_stream takes the pass when the stream holds at least this
 // many batchable frames with blocks (profiles/frames_batch_ab.txt).
 constexpr int64_t BATCH_MIN_FRAMES = 2;
+// A linked frame shares a pass (LZ4ADA_FRAMES_LINKED) when its slots sum to
+// at most this: one wave walks the whole frame, so past some size the frame
+// is faster on its own, every block at once (lz4ada_bulk_linked.cpp).
+// Measured (profiles/frames_linked_ab.txt): a pass of 2 frames
+// of 32 x 64 KiB is still 1.17x faster than the two on their own (7.9 against
+// 9.3 ms), one of 2 frames of 64 x 64 KiB is 1.46x slower (15.5 against
+// 10.6 ms); sizes in between were not measured.
+constexpr int64_t BATCH_LINKED_MAX = int64_t(2) << 20;
 
 thread_local lz4ada_batch_stats g_stats{};
 thread_local std::vector<std::string> g_job_errors;
@@ -43,6 +55,7 @@ struct Frame {
 	uint64_t slots = 0;  // its slots as the pass lays them out: sum of round256(slot_cap)
 	uint64_t caps = 0;   // sum of slot_cap: what it can decode to
 	bool skippable() const { return info.format == LZ4ADA_FORMAT_SKIPPABLE; }
+	bool linked() const { return info.format == LZ4ADA_FORMAT_MODERN && !info.independent; }
 };
 
 // The switches that pin a frame to one of the single-frame paths pin the
@@ -53,8 +66,9 @@ bool batch_enabled()
 }
 
 // Index the frame at fr.p and say whether it can share a pass.  *why (may
-// be null) gets the exception of a frame that does not index.
-void classify(Frame& fr, uint64_t budget, Error* why)
+// be null) gets the exception of a frame that does not index.  flags:
+// LZ4ADA_FRAMES_LINKED lets a linked frame of at most linked_max slot bytes in.
+void classify(Frame& fr, uint64_t budget, Error* why, uint32_t flags, uint64_t linked_max)
 {
 	fr.reason = LZ4ADA_BATCH_NOT_INDEXED;
 	fr.descs.clear();
@@ -70,7 +84,7 @@ void classify(Frame& fr, uint64_t budget, Error* why)
 	fr.reason = LZ4ADA_BATCH_OK;
 	if (fr.skippable())
 		return;  // consumed, no output
-	if (!fr.info.independent) {
+	if (fr.linked() && !(flags & LZ4ADA_FRAMES_LINKED)) {
 		fr.reason = LZ4ADA_BATCH_LINKED;
 		return;
 	}
@@ -86,6 +100,8 @@ void classify(Frame& fr, uint64_t budget, Error* why)
 	// (decode_lone_blocks) than as one wave each in a pass
 	if (few_large_blocks(fr.descs))
 		fr.reason = LZ4ADA_BATCH_BIG_BLOCK;
+	if (fr.reason == LZ4ADA_BATCH_OK && fr.linked() && fr.slots > linked_max)
+		fr.reason = LZ4ADA_BATCH_LINKED;
 	if (fr.reason == LZ4ADA_BATCH_OK && fr.slots > budget)
 		fr.reason = LZ4ADA_BATCH_OVER_BUDGET;
 }
@@ -109,7 +125,8 @@ void committed_now(const Report& rp, const Sink& out)
 void report_batched(const Report& rp, const Frame& fr, size_t i, int64_t off, int64_t n)
 {
 	++g_stats.frames_batched;
-	const int bits = LZ4ADA_PATH_BATCH | (fr.skippable() ? 0 : LZ4ADA_PATH_INDEPENDENT);
+	const int bits = LZ4ADA_PATH_BATCH |
+	                 (fr.skippable() ? 0 : fr.linked() ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT);
 	add_last_path(bits);
 	if (rp.jobs) {
 		lz4ada_frame_job& j = rp.jobs[i];
@@ -202,6 +219,14 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
 	uint8_t* const d_meta = scratch(SC_BATCH_META, desc_b + rec_b + st_b + off_b + loc_b + part_b);
 	if (!d_in || !d_slots || !d_cmp || !d_meta)
 		return false;
+	// the linked runs' sequence index, laid out as one launch_index over the
+	// whole pass would lay it out
+	bool any_linked = false;
+	for (size_t k = lo; k < hi; ++k)
+		any_linked = any_linked || (fs[k].linked() && !fs[k].descs.empty());
+	uint8_t* const d_tab = any_linked ? scratch(SC_TAB, index_table_bytes(stage_len, nb)) : nullptr;
+	if (any_linked && !d_tab)
+		return false;
 	auto* const d_desc = reinterpret_cast<lz4ada_block_desc*>(d_meta);
 	auto* const d_rec = reinterpret_cast<FrameRec*>(d_meta + desc_b);
 	auto* const d_st = reinterpret_cast<lz4ada_block_status*>(d_meta + desc_b + rec_b);
@@ -230,7 +255,7 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
 		r.first = b;
 		r.nblocks = uint32_t(fr.descs.size());
 		r.flags = (fr.info.has_content_size ? FRAME_HAS_SIZE : 0u) |
-		          (fr.info.content_checksum ? FRAME_HAS_CKSUM : 0u);
+		          (fr.info.content_checksum ? FRAME_HAS_CKSUM : 0u) | (fr.linked() ? FRAME_LINKED : 0u);
 		r.content_size = fr.info.content_size;
 		r.fail = -1;
 		h_rec[k - lo] = r;
@@ -249,7 +274,23 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
 	HIP_OK(hipMemcpyAsync(d_meta, hmeta.p, desc_b + rec_b, hipMemcpyHostToDevice, stream));
 	if (nb)
 		HIP_OK(hipMemsetAsync(d_st, 0, st_b, stream));
-	HIP_OK(launch_decode_checked(d_in, stage_len, d_desc, nb, d_slots, d_st, stream));
+	// the decode step: each maximal run of frames of one kind is one launch set
+	// over its sub-range of the descriptors (a pass of one kind: one set)
+	// (a frame without blocks rides in whichever run it falls into)
+	for (size_t k = lo; k < hi;) {
+		int kind = -1;
+		size_t m = k;
+		for (; m < hi; ++m) {
+			const int km = fs[m].descs.empty() ? -1 : int(fs[m].linked());
+			if (kind >= 0 && km >= 0 && km != kind)
+				break;
+			kind = kind >= 0 ? kind : km;
+		}
+		const PassRun run{ h_rec[k - lo].first, m < hi ? h_rec[m - lo].first : nb, uint32_t(k - lo),
+			           uint32_t(m - lo), kind == 1 };
+		decode_pass_run(d_in, stage_len, d_desc, nb, d_tab, d_slots, d_st, d_rec, run, stream);
+		k = m;
+	}
 	HIP_OK(launch_frames_plan(d_desc, d_st, nb, d_rec, nf, d_off, d_loc, d_part, stream));
 	HIP_OK(launch_compact(d_slots, d_desc, d_off, d_st, nb, d_cmp, stream));
 	HIP_OK(launch_xxh32_spans(d_cmp, d_rec, nf, hash_max, stream));
@@ -351,6 +392,33 @@ void run_frames(const std::vector<Frame>& fs, bool contiguous, Sink& out, const 
 }  // namespace
 
 int64_t batch_hash_max() { return env_bytes("LZ4ADA_BATCH_HASH_MAX", BATCH_HASH_MAX); }
+int64_t batch_linked_max() { return env_bytes("LZ4ADA_BATCH_LINKED_MAX", BATCH_LINKED_MAX); }
+uint32_t batch_env_flags()
+{
+	const char* e = getenv("LZ4ADA_BATCH_LINKED");
+	return e && *e && *e != '0' ? LZ4ADA_FRAMES_LINKED : 0u;
+}
+
+void decode_pass_run(const uint8_t* d_in, uint64_t in_len, const lz4ada_block_desc* d_desc, uint32_t nb,
+                     uint8_t* d_tab, uint8_t* d_slots, lz4ada_block_status* d_st, const FrameRec* d_rec,
+                     const PassRun& run, hipStream_t stream)
+{
+	const uint32_t n = run.b1 - run.b0;
+	if (n == 0)
+		return;
+	if (!run.linked) {
+		HIP_OK(launch_decode_checked(d_in, in_len, d_desc + run.b0, n, d_slots, d_st + run.b0, stream));
+		return;
+	}
+	// pass 1 over the run's blocks (the table's records land where block
+	// b0 + i of the whole pass has them), the block checksums beside it, then
+	// one wave per frame
+	HIP_OK(launch_block_checksums_beside(d_in, d_desc + run.b0, n, d_st + run.b0, stream));
+	HIP_OK(launch_index(d_in, in_len, d_desc + run.b0, n, d_tab + size_t(run.b0) * 64, d_st + run.b0, stream));
+	HIP_OK(launch_decode_idx_frames(d_in, in_len, d_desc, nb, d_tab, d_slots, d_st, d_rec + run.f0,
+	                                run.f1 - run.f0, stream));
+	HIP_OK(join_block_checksums(stream));
+}
 lz4ada_batch_stats& batch_stats() { return g_stats; }
 
 void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t* committed)
@@ -371,13 +439,14 @@ void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t*
 		}
 	}
 	if (several) {
-		const uint64_t budget = uint64_t(batch_budget());
+		const uint64_t budget = uint64_t(batch_budget()), linked_max = uint64_t(batch_linked_max());
+		const uint32_t flags = batch_env_flags();
 		int64_t real = 0;
 		while (pos < len) {
 			Frame fr;
 			fr.p = input + pos;
 			fr.len = len - pos;
-			classify(fr, budget, nullptr);
+			classify(fr, budget, nullptr, flags, linked_max);
 			if (fr.reason == LZ4ADA_BATCH_NOT_INDEXED)
 				break;  // from here on the per-frame loop, which raises in the reference's order
 			pos += fr.info.frame_len;
@@ -410,16 +479,22 @@ extern "C" {
 int lz4ada_stream_index(const uint8_t* input, int64_t len, lz4ada_stream_entry* entries, int64_t cap,
                         int64_t* nframes)
 {
+	return lz4ada_stream_index_opt(input, len, batch_env_flags(), entries, cap, nframes);
+}
+
+int lz4ada_stream_index_opt(const uint8_t* input, int64_t len, uint32_t flags, lz4ada_stream_entry* entries,
+                            int64_t cap, int64_t* nframes)
+{
 	*nframes = 0;
 	return guarded(nullptr, [&] {
-		const uint64_t budget = uint64_t(batch_budget());
+		const uint64_t budget = uint64_t(batch_budget()), linked_max = uint64_t(batch_linked_max());
 		int64_t pos = 0;
 		while (pos < len) {
 			Frame fr;
 			fr.p = input + pos;
 			fr.len = len - pos;
 			Error why{ LZ4ADA_OK, "" };
-			classify(fr, budget, &why);
+			classify(fr, budget, &why, flags, linked_max);
 			if (fr.reason == LZ4ADA_BATCH_NOT_INDEXED)
 				raise(why.code, why.msg);
 			if (entries) {
@@ -440,6 +515,12 @@ int lz4ada_stream_index(const uint8_t* input, int64_t len, lz4ada_stream_entry* 
 
 int lz4ada_decode_frames(lz4ada_frame_job* jobs, int64_t njobs, uint8_t** out, int64_t* out_len)
 {
+	return lz4ada_decode_frames_opt(jobs, njobs, batch_env_flags(), out, out_len);
+}
+
+int lz4ada_decode_frames_opt(lz4ada_frame_job* jobs, int64_t njobs, uint32_t flags, uint8_t** out,
+                             int64_t* out_len)
+{
 	*out = nullptr;
 	*out_len = 0;
 	g_stats = lz4ada_batch_stats{};
@@ -451,7 +532,7 @@ int lz4ada_decode_frames(lz4ada_frame_job* jobs, int64_t njobs, uint8_t** out, i
 		if (!jobs || njobs < 0)
 			raise(LZ4ADA_ASSERTION_ERROR, "lz4ada_decode_frames: jobs is NULL or njobs is negative");
 		g_job_errors.assign(size_t(njobs), std::string());
-		const uint64_t budget = uint64_t(batch_budget());
+		const uint64_t budget = uint64_t(batch_budget()), linked_max = uint64_t(batch_linked_max());
 		std::vector<Frame> fs(static_cast<size_t>(njobs));
 		for (int64_t i = 0; i < njobs; ++i) {
 			lz4ada_frame_job& j = jobs[i];
@@ -461,7 +542,7 @@ int lz4ada_decode_frames(lz4ada_frame_job* jobs, int64_t njobs, uint8_t** out, i
 			fs[size_t(i)].p = j.frame;
 			fs[size_t(i)].len = j.len;
 			if (j.frame && j.len >= 7)
-				classify(fs[size_t(i)], budget, nullptr);
+				classify(fs[size_t(i)], budget, nullptr, flags, linked_max);
 		}
 		Report rp;
 		rp.jobs = jobs;
@@ -484,6 +565,55 @@ const char* lz4ada_frames_error(int64_t i)
 void lz4ada_last_batch_stats(lz4ada_batch_stats* out) { *out = g_stats; }
 
 int64_t lz4ada_batch_hash_max(void) { return batch_hash_max(); }
+int64_t lz4ada_batch_linked_max(void) { return batch_linked_max(); }
+
+// Test-only (lz4ada_hip.h): k_index over the marked frames' blocks, then
+// k_decode_idx_frames over every record; the unmarked frames' blocks see no
+// launch at all.
+int lz4ada_decode_idx_frames_debug(const void* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_descs,
+                                   int64_t nblocks, const int64_t* first, const uint8_t* linked, int64_t nframes,
+                                   void* d_out, lz4ada_block_status* d_status, void* stream)
+{
+	return guarded(nullptr, [&] {
+		if (nblocks < 0 || nblocks >= (int64_t(1) << 31) || nframes < 0 || nframes >= (int64_t(1) << 31) ||
+		    !first || (nframes > 0 && !linked))
+			raise(LZ4ADA_CONSTRAINT_ERROR, "block or frame count out of range");
+		for (int64_t i = 0; i < nframes; ++i)
+			if (first[i] < 0 || first[i] > first[i + 1] || first[i + 1] > nblocks)
+				raise(LZ4ADA_CONSTRAINT_ERROR, "frame block ranges must rise within the blocks");
+		if (nframes == 0 || nblocks == 0)
+			return;
+		device_check_or_raise();
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		const auto* const in = static_cast<const uint8_t*>(d_frame);
+		std::vector<FrameRec> recs(static_cast<size_t>(nframes));
+		for (int64_t i = 0; i < nframes; ++i) {
+			FrameRec& r = recs[size_t(i)];
+			r = FrameRec{};
+			r.first = uint32_t(first[i]);
+			r.nblocks = uint32_t(first[i + 1] - first[i]);
+			r.flags = linked[i] ? FRAME_LINKED : 0u;
+			r.fail = -1;
+		}
+		DevBuf<FrameRec> d_rec;
+		d_rec.reserve(recs.size());
+		DevBuf<uint8_t> tab;
+		tab.reserve(index_table_bytes(frame_len, uint32_t(nblocks)));
+		vec_h2d(d_rec, recs, s);
+		for (int64_t i = 0; i < nframes;) {  // pass 1 per run of marked frames
+			int64_t m = i;
+			while (m < nframes && (linked[m] != 0) == (linked[i] != 0))
+				++m;
+			if (linked[i] && first[m] > first[i])
+				HIP_OK(launch_index(in, frame_len, d_descs + first[i], uint32_t(first[m] - first[i]),
+				                    tab.p + size_t(first[i]) * 64, d_status + first[i], s));
+			i = m;
+		}
+		HIP_OK(launch_decode_idx_frames(in, frame_len, d_descs, uint32_t(nblocks), tab.p,
+		                                static_cast<uint8_t*>(d_out), d_status, d_rec.p, uint32_t(nframes), s));
+		HIP_OK(hipStreamSynchronize(s));
+	});
+}
 
 int lz4ada_xxh32_spans_device(const void* d_buf, const int64_t* off, const int64_t* len, int64_t nspans,
                               uint32_t* hash, float* kernel_ms)

@@ -12,7 +12,9 @@
 // than lz4ada_batch_hash_max() bytes is hashed by the host chain
 // (content_xxh32_d2h with no host destination).  A frame the pass does not
 // find good in every respect gets LZ4ADA_EXACT_PATH and a reason; this unit
-// invents no exception text.
+// invents no exception text.  With LZ4ADA_FRAMES_LINKED the walk accepts
+// linked frames up to lz4ada_batch_linked_max() and the pass decodes them one
+// wave per frame, in runs by kind as the host engine does.
 #include "lz4ada_frame_walk.h"
 #include "lz4ada_host_common.h"
 
@@ -32,6 +34,9 @@ struct Index {
 	FrameSpan* d_span = nullptr;
 	FrameWalkRec* d_walk = nullptr;
 	uint64_t *d_first = nullptr, *d_slot = nullptr;  // n + 1 entries each
+	bool take_linked = false;                        // LZ4ADA_FRAMES_LINKED, and its cap
+	uint64_t linked_max = 0;
+	bool linked(size_t k) const { return (walk[k].flags & FRAME_LINKED) != 0; }
 	bool taken(size_t k) const { return walk[k].verdict == LZ4ADA_BATCH_OK; }
 	bool skippable(size_t k) const { return walk[k].format == LZ4ADA_FORMAT_SKIPPABLE; }
 };
@@ -44,8 +49,10 @@ struct Index {
 // The argument checks (nothing is launched before they pass), the sort, and
 // the walk of every job's frame with its one host synchronisation.
 void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ada_device_frame_job* jobs,
-                int64_t njobs, hipStream_t stream, Index& ix)
+                int64_t njobs, uint32_t flags, hipStream_t stream, Index& ix)
 {
+	ix.take_linked = (flags & LZ4ADA_FRAMES_LINKED) != 0;
+	ix.linked_max = uint64_t(batch_linked_max());
 	if (njobs < 0 || (njobs > 0 && !jobs) || in_len < 0 || (in_len > 0 && !d_in) ||
 	    njobs >= (int64_t(1) << 31))
 		misuse(entry, "jobs or d_in is NULL, or a count is out of range");
@@ -88,7 +95,7 @@ void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ad
 	memcpy(h.p, ix.span.data(), span_b);
 	HIP_OK(hipMemcpyAsync(ix.d_span, h.p, span_b, hipMemcpyHostToDevice, stream));
 	HIP_OK(launch_frames_walk(static_cast<const uint8_t*>(d_in), ix.d_span, uint32_t(n), lone_blocks_disabled(),
-	                          uint64_t(batch_budget()), ix.d_walk, stream));
+	                          uint64_t(batch_budget()), ix.take_linked, ix.linked_max, ix.d_walk, stream));
 	// the index's host synchronisation: verdicts and sizes, no frame byte
 	HIP_OK(hipMemcpyAsync(h.p, ix.d_walk, walk_b, hipMemcpyDeviceToHost, stream));
 	HIP_OK(hipStreamSynchronize(stream));
@@ -148,7 +155,7 @@ void fill_pass(const Index& ix, size_t lo, size_t hi, const uint8_t* d_in, const
 	const uint32_t nf = uint32_t(hi - lo);
 	HIP_OK(launch_frames_scan(ix.d_walk + lo, nf, ix.d_first, ix.d_slot, stream));
 	HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, ix.d_walk + lo, ix.d_first, ix.d_slot, nf,
-	                          lone_blocks_disabled(), m.d_desc, m.d_rec, stream));
+	                          lone_blocks_disabled(), ix.take_linked, ix.linked_max, m.d_desc, m.d_rec, stream));
 }
 
 void job_rejected(lz4ada_device_frame_job& j, int reason)
@@ -185,7 +192,35 @@ void run_device_pass(const Index& ix, size_t lo, size_t hi, uint32_t nb, uint64_
 	// in_off rises strictly over the pass (the jobs are sorted and their frames
 	// disjoint) and in_len covers every block: what the index decoder's table
 	// relies on (lz4ada_bulk_frames.cpp, run_pass)
-	HIP_OK(launch_decode_checked(d_in, in_len, m.d_desc, nb, d_slots, m.d_st, stream));
+	// the decode step in runs of one kind (lz4ada_bulk_frames.cpp, run_pass);
+	// the frames' first blocks as k_frames_scan counts them: the accepted
+	// frames' block counts, in order
+	{
+		bool any_linked = false;
+		for (size_t k = lo; k < hi; ++k)
+			any_linked = any_linked || (ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks);
+		uint8_t* const d_tab = any_linked ? scratch(SC_TAB, index_table_bytes(in_len, nb)) : nullptr;
+		if (any_linked && !d_tab)
+			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's sequence index");
+		uint32_t b_at = 0;
+		for (size_t k = lo; k < hi;) {
+			int kind = -1;
+			size_t q = k;
+			uint32_t b_end = b_at;
+			for (; q < hi; ++q) {
+				const uint32_t nbq = ix.taken(q) ? uint32_t(ix.walk[q].nblocks) : 0u;
+				const int kq = nbq ? int(ix.linked(q)) : -1;
+				if (kind >= 0 && kq >= 0 && kq != kind)
+					break;
+				kind = kind >= 0 ? kind : kq;
+				b_end += nbq;
+			}
+			const PassRun run{ b_at, b_end, uint32_t(k - lo), uint32_t(q - lo), kind == 1 };
+			decode_pass_run(d_in, in_len, m.d_desc, nb, d_tab, d_slots, m.d_st, m.d_rec, run, stream);
+			b_at = b_end;
+			k = q;
+		}
+	}
 	HIP_OK(launch_frames_plan(m.d_desc, m.d_st, nb, m.d_rec, nf, m.d_off, m.d_loc, m.d_part, stream));
 	HIP_OK(launch_compact(d_slots, m.d_desc, m.d_off, m.d_st, nb, dst, stream));
 	HIP_OK(launch_xxh32_spans(dst, m.d_rec, nf, hash_max, stream));
@@ -235,7 +270,7 @@ void run_device_pass(const Index& ix, size_t lo, size_t hi, uint32_t nb, uint64_
 		j.status = LZ4ADA_OK;
 		j.reason = LZ4ADA_DEVFRAME_OK;
 		++stats.frames_batched;
-		add_last_path(LZ4ADA_PATH_BATCH | LZ4ADA_PATH_INDEPENDENT);
+		add_last_path(LZ4ADA_PATH_BATCH | (ix.linked(k) ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT));
 	}
 	*base += rec[nf - 1].out_off + rec[nf - 1].out_len;
 }
@@ -255,15 +290,32 @@ int lz4ada_frame_walk_host(const uint8_t* frame, int64_t len, lz4ada_frame_info*
 	return frame_walk(frame, len, lone_blocks_disabled(), info, &sums, descs ? &e : nullptr);
 }
 
+int lz4ada_frame_walk_host_opt(const uint8_t* frame, int64_t len, uint32_t flags, lz4ada_frame_info* info,
+                               lz4ada_block_desc* descs, int64_t desc_cap)
+{
+	WalkSums sums;
+	WalkEmit e{};
+	e.descs = descs;
+	e.cap = desc_cap;
+	return frame_walk(frame, len, lone_blocks_disabled(), info, &sums, descs ? &e : nullptr,
+	                  (flags & LZ4ADA_FRAMES_LINKED) != 0, uint64_t(batch_linked_max()));
+}
+
 int lz4ada_frames_device_bound(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
                                int64_t* bound, void* stream)
+{
+	return lz4ada_frames_device_bound_opt(d_in, in_len, jobs, njobs, batch_env_flags(), bound, stream);
+}
+
+int lz4ada_frames_device_bound_opt(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs,
+                                   int64_t njobs, uint32_t flags, int64_t* bound, void* stream)
 {
 	*bound = 0;
 	batch_stats() = lz4ada_batch_stats{};
 	return guarded(nullptr, [&] {
 		Index ix;
-		index_jobs("lz4ada_frames_device_bound", d_in, in_len, jobs, njobs, static_cast<hipStream_t>(stream),
-		           ix);
+		index_jobs("lz4ada_frames_device_bound", d_in, in_len, jobs, njobs, flags,
+		           static_cast<hipStream_t>(stream), ix);
 		*bound = report_index(ix, jobs);
 	});
 }
@@ -271,13 +323,21 @@ int lz4ada_frames_device_bound(const void* d_in, int64_t in_len, lz4ada_device_f
 int lz4ada_decode_frames_device(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
                                 void* d_out, int64_t out_cap, int64_t* out_len, void* stream)
 {
+	return lz4ada_decode_frames_device_opt(d_in, in_len, jobs, njobs, batch_env_flags(), d_out, out_cap, out_len,
+	                                       stream);
+}
+
+int lz4ada_decode_frames_device_opt(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs,
+                                    int64_t njobs, uint32_t flags, void* d_out, int64_t out_cap,
+                                    int64_t* out_len, void* stream)
+{
 	*out_len = 0;
 	batch_stats() = lz4ada_batch_stats{};
 	set_last_path(0);
 	return guarded(nullptr, [&] {
 		hipStream_t s = static_cast<hipStream_t>(stream);
 		Index ix;
-		index_jobs("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, s, ix);
+		index_jobs("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, flags, s, ix);
 		const int64_t bound = report_index(ix, jobs);
 		if (out_cap < bound || (bound > 0 && !d_out)) {
 			*out_len = bound;
@@ -325,7 +385,7 @@ int lz4ada_frames_index_device_debug(const void* d_in, int64_t in_len, const lz4
 	return guarded(nullptr, [&] {
 		hipStream_t s = static_cast<hipStream_t>(stream);
 		Index ix;
-		index_jobs("lz4ada_frames_index_device_debug", d_in, in_len, jobs, njobs, s, ix);
+		index_jobs("lz4ada_frames_index_device_debug", d_in, in_len, jobs, njobs, batch_env_flags(), s, ix);
 		const size_t n = ix.order.size();
 		uint64_t nb = 0;
 		for (size_t k = 0; k < n; ++k) {

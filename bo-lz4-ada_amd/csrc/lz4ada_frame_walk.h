@@ -97,10 +97,16 @@ LZ4ADA_HD inline uint32_t walk_slot_cap(uint32_t in_len, bool stored, int64_t bm
 // would say (_OVER_BUDGET is the caller's: compare sums->slots).  *info is
 // filled as index_frame fills it whenever the result is not _NOT_INDEXED.
 // no_lone: LZ4ADA_NO_LONE is set (few_large_blocks then never applies).
+// take_linked (LZ4ADA_FRAMES_LINKED): a modern frame with
+// B.Indep clear is judged by the other rules too and is LZ4ADA_BATCH_OK when
+// it passes them and its slots sum to at most linked_max bytes (one wave walks
+// the whole frame), else LZ4ADA_BATCH_LINKED; info->independent stays 0, which
+// tells the engine the decoder the frame takes.  Off: today's verdicts.
 // Reads no byte outside [p, p + len); ends with the input, since every block
 // takes at least 4 bytes of it.
 LZ4ADA_HD inline int frame_walk(const uint8_t* p, int64_t len, bool no_lone, lz4ada_frame_info* info,
-                                WalkSums* sums, WalkEmit* emit)
+                                WalkSums* sums, WalkEmit* emit, bool take_linked = false,
+                                uint64_t linked_max = 0)
 {
 	memset(info, 0, sizeof *info);
 	sums->slots = sums->caps = 0;
@@ -216,11 +222,13 @@ LZ4ADA_HD inline int frame_walk(const uint8_t* p, int64_t len, bool no_lone, lz4
 	}
 	info->nblocks = nb;
 	info->frame_len = pos;
-	if (!info->independent)
+	if (!info->independent && !take_linked)
 		return LZ4ADA_BATCH_LINKED;
 	const bool lone = !no_lone && nb >= 1 && nb <= WALK_LONE_BLOCKS && sums->max_in >= WALK_LONE_MIN_IN &&
 	                  int64_t(sums->max_in) <= WALK_LONE_MAX_IN;
-	return big || lone ? LZ4ADA_BATCH_BIG_BLOCK : LZ4ADA_BATCH_OK;
+	if (big || lone)
+		return LZ4ADA_BATCH_BIG_BLOCK;
+	return !info->independent && sums->slots > linked_max ? LZ4ADA_BATCH_LINKED : LZ4ADA_BATCH_OK;
 }
 
 }  // namespace lz4ada

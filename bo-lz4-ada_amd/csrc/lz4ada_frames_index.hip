@@ -29,6 +29,7 @@ constexpr uint32_t SCAN_WG = 256;  // frames per round of the scan
 __global__ __launch_bounds__(WALK_WG) void k_frames_walk(const uint8_t* __restrict__ in,
                                                          const FrameSpan* __restrict__ span,
                                                          uint32_t nframes, bool no_lone, uint64_t budget,
+                                                         bool take_linked, uint64_t linked_max,
                                                          FrameWalkRec* __restrict__ walk)
 {
 	const uint32_t i = blockIdx.x * WALK_WG + threadIdx.x;
@@ -36,12 +37,14 @@ __global__ __launch_bounds__(WALK_WG) void k_frames_walk(const uint8_t* __restri
 		return;
 	lz4ada_frame_info info;
 	WalkSums sums;
-	int v = frame_walk(in + span[i].off, int64_t(span[i].len), no_lone, &info, &sums, nullptr);
+	int v = frame_walk(in + span[i].off, int64_t(span[i].len), no_lone, &info, &sums, nullptr, take_linked,
+	                   linked_max);
 	if (v == LZ4ADA_BATCH_OK && sums.slots > budget)
 		v = LZ4ADA_BATCH_OVER_BUDGET;
 	FrameWalkRec r;
 	r.verdict = v;
-	r.flags = (info.has_content_size ? FRAME_HAS_SIZE : 0u) | (info.content_checksum ? FRAME_HAS_CKSUM : 0u);
+	r.flags = (info.has_content_size ? FRAME_HAS_SIZE : 0u) | (info.content_checksum ? FRAME_HAS_CKSUM : 0u) |
+	          (info.format == LZ4ADA_FORMAT_MODERN && !info.independent ? FRAME_LINKED : 0u);
 	r.nblocks = uint64_t(info.nblocks);
 	r.slots = sums.slots;
 	r.caps = sums.caps;
@@ -83,7 +86,8 @@ __global__ __launch_bounds__(WALK_WG) void k_frames_fill(const uint8_t* __restri
                                                          const FrameWalkRec* __restrict__ walk,
                                                          const uint64_t* __restrict__ first,
                                                          const uint64_t* __restrict__ slot, uint32_t nframes,
-                                                         bool no_lone, lz4ada_block_desc* __restrict__ desc,
+                                                         bool no_lone, bool take_linked, uint64_t linked_max,
+                                                         lz4ada_block_desc* __restrict__ desc,
                                                          FrameRec* __restrict__ rec)
 {
 	const uint32_t i = blockIdx.x * WALK_WG + threadIdx.x;
@@ -113,7 +117,8 @@ __global__ __launch_bounds__(WALK_WG) void k_frames_fill(const uint8_t* __restri
 		e.out_base = slot[i];
 		e.out_limit = slot[i] + w.slots;
 		e.written = 0;
-		const int v = frame_walk(in + span[i].off, int64_t(span[i].len), no_lone, &info, &sums, &e);
+		const int v = frame_walk(in + span[i].off, int64_t(span[i].len), no_lone, &info, &sums, &e, take_linked,
+		                         linked_max);
 		if (v != LZ4ADA_BATCH_OK || e.written != int64_t(w.nblocks) || sums.slots != w.slots) {
 			// the input changed between the walks: the frame fails, and the
 			// decoders find nothing to do in what is left of its descriptors
@@ -133,12 +138,13 @@ __global__ __launch_bounds__(WALK_WG) void k_frames_fill(const uint8_t* __restri
 }
 
 hipError_t launch_frames_walk(const uint8_t* d_in, const FrameSpan* d_span, uint32_t nframes, bool no_lone,
-                              uint64_t budget, FrameWalkRec* d_walk, hipStream_t stream)
+                              uint64_t budget, bool take_linked, uint64_t linked_max, FrameWalkRec* d_walk,
+                              hipStream_t stream)
 {
 	if (nframes == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_frames_walk, dim3((nframes + WALK_WG - 1) / WALK_WG), dim3(WALK_WG), 0, stream,
-	                   d_in, d_span, nframes, no_lone, budget, d_walk);
+	                   d_in, d_span, nframes, no_lone, budget, take_linked, linked_max, d_walk);
 	return hipGetLastError();
 }
 
@@ -151,12 +157,14 @@ hipError_t launch_frames_scan(const FrameWalkRec* d_walk, uint32_t nframes, uint
 
 hipError_t launch_frames_fill(const uint8_t* d_in, const FrameSpan* d_span, const FrameWalkRec* d_walk,
                               const uint64_t* d_first, const uint64_t* d_slot, uint32_t nframes,
-                              bool no_lone, lz4ada_block_desc* d_desc, FrameRec* d_rec, hipStream_t stream)
+                              bool no_lone, bool take_linked, uint64_t linked_max, lz4ada_block_desc* d_desc,
+                              FrameRec* d_rec, hipStream_t stream)
 {
 	if (nframes == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_frames_fill, dim3((nframes + WALK_WG - 1) / WALK_WG), dim3(WALK_WG), 0, stream,
-	                   d_in, d_span, d_walk, d_first, d_slot, nframes, no_lone, d_desc, d_rec);
+	                   d_in, d_span, d_walk, d_first, d_slot, nframes, no_lone, take_linked, linked_max, d_desc,
+	                   d_rec);
 	return hipGetLastError();
 }
 

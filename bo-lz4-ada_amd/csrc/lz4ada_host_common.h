@@ -454,6 +454,27 @@ void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t*
 int64_t batch_budget();
 int64_t batch_hash_max();
 lz4ada_batch_stats& batch_stats();
+// Linked frames in a pass: the slot bytes up to which a linked
+// frame shares one (LZ4ADA_BATCH_LINKED_MAX), and the flags of the entries
+// that take none (LZ4ADA_BATCH_LINKED=1 -> LZ4ADA_FRAMES_LINKED), both read
+// per call.
+int64_t batch_linked_max();
+uint32_t batch_env_flags();
+// A maximal run of frames of one kind inside a pass: blocks [b0, b1) and
+// frames [f0, f1) of the pass's arrays.
+struct PassRun {
+	uint32_t b0, b1, f0, f1;
+	bool linked;
+};
+// The decode launches of one run, on stream, no synchronisation.  An
+// independent run: launch_decode_checked over its blocks.  A linked run: the
+// block checksums beside launch_index over its blocks, k_decode_idx_frames
+// over its frames, then the join.  d_tab: index_table_bytes(in_len, nb) bytes
+// (may be null when no run is linked); d_desc / d_st / d_rec: the pass's
+// arrays (nb blocks).
+void decode_pass_run(const uint8_t* d_in, uint64_t in_len, const lz4ada_block_desc* d_desc, uint32_t nb,
+                     uint8_t* d_tab, uint8_t* d_slots, lz4ada_block_status* d_st, const FrameRec* d_rec,
+                     const PassRun& run, hipStream_t stream);
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

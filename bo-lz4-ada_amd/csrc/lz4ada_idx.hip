@@ -25,6 +25,10 @@
 //    (a leader loop: the first pending item always runs, every other whose
 //    source is already final runs with it).
 //
+//  * k_decode_idx_frames (pass 2 of the linked frames of a many-frame pass,
+//    one wave per frame): the frame's blocks in order, each reading the
+//    earlier output as history.
+//
 // Blocks either pass declines (DS_RETRY: malformed data, a back-reference
 // before the block start, an oversize block) are redone by k_decode_pc,
 // which produces the exact statuses; so this pair never changes a result,
@@ -2585,6 +2589,78 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	decode_block(D, frame, frame_len, desc, blockIdx.x, tab_all, out, status, LINK_HIST, len, false, true);
 }
 
+// Many linked frames side by side (a many-frame pass): one wave
+// per frame of the pass.  Workgroup f takes the blocks [first, first + nblocks)
+// of frames[f] when the record carries FRAME_LINKED (any other frame is
+// another launch's) and runs pass 2 over them in order, as K_SERIAL does for
+// one frame: each block reads the earlier output as history while every block
+// so far is full and its slot continues the previous one; from the first
+// block that is declined, short or not contiguous on, the later blocks of the
+// frame get DS_RETRY and the ones before keep DS_OK.  Pass 1 is an ordinary
+// launch_index over the same descriptors, ahead of this kernel.
+//
+// Quirk D1 from the real round state: the wave knows every decoded length, so
+// it replays Output_Pos / Output_Pos_History as the host does for one linked
+// frame (lz4ada_bulk_linked.cpp: opos = 0 when >= 65536 at a block's start,
+// opos += len, oph = opos when >= 65536).  A block that pass 2 flagged
+// AUX_D1_RISK while oph is in [65536, 65542] gets DS_RETRY and ends the chain
+// (nothing is emulated here: D1E stays false); outside that state the flagged
+// match reads plain history.
+//
+// The range is clamped to the launch's nblocks, so no status and no slot
+// outside the frame's blocks is written whatever the record says, and every
+// loop ends with the range.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_frames(
+        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
+        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
+        lz4ada_block_status* __restrict__ status, const FrameRec* __restrict__ frames, uint32_t nframes)
+{
+	__shared__ DecLds D;
+	if (blockIdx.x >= nframes)
+		return;
+	const uint32_t flags = frames[blockIdx.x].flags;
+	if (!(flags & FRAME_LINKED))
+		return;
+	const uint32_t first = min(frames[blockIdx.x].first, nblocks);
+	const uint32_t bend = first + min(frames[blockIdx.x].nblocks, nblocks - first);
+	int64_t hist = 0, opos = 0, oph = 0;
+	uint32_t stop = bend;  // the first block left DS_RETRY
+	for (uint32_t b = first; b < bend; ++b) {
+		if (opos >= HISTORY_SIZE)
+			opos = 0;
+		const bool in_d1 = oph >= HISTORY_SIZE && oph <= HISTORY_SIZE + 6;
+		int32_t len;
+		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status, hist, len);
+		vm_wait();  // the next block reads this output as history
+		__syncthreads();
+		if (code != DS_OK) {
+			stop = b + 1;  // (its own status is non-zero already)
+			break;
+		}
+		if (in_d1) {
+			// the flag lane 0 has just stored (complete: vm_wait), read past
+			// the L1 line this wave filled when it read the status before
+			const int32_t aux = __builtin_amdgcn_readfirstlane(
+			    __hip_atomic_load(&status[b].aux, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+			if (aux & AUX_D1_RISK) {
+				stop = b;
+				break;
+			}
+		}
+		opos += len;
+		if (opos >= HISTORY_SIZE)
+			oph = opos;
+		if (b + 1 < bend && (uint32_t(len) != desc[b].out_cap ||
+		                     desc[b + 1].out_off != desc[b].out_off + uint64_t(len))) {
+			stop = b + 1;  // the next block's history would not be contiguous
+			break;
+		}
+		hist += len;
+	}
+	for (uint32_t r = stop + lane_id(); r < bend; r += 64)
+		status[r].code = DS_RETRY;
+}
+
 // ============================================================ pipelined pair
 // k_decode_pp2 (round 5): two waves per block that pipeline consecutive
 // batches instead of splitting each one (k_decode_idx2), for launches of at
@@ -3270,6 +3346,18 @@ hipError_t launch_decode_idx_tab(const uint8_t* d_frame, uint64_t frame_len,
 		hipLaunchKernelGGL(k, dim3(nblocks), dim3(mode == IdxMode::FUSED_PAIR ? 128 : 64), 0, stream, d_frame,
 		                   frame_len, d_desc, nblocks, tab, d_out, d_status);
 	}
+	return hipGetLastError();
+}
+
+hipError_t launch_decode_idx_frames(const uint8_t* d_frame, uint64_t frame_len,
+                                    const lz4ada_block_desc* d_desc, uint32_t nblocks, const uint8_t* d_tab,
+                                    uint8_t* d_out, lz4ada_block_status* d_status, const FrameRec* d_frames,
+                                    uint32_t nframes, hipStream_t stream)
+{
+	if (nframes == 0 || nblocks == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(idx::k_decode_idx_frames, dim3(nframes), dim3(64), 0, stream, d_frame, frame_len, d_desc,
+	                   nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, d_frames, nframes);
 	return hipGetLastError();
 }
 

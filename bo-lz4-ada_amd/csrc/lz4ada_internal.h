@@ -306,11 +306,12 @@ hipError_t launch_compact(const uint8_t* d_src, const lz4ada_block_desc* d_desc,
 // the block statuses, k_xxh32_spans fills hash.
 constexpr uint32_t FRAME_HAS_SIZE = 1u;   // content_size is declared
 constexpr uint32_t FRAME_HAS_CKSUM = 2u;  // C.Checksum
+constexpr uint32_t FRAME_LINKED = 4u;     // B.Indep clear: its blocks are k_decode_idx_frames' 
 constexpr int32_t FRAME_SIZE_BAD = 1;     // verdict: out_len != content_size
 constexpr int32_t FRAME_GPU_HASHED = 2;   // verdict: hash holds XXH32 of the frame's output
 struct FrameRec {
 	uint32_t first, nblocks;  // its blocks among the pass's
-	uint32_t flags;           // FRAME_HAS_*
+	uint32_t flags;           // FRAME_HAS_*, FRAME_LINKED
 	uint32_t hash;
 	uint64_t content_size;
 	uint64_t out_off, out_len;  // its bytes in the compacted output
@@ -341,6 +342,20 @@ hipError_t launch_frames_plan(const lz4ada_block_desc* d_desc, lz4ada_block_stat
 // four frames per wave.
 hipError_t launch_xxh32_spans(const uint8_t* d_buf, FrameRec* d_frames, uint32_t nframes,
                               uint64_t hash_max, hipStream_t stream);
+// The linked frames of a pass, one wave per frame (k_decode_idx_frames,
+// lz4ada_idx.hip): pass 2 over the blocks [first, first + nblocks) of every
+// record among d_frames[0 .. nframes) that carries FRAME_LINKED, in order,
+// each block reading the frame's earlier output as history; records without
+// the flag are left alone.  d_desc / d_status / nblocks are the arrays the
+// records' `first` counts in, and d_tab the table of a launch_index over
+// those blocks laid out for the same arrays (block b's records at
+// ((in_off >> 8) + b)).  A block that is declined, short, not contiguous or in
+// quirk D1's round state ends its frame's chain: it and the later blocks of
+// the frame get a non-zero code.
+hipError_t launch_decode_idx_frames(const uint8_t* d_frame, uint64_t frame_len,
+                                    const lz4ada_block_desc* d_desc, uint32_t nblocks, const uint8_t* d_tab,
+                                    uint8_t* d_out, lz4ada_block_status* d_status, const FrameRec* d_frames,
+                                    uint32_t nframes, hipStream_t stream);
 
 // ---- frames indexed on the device (lz4ada_frames_index.hip) ----
 // A job's bytes inside the device input: the frame and whatever follows it.
@@ -350,7 +365,7 @@ struct FrameSpan {
 // What k_frames_walk found out about one frame (frame_walk, lz4ada_frame_walk.h).
 struct FrameWalkRec {
 	int32_t verdict;  // LZ4ADA_BATCH_*; _OVER_BUDGET when its slots alone exceed the budget
-	uint32_t flags;   // FRAME_HAS_*
+	uint32_t flags;   // FRAME_HAS_*, FRAME_LINKED (a modern frame with B.Indep clear)
 	uint64_t nblocks;
 	uint64_t slots, caps;  // sum of round256(slot_cap), sum of slot_cap
 	int64_t frame_len;
@@ -359,9 +374,11 @@ struct FrameWalkRec {
 	int32_t format;  // LZ4ADA_FORMAT_*, 0 when the frame does not index
 };
 // One lane per frame: d_walk[i] from the frame at d_span[i].  Reads no byte
-// outside a frame's span.
+// outside a frame's span.  take_linked / linked_max: frame_walk's option
+// (linked frames of at most linked_max slot bytes are accepted).
 hipError_t launch_frames_walk(const uint8_t* d_in, const FrameSpan* d_span, uint32_t nframes, bool no_lone,
-                              uint64_t budget, FrameWalkRec* d_walk, hipStream_t stream);
+                              uint64_t budget, bool take_linked, uint64_t linked_max, FrameWalkRec* d_walk,
+                              hipStream_t stream);
 // One workgroup: d_first[i] / d_slot[i] get the blocks / slot bytes of the
 // accepted frames (verdict LZ4ADA_BATCH_OK) before frame i, entry nframes the
 // totals.  Frames that are not accepted count as nothing.
@@ -376,7 +393,7 @@ hipError_t launch_frames_scan(const FrameWalkRec* d_walk, uint32_t nframes, uint
 // between), the frame's remaining descriptors are empty and its fail is 0.
 hipError_t launch_frames_fill(const uint8_t* d_in, const FrameSpan* d_span, const FrameWalkRec* d_walk,
                               const uint64_t* d_first, const uint64_t* d_slot, uint32_t nframes,
-                              bool no_lone, lz4ada_block_desc* d_desc, FrameRec* d_rec,
-                              hipStream_t stream);
+                              bool no_lone, bool take_linked, uint64_t linked_max, lz4ada_block_desc* d_desc,
+                              FrameRec* d_rec, hipStream_t stream);
 
 }  // namespace lz4ada

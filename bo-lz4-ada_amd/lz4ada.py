@@ -202,6 +202,9 @@ BLOCK_HAS_CKSUM = 2
 FORMAT_MODERN, FORMAT_LEGACY, FORMAT_SKIPPABLE = 1, 2, 3
 # StreamEntry.batchable: why a frame does not take the many-frame pass
 BATCH_OK, BATCH_LINKED, BATCH_BIG_BLOCK, BATCH_OVER_BUDGET, BATCH_NOT_INDEXED = 0, 1, 2, 3, 4
+# flags of the many-frame calls (the `linked` keyword): linked frames up to
+# batch_linked_max() share the pass
+FRAMES_LINKED = 1
 
 _P = ctypes.POINTER
 _sig = {
@@ -219,6 +222,16 @@ _sig = {
     "lz4ada_frames_device_bound": ([_vp, _i64, _vp, _i64, _pi64, _vp], ctypes.c_int),
     "lz4ada_decode_frames_device": ([_vp, _i64, _vp, _i64, _vp, _i64, _pi64, _vp], ctypes.c_int),
     "lz4ada_frame_walk_host": ([_vp, _i64, ctypes.POINTER(FrameInfo), _vp, _i64], ctypes.c_int),
+    "lz4ada_decode_frames_opt": ([_vp, _i64, ctypes.c_uint32, ctypes.POINTER(_vp), _pi64], ctypes.c_int),
+    "lz4ada_stream_index_opt": ([_vp, _i64, ctypes.c_uint32, _vp, _i64, _pi64], ctypes.c_int),
+    "lz4ada_frames_device_bound_opt": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _pi64, _vp], ctypes.c_int),
+    "lz4ada_decode_frames_device_opt": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _vp, _i64, _pi64, _vp],
+                                        ctypes.c_int),
+    "lz4ada_frame_walk_host_opt": ([_vp, _i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo), _vp, _i64],
+                                   ctypes.c_int),
+    "lz4ada_batch_linked_max": ([], ctypes.c_int64),
+    "lz4ada_decode_idx_frames_debug": ([_vp, ctypes.c_uint64, _vp, _i64, _pi64, _vp, _i64, _vp, _vp, _vp],
+                                       ctypes.c_int),
     "lz4ada_frames_index_device_debug": ([_vp, _i64, _vp, _i64, ctypes.POINTER(ctypes.c_int32), _pi64,
                                           _vp, _i64, _vp], ctypes.c_int),
     "lz4ada_abi_version": ([], ctypes.c_int),
@@ -502,17 +515,28 @@ def decode_stream(data) -> bytes:
     return _take(p, olen.value)
 
 
-def stream_index(data):
+def _index(linked, plain, opt):
+    """The C entry for a `linked` keyword: the plain one (which takes
+    LZ4ADA_BATCH_LINKED from the environment) when it is False, else the
+    _opt one with FRAMES_LINKED bound in."""
+    if not linked:
+        return plain
+    return lambda *a: opt(*a[:2], FRAMES_LINKED, *a[2:])
+
+
+def stream_index(data, linked=False):
     """Host walk of every frame of a concatenated stream -> list of
     StreamEntry (offset, frame_len, info, batchable: a BATCH_* reason code).
     Raises the exception of the first frame that does not index or is cut
-    short; the frames before it are in the exception's `entries`."""
+    short; the frames before it are in the exception's `entries`.  linked:
+    linked frames up to batch_linked_max() are batchable."""
+    index = _index(linked, _lib.lz4ada_stream_index, _lib.lz4ada_stream_index_opt)
     n = _i64()
-    st = _lib.lz4ada_stream_index(_addr(data), len(data), None, 0, ctypes.byref(n))
+    st = index(_addr(data), len(data), None, 0, ctypes.byref(n))
     msg = _thread_error() if st else ""
     entries = (StreamEntry * max(n.value, 1))()
     m = _i64()
-    _lib.lz4ada_stream_index(_addr(data), len(data), entries, n.value, ctypes.byref(m))
+    index(_addr(data), len(data), entries, n.value, ctypes.byref(m))
     out = [entries[i] for i in range(n.value)]
     if st:
         exc = _ERRORS.get(st, LZ4AdaError)(msg)
@@ -521,27 +545,29 @@ def stream_index(data):
     return out
 
 
-def decode_frames_jobs(frames):
+def decode_frames_jobs(frames, linked=False):
     """lz4ada_decode_frames as it is -> (the output buffer as bytes, the
-    FrameJob array: out_off, out_len, consumed, status, path per frame)."""
+    FrameJob array: out_off, out_len, consumed, status, path per frame).
+    linked: lz4ada_decode_frames_opt with FRAMES_LINKED."""
     frames = [f if isinstance(f, bytes) else bytes(f) for f in frames]
     jobs = (FrameJob * max(len(frames), 1))()
     for j, f in zip(jobs, frames):
         j.frame = _addr(f)
         j.len = len(f)
     p, olen = _vp(), _i64()
-    _check(_lib.lz4ada_decode_frames(jobs, len(frames), ctypes.byref(p), ctypes.byref(olen)),
-           _thread_error())
+    decode = _index(linked, _lib.lz4ada_decode_frames, _lib.lz4ada_decode_frames_opt)
+    _check(decode(jobs, len(frames), ctypes.byref(p), ctypes.byref(olen)), _thread_error())
     return _take(p, olen.value), jobs
 
 
-def decode_frames(frames):
+def decode_frames(frames, linked=False):
     """Many independent frames (each with Single_Frame semantics) in as few
     device passes as the byte budget allows -> list of (decoded bytes, bytes
     consumed, exception or None), one per frame.  One bad frame does not
     cost the others: a failed frame holds what the reference had output
-    before raising, as decode_frame_partial gives it."""
-    out, jobs = decode_frames_jobs(frames)
+    before raising, as decode_frame_partial gives it.  linked: linked frames
+    up to batch_linked_max() share the passes too."""
+    out, jobs = decode_frames_jobs(frames, linked)
     res = []
     for i in range(len(frames)):
         j = jobs[i]
@@ -562,6 +588,12 @@ def batch_hash_max() -> int:
     """G: the decoded length up to which a pass hashes a frame's content
     checksum on the GPU (LZ4ADA_BATCH_HASH_MAX overrides the default)."""
     return int(_lib.lz4ada_batch_hash_max())
+
+
+def batch_linked_max() -> int:
+    """The slot bytes up to which a linked frame shares a pass
+    (LZ4ADA_BATCH_LINKED_MAX overrides the default)."""
+    return int(_lib.lz4ada_batch_linked_max())
 
 
 def xxh32_spans_device(d_buf: int, spans):
@@ -586,18 +618,25 @@ def _device_jobs(spans):
     return jobs
 
 
-def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0):
+def _device_entry(linked, plain, opt):
+    if not linked:
+        return plain
+    return lambda *a: opt(*a[:4], FRAMES_LINKED, *a[4:])
+
+
+def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0, linked=False):
     """Index the frames at spans [(in_off, in_len)] of the device buffer d_in
     (raw pointer) on the device -> (an out_cap that always suffices, the
     DeviceFrameJob array with the index's verdict per frame)."""
     jobs = _device_jobs(spans)
     bound = _i64()
-    _check(_lib.lz4ada_frames_device_bound(d_in, in_len, jobs, len(spans), ctypes.byref(bound),
-                                           stream), _thread_error())
+    call = _device_entry(linked, _lib.lz4ada_frames_device_bound, _lib.lz4ada_frames_device_bound_opt)
+    _check(call(d_in, in_len, jobs, len(spans), ctypes.byref(bound), stream), _thread_error())
     return bound.value, jobs
 
 
-def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0):
+def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0,
+                         linked=False):
     """Decode the frames at spans [(in_off, in_len)] of the device buffer d_in
     into the device buffer d_out (raw pointers) -> (bytes written, the
     DeviceFrameJob array: out_off, out_len, consumed, status, reason).  A
@@ -605,8 +644,8 @@ def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int
     reference's verdict.  TooLittleMemory carries the needed size as .bound."""
     jobs = _device_jobs(spans)
     n = _i64()
-    st = _lib.lz4ada_decode_frames_device(d_in, in_len, jobs, len(spans), d_out, out_cap,
-                                          ctypes.byref(n), stream)
+    call = _device_entry(linked, _lib.lz4ada_decode_frames_device, _lib.lz4ada_decode_frames_device_opt)
+    st = call(d_in, in_len, jobs, len(spans), d_out, out_cap, ctypes.byref(n), stream)
     if st:
         exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
         exc.bound = n.value
@@ -614,7 +653,7 @@ def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int
     return n.value, jobs
 
 
-def decode_frames_tensor(t, spans, out=None):
+def decode_frames_tensor(t, spans, out=None, linked=False):
     """decode_frames_device for a CUDA torch.uint8 tensor holding the frames,
     on torch's current stream -> (the decoded bytes as a uint8 tensor on the
     same device, the DeviceFrameJob array).  out: a uint8 tensor there to
@@ -626,13 +665,13 @@ def decode_frames_tensor(t, spans, out=None):
     with torch.cuda.device(t.device):
         stream = torch.cuda.current_stream().cuda_stream
         if out is None:
-            bound, _ = frames_device_bound(t.data_ptr(), t.numel(), spans, stream)
+            bound, _ = frames_device_bound(t.data_ptr(), t.numel(), spans, stream, linked)
             out = torch.empty(max(bound, 1), dtype=torch.uint8, device=t.device)
         elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8
                   and out.is_contiguous()):
             raise ValueError("out must be a contiguous CUDA uint8 tensor on the frames' device")
         n, jobs = decode_frames_device(t.data_ptr(), t.numel(), spans, out.data_ptr(), out.numel(),
-                                       stream)
+                                       stream, linked)
     return out[:n], jobs
 
 
@@ -649,16 +688,18 @@ def explain_frame(t_or_bytes, job):
     return decode_frame_partial(data)
 
 
-def frame_walk_host(data, offset: int = 0):
+def frame_walk_host(data, offset: int = 0, linked=False):
     """Test-only: the device index's frame walk run on the host ->
     (verdict: a BATCH_* reason, FrameInfo, ctypes array of BlockDesc as
-    frame_index lays them out)."""
+    frame_index lays them out).  linked: lz4ada_frame_walk_host_opt with
+    FRAMES_LINKED (plain flags otherwise: no environment switch here)."""
     n = len(data) - offset
     info = FrameInfo()
-    v = _lib.lz4ada_frame_walk_host(_addr(data, offset), n, ctypes.byref(info), None, 0)
+    walk = _index(linked, _lib.lz4ada_frame_walk_host, _lib.lz4ada_frame_walk_host_opt)
+    v = walk(_addr(data, offset), n, ctypes.byref(info), None, 0)
     descs = (BlockDesc * max(info.nblocks, 1))()
     info2 = FrameInfo()
-    v2 = _lib.lz4ada_frame_walk_host(_addr(data, offset), n, ctypes.byref(info2), descs, info.nblocks)
+    v2 = walk(_addr(data, offset), n, ctypes.byref(info2), descs, info.nblocks)
     assert v2 == v and bytes(info2) == bytes(info)
     return v, info, descs
 
@@ -819,6 +860,20 @@ def index_table_debug(d_frame, frame_len, d_descs, nblocks, d_status, stream=0, 
     _check(_lib.lz4ada_index_table_debug(d_frame, frame_len, d_descs, nblocks, buf, cap, d_status,
                                          stream, waves), _thread_error())
     return bytes(buf)
+
+
+def decode_idx_frames_debug(d_frame, frame_len, d_descs, nblocks, first, linked, d_out, d_status,
+                            stream=0):
+    """Test-only: k_index + k_decode_idx_frames alone.  first: nframes + 1
+    rising block indices (frame i holds blocks first[i] .. first[i + 1] - 1 of
+    d_descs); linked[i] true marks the frames to walk (one wave each, the
+    blocks in order with the earlier output as history); the others' statuses
+    and slots are left alone.  Returns after the stream has drained."""
+    nframes = len(first) - 1
+    f = (_i64 * (nframes + 1))(*first)
+    m = (ctypes.c_uint8 * max(nframes, 1))(*[1 if x else 0 for x in linked])
+    _check(_lib.lz4ada_decode_idx_frames_debug(d_frame, frame_len, d_descs, nblocks, f, m, nframes,
+                                               d_out, d_status, stream), _thread_error())
 
 
 def lone_scratch_bytes(n: int, cap: int) -> int:

@@ -446,6 +446,44 @@ int64_t lz4ada_batch_hash_max(void);
 int lz4ada_xxh32_spans_device(const void *d_buf, const int64_t *off, const int64_t *len,
                               int64_t nspans, uint32_t *hash, float *kernel_ms);
 
+/* ---------------------------------------------- linked frames in a pass */
+/*
+ * Linked blocks are the LZ4F default, so many small frames written by a
+ * library are linked frames.  With LZ4ADA_FRAMES_LINKED in `flags`, a modern
+ * frame with B.Indep clear shares the pass when it passes every other rule
+ * and its slots sum to at most lz4ada_batch_linked_max() bytes; one wave
+ * decodes its blocks in order (k_decode_idx_frames),
+ * N frames side by side.  A frame over the cap keeps LZ4ADA_BATCH_LINKED.
+ * info.independent stays 0.  A linked frame the pass does not find good in
+ * every respect (a block error, a block checksum, quirk D1 in its round
+ * state, a reference before the frame start, a short middle block) goes the
+ * single way as every other such frame: the reference's bytes and exception
+ * from the host calls, LZ4ADA_EXACT_PATH / LZ4ADA_DEVFRAME_BLOCK from the
+ * device call.  A committed linked frame reports LZ4ADA_PATH_BATCH |
+ * LZ4ADA_PATH_LINKED.  flags 0 is the call without _opt.  The calls without
+ * _opt, lz4ada_decode_stream / _alloc and the CLIs built on them take
+ * LZ4ADA_BATCH_LINKED=1 from the environment, read per call, as their flags.
+ */
+#define LZ4ADA_FRAMES_LINKED 1u /* flags: linked frames up to lz4ada_batch_linked_max() share the pass */
+int lz4ada_decode_frames_opt(lz4ada_frame_job *jobs, int64_t njobs, uint32_t flags, uint8_t **out,
+                             int64_t *out_len);
+int lz4ada_stream_index_opt(const uint8_t *input, int64_t len, uint32_t flags,
+                            lz4ada_stream_entry *entries, int64_t cap, int64_t *nframes);
+/* The slot bytes (sum of the block slots, each rounded up to 256) up to which
+ * a linked frame shares a pass: the built-in default, or
+ * LZ4ADA_BATCH_LINKED_MAX, read per call. */
+int64_t lz4ada_batch_linked_max(void);
+/* Test-only, like lz4ada_index_table_debug: k_index + k_decode_idx_frames alone
+ * over nframes block ranges first[0..nframes] (host array, nframes + 1 rising
+ * entries) of d_descs; linked[i] != 0 marks the frames to walk, and the blocks
+ * of the others see no launch.  d_status gets a code per block of a marked
+ * frame: 0 with out_len, or non-zero from the block that ended the frame's
+ * chain on.  Returns after the stream has drained. */
+int lz4ada_decode_idx_frames_debug(const void *d_frame, uint64_t frame_len,
+                                   const lz4ada_block_desc *d_descs, int64_t nblocks,
+                                   const int64_t *first, const uint8_t *linked, int64_t nframes,
+                                   void *d_out, lz4ada_block_status *d_status, void *stream);
+
 /* ------------------------- many frames, device memory to device memory */
 /*
  * The same pass for frames that already lie in device memory (read there by
@@ -504,6 +542,15 @@ int lz4ada_frames_device_bound(const void *d_in, int64_t in_len,
 int lz4ada_decode_frames_device(const void *d_in, int64_t in_len,
                                 lz4ada_device_frame_job *jobs, int64_t njobs,
                                 void *d_out, int64_t out_cap, int64_t *out_len, void *stream);
+/* The two calls with flags (LZ4ADA_FRAMES_LINKED, above): the walk then accepts
+ * linked frames up to lz4ada_batch_linked_max(); lz4ada_last_path() gains
+ * LZ4ADA_PATH_LINKED when a linked frame was committed. */
+int lz4ada_frames_device_bound_opt(const void *d_in, int64_t in_len,
+                                   lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
+                                   int64_t *bound, void *stream);
+int lz4ada_decode_frames_device_opt(const void *d_in, int64_t in_len,
+                                    lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
+                                    void *d_out, int64_t out_cap, int64_t *out_len, void *stream);
 
 /* Test-only, in the spirit of lz4ada_index_table_debug. */
 /* The walk on the host: verdict as return value (LZ4ADA_DEVFRAME_* 0..4), info
@@ -512,6 +559,10 @@ int lz4ada_decode_frames_device(const void *d_in, int64_t in_len,
  * unless the verdict is NOT_INDEXED.  Host only, no HIP call. */
 int lz4ada_frame_walk_host(const uint8_t *frame, int64_t len, lz4ada_frame_info *info,
                            lz4ada_block_desc *descs, int64_t desc_cap);
+/* The same with flags (LZ4ADA_FRAMES_LINKED and its cap); flags 0 is the call above. */
+int lz4ada_frame_walk_host_opt(const uint8_t *frame, int64_t len, uint32_t flags,
+                               lz4ada_frame_info *info, lz4ada_block_desc *descs,
+                               int64_t desc_cap);
 /* k_frames_walk + scan + k_frames_fill alone: per job the verdict and nblocks
  * (0 for a frame that does not index), and the descriptors of all accepted
  * frames in pass order (rising in_off), copied to the host: in_off absolute in
