@@ -1,49 +1,26 @@
 // lz4ada_bulk_frames.cpp -- many frames in one device pass:
 // the stream index (which frames a concatenated stream holds and which of
-// them can share a pass), the pass itself (one H2D of the frames, one
-// decode launch over every block of every frame, k_frames_plan's device
-// scan and per-frame verdicts, k_compact, k_xxh32_spans, one D2H of the
-// per-frame records and one of the bytes), and the entries built on it:
+// them can share a pass), the pass itself (one H2D of the frames, the device
+// half that lz4ada_frames_pass.cpp states for this engine and the
+// device-to-device one, one D2H of the bytes), and the entries built on it:
 // lz4ada_stream_index, lz4ada_decode_frames and the routing of
 // lz4ada_decode_stream / _alloc.  A frame the pass does not find good in
 // every respect is decoded again by decode_one_frame (lz4ada_bulk.cpp), so
 // every error text is the reference's; this unit invents none for a decode.
 // With LZ4ADA_FRAMES_LINKED, linked frames up to lz4ada_batch_linked_max()
-// share the pass: the frames of a pass are cut into runs of
-// one kind, an independent run decoded as before and a linked run by one wave
-// per frame (k_decode_idx_frames).
+// share the pass.
+#include "lz4ada_frame_walk.h"
 #include "lz4ada_host_common.h"
 
 using namespace lz4ada;
 
 namespace lz4ada {
-
-int64_t batch_budget() { return env_bytes("LZ4ADA_BATCH_BYTES", int64_t(4) << 30); }
-
 namespace {
 
-// The bulk decoders take blocks whose slot is at most this (MAX_RUN,
-// lz4ada_idx.hip); a legacy frame may declare more.
-constexpr int64_t BATCH_SLOT_MAX = int64_t(4) << 20;
-// G: a frame's content checksum is hashed by k_xxh32_spans when the frame
-// decodes to at most this many bytes, else by the host chain while its
-// bytes are copied out.  Measured (profiles/frames_batch_xxh.txt, DESIGN.md
-// §10): with 64 spans side by side the kernel is faster than one host core
-// at every size from 4 KiB to 16 MiB, the largest size measured.
-constexpr int64_t BATCH_HASH_MAX = int64_t(16) << 20;
 // lz4ada_decode_stream takes the pass when the stream holds at least this
 // many batchable frames with blocks (profiles/frames_batch_ab.txt).
 constexpr int64_t BATCH_MIN_FRAMES = 2;
-// A linked frame shares a pass (LZ4ADA_FRAMES_LINKED) when its slots sum to
-// at most this: one wave walks the whole frame, so past some size the frame
-// is faster on its own, every block at once (lz4ada_bulk_linked.cpp).
-// Measured (profiles/frames_linked_ab.txt): a pass of 2 frames
-// of 32 x 64 KiB is still 1.17x faster than the two on their own (7.9 against
-// 9.3 ms), one of 2 frames of 64 x 64 KiB is 1.46x slower (15.5 against
-// 10.6 ms); sizes in between were not measured.
-constexpr int64_t BATCH_LINKED_MAX = int64_t(2) << 20;
 
-thread_local lz4ada_batch_stats g_stats{};
 thread_local std::vector<std::string> g_job_errors;
 
 struct Frame {
@@ -91,7 +68,7 @@ void classify(Frame& fr, uint64_t budget, Error* why, uint32_t flags, uint64_t l
 	fr.slots = fr.caps = 0;
 	for (const auto& d : fr.descs) {
 		const uint32_t cap = slot_cap(d, fr.info.block_max);
-		if (cap > BATCH_SLOT_MAX)
+		if (cap > WALK_SLOT_MAX)
 			fr.reason = LZ4ADA_BATCH_BIG_BLOCK;
 		fr.slots += round256(cap);
 		fr.caps += cap;
@@ -124,7 +101,7 @@ void committed_now(const Report& rp, const Sink& out)
 // Frame i was committed from a pass: its n bytes lie at `off` of the output.
 void report_batched(const Report& rp, const Frame& fr, size_t i, int64_t off, int64_t n)
 {
-	++g_stats.frames_batched;
+	++batch_stats().frames_batched;
 	const int bits = LZ4ADA_PATH_BATCH |
 	                 (fr.skippable() ? 0 : fr.linked() ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT);
 	add_last_path(bits);
@@ -141,7 +118,7 @@ void report_batched(const Report& rp, const Frame& fr, size_t i, int64_t off, in
 // Frame i on its own, by today's path: the reference's output or exception.
 void decode_single(const Report& rp, const Frame& fr, size_t i, Sink& out)
 {
-	++g_stats.frames_single;
+	++batch_stats().frames_single;
 	int64_t c = 0;
 	if (!rp.jobs) {
 		decode_one_frame(fr.p, fr.len, out, c);
@@ -181,15 +158,14 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
               const Report& rp, uint64_t hash_max)
 {
 	device_check_or_raise();
-	const uint32_t nf = uint32_t(hi - lo);
-	uint64_t nb64 = 0, slots = 0, caps = 0, packed = 0;
+	std::vector<PassFrame> frames;
+	uint64_t slots = 0, caps = 0, packed = 0;
 	for (size_t k = lo; k < hi; ++k) {
-		nb64 += fs[k].descs.size();
+		frames.push_back(PassFrame{ uint32_t(fs[k].descs.size()), fs[k].linked() });
 		slots += fs[k].slots;
 		caps += fs[k].caps;
 		packed += uint64_t(fs[k].info.frame_len);
 	}
-	const uint32_t nb = uint32_t(nb64);
 
 	// Stage: a stream's frames are already back to back, so their covering
 	// range is copied as it is; a job array's frames are packed into pinned
@@ -209,42 +185,21 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
 		src = pack.p;
 	}
 
-	// device: descriptors | frame records | statuses | dst_off | loc | part
-	const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), rec_b = size_t(nf) * sizeof(FrameRec);
-	const size_t st_b = size_t(nb) * sizeof(lz4ada_block_status), off_b = (size_t(nb) + 1) * 8;
-	const size_t loc_b = size_t(nb) * 8, part_b = (size_t(plan_tiles(nb)) + 1) * 8;
+	// every reservation before the first copy is queued
 	uint8_t* const d_in = scratch(SC_FRAME, size_t(stage_len));
-	uint8_t* const d_slots = scratch(SC_OUT, size_t(std::max<uint64_t>(slots, 1)));
 	uint8_t* const d_cmp = scratch(SC_BATCH, size_t(std::max<uint64_t>(caps, 1)));
-	uint8_t* const d_meta = scratch(SC_BATCH_META, desc_b + rec_b + st_b + off_b + loc_b + part_b);
-	if (!d_in || !d_slots || !d_cmp || !d_meta)
+	PassArrays a;
+	if (!d_in || !d_cmp || a.reserve(frames, slots, stage_len))
 		return false;
-	// the linked runs' sequence index, laid out as one launch_index over the
-	// whole pass would lay it out
-	bool any_linked = false;
-	for (size_t k = lo; k < hi; ++k)
-		any_linked = any_linked || (fs[k].linked() && !fs[k].descs.empty());
-	uint8_t* const d_tab = any_linked ? scratch(SC_TAB, index_table_bytes(stage_len, nb)) : nullptr;
-	if (any_linked && !d_tab)
-		return false;
-	auto* const d_desc = reinterpret_cast<lz4ada_block_desc*>(d_meta);
-	auto* const d_rec = reinterpret_cast<FrameRec*>(d_meta + desc_b);
-	auto* const d_st = reinterpret_cast<lz4ada_block_status*>(d_meta + desc_b + rec_b);
-	auto* const d_off = reinterpret_cast<uint64_t*>(d_meta + desc_b + rec_b + st_b);
-	auto* const d_loc = reinterpret_cast<uint64_t*>(d_meta + desc_b + rec_b + st_b + off_b);
-	auto* const d_part = reinterpret_cast<uint64_t*>(d_meta + desc_b + rec_b + st_b + off_b + loc_b);
 
-	// Descriptors rebased to the staged base, in frame order and block order:
-	// in_off is strictly increasing over the whole pass and stage_len covers
-	// the whole staged range.  The index decoder relies on both: its table
-	// keeps block b's records at ((in_off >> 8) + b) and is sized from the
-	// frame length it is given (lz4ada_idx.hip, index_table_bytes), so blocks
-	// out of order or a shorter length would make two blocks' records overlap
-	// or leave the table.  Slots as bulk_independent lays them out.
+	// Descriptors rebased to the staged base, in frame and block order, and
+	// stage_len covers the staged range, as decode_pass asks; slots as
+	// bulk_independent lays them out.  The records stay in a pinned buffer of
+	// this pass: decode_single runs between the reads of them.
 	PinBuf hmeta;
-	hmeta.reserve(desc_b + rec_b);
+	hmeta.reserve(a.desc_b + a.rec_b);
 	auto* const h_desc = reinterpret_cast<lz4ada_block_desc*>(hmeta.p);
-	auto* const h_rec = reinterpret_cast<FrameRec*>(hmeta.p + desc_b);
+	auto* const h_rec = reinterpret_cast<FrameRec*>(hmeta.p + a.desc_b);
 	uint32_t b = 0;
 	uint64_t slot_at = 0, in_at = 0;
 	for (size_t k = lo; k < hi; ++k) {
@@ -271,63 +226,32 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
 
 	hipStream_t stream = nullptr;
 	HIP_OK(hipMemcpyAsync(d_in, src, size_t(stage_len), hipMemcpyHostToDevice, stream));
-	HIP_OK(hipMemcpyAsync(d_meta, hmeta.p, desc_b + rec_b, hipMemcpyHostToDevice, stream));
-	if (nb)
-		HIP_OK(hipMemsetAsync(d_st, 0, st_b, stream));
-	// the decode step: each maximal run of frames of one kind is one launch set
-	// over its sub-range of the descriptors (a pass of one kind: one set)
-	// (a frame without blocks rides in whichever run it falls into)
-	for (size_t k = lo; k < hi;) {
-		int kind = -1;
-		size_t m = k;
-		for (; m < hi; ++m) {
-			const int km = fs[m].descs.empty() ? -1 : int(fs[m].linked());
-			if (kind >= 0 && km >= 0 && km != kind)
-				break;
-			kind = kind >= 0 ? kind : km;
-		}
-		const PassRun run{ h_rec[k - lo].first, m < hi ? h_rec[m - lo].first : nb, uint32_t(k - lo),
-			           uint32_t(m - lo), kind == 1 };
-		decode_pass_run(d_in, stage_len, d_desc, nb, d_tab, d_slots, d_st, d_rec, run, stream);
-		k = m;
-	}
-	HIP_OK(launch_frames_plan(d_desc, d_st, nb, d_rec, nf, d_off, d_loc, d_part, stream));
-	HIP_OK(launch_compact(d_slots, d_desc, d_off, d_st, nb, d_cmp, stream));
-	HIP_OK(launch_xxh32_spans(d_cmp, d_rec, nf, hash_max, stream));
-	// the pass's one host synchronisation: the per-frame records
-	HIP_OK(hipMemcpyAsync(h_rec, d_rec, rec_b, hipMemcpyDeviceToHost, stream));
-	HIP_OK(hipStreamSynchronize(stream));
-	++g_stats.passes;
+	HIP_OK(hipMemcpyAsync(a.d_desc, hmeta.p, a.desc_b + a.rec_b, hipMemcpyHostToDevice, stream));
+	decode_pass(a, d_in, stage_len, d_cmp, hash_max, h_rec, stream);
 
 	const auto rec = [&](size_t k) -> const FrameRec& { return h_rec[k - lo]; };
-	// good as far as the device can tell: every block, the content size and
-	// (when it was hashed there) the content checksum
-	const auto device_good = [&](size_t k) {
-		const FrameRec& r = rec(k);
-		if (r.fail >= 0 || (r.verdict & FRAME_SIZE_BAD))
-			return false;
-		return !(r.verdict & FRAME_GPU_HASHED) || r.hash == fs[k].info.content_checksum_declared;
-	};
-	const auto host_hashed = [&](size_t k) {
-		return (rec(k).flags & FRAME_HAS_CKSUM) && !(rec(k).verdict & FRAME_GPU_HASHED);
-	};
-	for (size_t k = lo; k < hi; ++k)
-		g_stats.gpu_hashed += (rec(k).verdict & FRAME_GPU_HASHED) ? 1 : 0;
-
+	std::vector<FrameVerdict> verdict(frames.size());
+	for (size_t k = lo; k < hi; ++k) {
+		bool hashed = false;
+		verdict[k - lo] = frame_verdict(rec(k), fs[k].info.content_checksum_declared, &hashed);
+		batch_stats().gpu_hashed += hashed ? 1 : 0;
+	}
 	size_t k = lo;
 	while (k < hi) {
-		if (!device_good(k)) {
+		// good as far as the device can tell: every block, the content size and
+		// (when it was hashed there) the content checksum
+		if (verdict[k - lo] != FV_GOOD && verdict[k - lo] != FV_HOST_HASH) {
 			decode_single(rp, fs[k], k, out);
 			++k;
 			continue;
 		}
-		if (host_hashed(k)) {  // over hash_max: the host chain while its bytes are copied out
+		if (verdict[k - lo] == FV_HOST_HASH) {  // over hash_max: hashed while its bytes are copied out
 			const FrameRec& r = rec(k);
 			uint8_t* dst = out.room(int64_t(r.out_len));
 			lz4ada_xxh32_state hs;
 			lz4ada_xxh32_reset(&hs, 0);
 			content_xxh32_d2h(hs, d_cmp + r.out_off, int64_t(r.out_len), dst, stream);
-			++g_stats.host_hashed;
+			++batch_stats().host_hashed;
 			if (host_xxh32_final(hs) != fs[k].info.content_checksum_declared) {
 				decode_single(rp, fs[k], k, out);  // over the bytes just copied: none was committed
 			} else {
@@ -340,7 +264,7 @@ bool run_pass(const std::vector<Frame>& fs, size_t lo, size_t hi, bool contiguou
 		}
 		// a run of good frames: adjacent in the compacted output, one D2H
 		size_t m = k;
-		while (m < hi && device_good(m) && !host_hashed(m))
+		while (m < hi && verdict[m - lo] == FV_GOOD)
 			++m;
 		const uint64_t off0 = rec(k).out_off;
 		const uint64_t total = rec(m - 1).out_off + rec(m - 1).out_len - off0;
@@ -391,39 +315,9 @@ void run_frames(const std::vector<Frame>& fs, bool contiguous, Sink& out, const 
 
 }  // namespace
 
-int64_t batch_hash_max() { return env_bytes("LZ4ADA_BATCH_HASH_MAX", BATCH_HASH_MAX); }
-int64_t batch_linked_max() { return env_bytes("LZ4ADA_BATCH_LINKED_MAX", BATCH_LINKED_MAX); }
-uint32_t batch_env_flags()
-{
-	const char* e = getenv("LZ4ADA_BATCH_LINKED");
-	return e && *e && *e != '0' ? LZ4ADA_FRAMES_LINKED : 0u;
-}
-
-void decode_pass_run(const uint8_t* d_in, uint64_t in_len, const lz4ada_block_desc* d_desc, uint32_t nb,
-                     uint8_t* d_tab, uint8_t* d_slots, lz4ada_block_status* d_st, const FrameRec* d_rec,
-                     const PassRun& run, hipStream_t stream)
-{
-	const uint32_t n = run.b1 - run.b0;
-	if (n == 0)
-		return;
-	if (!run.linked) {
-		HIP_OK(launch_decode_checked(d_in, in_len, d_desc + run.b0, n, d_slots, d_st + run.b0, stream));
-		return;
-	}
-	// pass 1 over the run's blocks (the table's records land where block
-	// b0 + i of the whole pass has them), the block checksums beside it, then
-	// one wave per frame
-	HIP_OK(launch_block_checksums_beside(d_in, d_desc + run.b0, n, d_st + run.b0, stream));
-	HIP_OK(launch_index(d_in, in_len, d_desc + run.b0, n, d_tab + size_t(run.b0) * 64, d_st + run.b0, stream));
-	HIP_OK(launch_decode_idx_frames(d_in, in_len, d_desc, nb, d_tab, d_slots, d_st, d_rec + run.f0,
-	                                run.f1 - run.f0, stream));
-	HIP_OK(join_block_checksums(stream));
-}
-lz4ada_batch_stats& batch_stats() { return g_stats; }
-
 void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t* committed)
 {
-	g_stats = lz4ada_batch_stats{};
+	batch_stats() = lz4ada_batch_stats{};
 	Report rp;
 	rp.committed = committed;
 	std::vector<Frame> fs;
@@ -463,7 +357,7 @@ void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t*
 	while (pos < len) {
 		int64_t c = 0;
 		partial_frame_check(len - pos);
-		++g_stats.frames_single;
+		++batch_stats().frames_single;
 		decode_one_frame(input + pos, len - pos, out, c);
 		committed_now(rp, out);
 		if (c <= 0)
@@ -523,7 +417,7 @@ int lz4ada_decode_frames_opt(lz4ada_frame_job* jobs, int64_t njobs, uint32_t fla
 {
 	*out = nullptr;
 	*out_len = 0;
-	g_stats = lz4ada_batch_stats{};
+	batch_stats() = lz4ada_batch_stats{};
 	g_job_errors.clear();
 	set_last_path(0);
 	Sink s;
@@ -562,7 +456,7 @@ const char* lz4ada_frames_error(int64_t i)
 	return i >= 0 && size_t(i) < g_job_errors.size() ? g_job_errors[size_t(i)].c_str() : "";
 }
 
-void lz4ada_last_batch_stats(lz4ada_batch_stats* out) { *out = g_stats; }
+void lz4ada_last_batch_stats(lz4ada_batch_stats* out) { *out = batch_stats(); }
 
 int64_t lz4ada_batch_hash_max(void) { return batch_hash_max(); }
 int64_t lz4ada_batch_linked_max(void) { return batch_linked_max(); }
@@ -587,6 +481,7 @@ int lz4ada_decode_idx_frames_debug(const void* d_frame, uint64_t frame_len, cons
 		hipStream_t s = static_cast<hipStream_t>(stream);
 		const auto* const in = static_cast<const uint8_t*>(d_frame);
 		std::vector<FrameRec> recs(static_cast<size_t>(nframes));
+		std::vector<PassFrame> frames;
 		for (int64_t i = 0; i < nframes; ++i) {
 			FrameRec& r = recs[size_t(i)];
 			r = FrameRec{};
@@ -594,21 +489,17 @@ int lz4ada_decode_idx_frames_debug(const void* d_frame, uint64_t frame_len, cons
 			r.nblocks = uint32_t(first[i + 1] - first[i]);
 			r.flags = linked[i] ? FRAME_LINKED : 0u;
 			r.fail = -1;
+			frames.push_back(PassFrame{ r.nblocks, linked[i] != 0 });
 		}
 		DevBuf<FrameRec> d_rec;
 		d_rec.reserve(recs.size());
 		DevBuf<uint8_t> tab;
 		tab.reserve(index_table_bytes(frame_len, uint32_t(nblocks)));
 		vec_h2d(d_rec, recs, s);
-		for (int64_t i = 0; i < nframes;) {  // pass 1 per run of marked frames
-			int64_t m = i;
-			while (m < nframes && (linked[m] != 0) == (linked[i] != 0))
-				++m;
-			if (linked[i] && first[m] > first[i])
-				HIP_OK(launch_index(in, frame_len, d_descs + first[i], uint32_t(first[m] - first[i]),
-				                    tab.p + size_t(first[i]) * 64, d_status + first[i], s));
-			i = m;
-		}
+		for (const PassRun& r : pass_runs(frames))  // pass 1 per run of marked frames
+			if (r.linked)
+				HIP_OK(launch_index(in, frame_len, d_descs + first[r.f0], r.b1 - r.b0,
+				                    tab.p + size_t(first[r.f0]) * 64, d_status + first[r.f0], s));
 		HIP_OK(launch_decode_idx_frames(in, frame_len, d_descs, uint32_t(nblocks), tab.p,
 		                                static_cast<uint8_t*>(d_out), d_status, d_rec.p, uint32_t(nframes), s));
 		HIP_OK(hipStreamSynchronize(s));

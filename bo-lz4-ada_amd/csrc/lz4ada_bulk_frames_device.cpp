@@ -1,20 +1,18 @@
 // lz4ada_bulk_frames_device.cpp -- many frames that already lie in device
-// memory, decoded into device memory.  The pass is the one of
-// lz4ada_bulk_frames.cpp (one decode launch over every block of every frame,
-// k_frames_plan, k_compact, k_xxh32_spans); what differs is where its index
-// comes from and where its bytes go: the frames are indexed where they lie by
-// k_frames_walk / k_frames_scan / k_frames_fill (lz4ada_frames_index.hip), the
-// decoders read the caller's d_in itself, and the compaction writes into the
-// caller's d_out.  The host sees the per-frame walk records (one D2H per
-// call: verdicts and sizes, from which it sizes the scratch and splits the
-// passes by the byte budget) and the per-frame pass records (one D2H per
-// pass); no payload byte crosses, except that a content checksum over more
-// than lz4ada_batch_hash_max() bytes is hashed by the host chain
-// (content_xxh32_d2h with no host destination).  A frame the pass does not
-// find good in every respect gets LZ4ADA_EXACT_PATH and a reason; this unit
-// invents no exception text.  With LZ4ADA_FRAMES_LINKED the walk accepts
-// linked frames up to lz4ada_batch_linked_max() and the pass decodes them one
-// wave per frame, in runs by kind as the host engine does.
+// memory, decoded into device memory.  The device half of the
+// pass is the host engine's too (decode_pass, lz4ada_frames_pass.cpp); what
+// differs is where its index comes from and where its bytes go: the frames are
+// indexed where they lie by k_frames_walk / k_frames_scan / k_frames_fill
+// (lz4ada_frames_index.hip), the decoders read the caller's d_in itself, and
+// the compaction writes into the caller's d_out.  The host sees the per-frame
+// walk records (one D2H per call: verdicts and sizes, from which it sizes the
+// scratch and splits the passes by the byte budget) and the per-frame pass
+// records (one D2H per pass); no payload byte crosses, except that a content
+// checksum over more than lz4ada_batch_hash_max() bytes is hashed by the host
+// chain (content_xxh32_d2h with no host destination).  A frame the pass does
+// not find good in every respect gets LZ4ADA_EXACT_PATH and a reason; this
+// unit invents no exception text.  With LZ4ADA_FRAMES_LINKED the walk accepts
+// linked frames up to lz4ada_batch_linked_max().
 #include "lz4ada_frame_walk.h"
 #include "lz4ada_host_common.h"
 
@@ -122,39 +120,24 @@ int64_t report_index(const Index& ix, lz4ada_device_frame_job* jobs)
 	return int64_t(bound);
 }
 
-// The pass's device arrays, in this thread's SC_BATCH_META scratch:
-// descriptors | frame records | statuses | dst_off | loc | part
-struct PassMeta {
-	size_t desc_b, rec_b, st_b, off_b, loc_b, part_b;
-	lz4ada_block_desc* d_desc = nullptr;
-	FrameRec* d_rec = nullptr;
-	lz4ada_block_status* d_st = nullptr;
-	uint64_t *d_off = nullptr, *d_loc = nullptr, *d_part = nullptr;
-	PassMeta(uint32_t nb, uint32_t nf)
-	    : desc_b(size_t(nb) * sizeof(lz4ada_block_desc)), rec_b(size_t(nf) * sizeof(FrameRec)),
-	      st_b(size_t(nb) * sizeof(lz4ada_block_status)), off_b((size_t(nb) + 1) * 8), loc_b(size_t(nb) * 8),
-	      part_b((size_t(plan_tiles(nb)) + 1) * 8)
-	{
-		uint8_t* const d = scratch(SC_BATCH_META, desc_b + rec_b + st_b + off_b + loc_b + part_b);
-		if (!d)
-			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's block arrays");
-		d_desc = reinterpret_cast<lz4ada_block_desc*>(d);
-		d_rec = reinterpret_cast<FrameRec*>(d + desc_b);
-		d_st = reinterpret_cast<lz4ada_block_status*>(d + desc_b + rec_b);
-		d_off = reinterpret_cast<uint64_t*>(d + desc_b + rec_b + st_b);
-		d_loc = reinterpret_cast<uint64_t*>(d + desc_b + rec_b + st_b + off_b);
-		d_part = reinterpret_cast<uint64_t*>(d + desc_b + rec_b + st_b + off_b + loc_b);
-	}
-};
+// Room on the device for a pass over the sorted jobs [lo, hi), their blocks as
+// k_frames_scan counts them: a frame the index did not take rides without any.
+void reserve_pass(PassArrays& a, const Index& ix, size_t lo, size_t hi, uint64_t slots, uint64_t in_len)
+{
+	std::vector<PassFrame> frames;
+	for (size_t k = lo; k < hi; ++k)
+		frames.push_back(PassFrame{ ix.taken(k) ? uint32_t(ix.walk[k].nblocks) : 0u, ix.linked(k) });
+	if (const char* what = a.reserve(frames, slots, in_len))
+		raise(LZ4ADA_DEVICE_ERROR, std::string("no device memory for the pass's ") + what);
+}
 
 // The scan and the fill over the sorted jobs [lo, hi): descriptors and frame
 // records of a pass, on the device.
-void fill_pass(const Index& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassMeta& m,
+void fill_pass(const Index& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassArrays& m,
                hipStream_t stream)
 {
-	const uint32_t nf = uint32_t(hi - lo);
-	HIP_OK(launch_frames_scan(ix.d_walk + lo, nf, ix.d_first, ix.d_slot, stream));
-	HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, ix.d_walk + lo, ix.d_first, ix.d_slot, nf,
+	HIP_OK(launch_frames_scan(ix.d_walk + lo, m.nf, ix.d_first, ix.d_slot, stream));
+	HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, ix.d_walk + lo, ix.d_first, ix.d_slot, m.nf,
 	                          lone_blocks_disabled(), ix.take_linked, ix.linked_max, m.d_desc, m.d_rec, stream));
 }
 
@@ -173,65 +156,22 @@ void job_skipped(lz4ada_device_frame_job& j, const FrameWalkRec& w, uint64_t at)
 	add_last_path(LZ4ADA_PATH_BATCH);
 }
 
-// One pass over the sorted jobs [lo, hi) (nb blocks, `slots` slot bytes; the
-// frames the index did not take ride along as frames without blocks): their
-// bytes go to d_out from *base on, which then moves past them.
-void run_device_pass(const Index& ix, size_t lo, size_t hi, uint32_t nb, uint64_t slots, const uint8_t* d_in,
-                     uint64_t in_len, lz4ada_device_frame_job* jobs, uint8_t* d_out, uint64_t* base,
-                     uint64_t hash_max, hipStream_t stream)
+// One pass over the sorted jobs [lo, hi) (`slots` slot bytes): their bytes go
+// to d_out from *base on, which then moves past them.  The jobs are sorted and
+// their frames disjoint, and in_len covers every block, as decode_pass asks.
+void run_device_pass(const Index& ix, size_t lo, size_t hi, uint64_t slots, const uint8_t* d_in, uint64_t in_len,
+                     lz4ada_device_frame_job* jobs, uint8_t* d_out, uint64_t* base, uint64_t hash_max,
+                     hipStream_t stream)
 {
-	const uint32_t nf = uint32_t(hi - lo);
-	const PassMeta m(nb, nf);
-	uint8_t* const d_slots = scratch(SC_OUT, size_t(std::max<uint64_t>(slots, 1)));
-	if (!d_slots)
-		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's slots");
+	PassArrays m;
+	reserve_pass(m, ix, lo, hi, slots, in_len);
 	uint8_t* const dst = d_out + *base;
 	fill_pass(ix, lo, hi, d_in, m, stream);
-	if (nb)
-		HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
-	// in_off rises strictly over the pass (the jobs are sorted and their frames
-	// disjoint) and in_len covers every block: what the index decoder's table
-	// relies on (lz4ada_bulk_frames.cpp, run_pass)
-	// the decode step in runs of one kind (lz4ada_bulk_frames.cpp, run_pass);
-	// the frames' first blocks as k_frames_scan counts them: the accepted
-	// frames' block counts, in order
-	{
-		bool any_linked = false;
-		for (size_t k = lo; k < hi; ++k)
-			any_linked = any_linked || (ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks);
-		uint8_t* const d_tab = any_linked ? scratch(SC_TAB, index_table_bytes(in_len, nb)) : nullptr;
-		if (any_linked && !d_tab)
-			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's sequence index");
-		uint32_t b_at = 0;
-		for (size_t k = lo; k < hi;) {
-			int kind = -1;
-			size_t q = k;
-			uint32_t b_end = b_at;
-			for (; q < hi; ++q) {
-				const uint32_t nbq = ix.taken(q) ? uint32_t(ix.walk[q].nblocks) : 0u;
-				const int kq = nbq ? int(ix.linked(q)) : -1;
-				if (kind >= 0 && kq >= 0 && kq != kind)
-					break;
-				kind = kind >= 0 ? kind : kq;
-				b_end += nbq;
-			}
-			const PassRun run{ b_at, b_end, uint32_t(k - lo), uint32_t(q - lo), kind == 1 };
-			decode_pass_run(d_in, in_len, m.d_desc, nb, d_tab, d_slots, m.d_st, m.d_rec, run, stream);
-			b_at = b_end;
-			k = q;
-		}
-	}
-	HIP_OK(launch_frames_plan(m.d_desc, m.d_st, nb, m.d_rec, nf, m.d_off, m.d_loc, m.d_part, stream));
-	HIP_OK(launch_compact(d_slots, m.d_desc, m.d_off, m.d_st, nb, dst, stream));
-	HIP_OK(launch_xxh32_spans(dst, m.d_rec, nf, hash_max, stream));
 	PinBuf& h = scratch_cache().pin;  // this thread's small pinned transfers
 	h.reserve(m.rec_b);
-	// the pass's host synchronisation: the per-frame records
-	HIP_OK(hipMemcpyAsync(h.p, m.d_rec, m.rec_b, hipMemcpyDeviceToHost, stream));
-	HIP_OK(hipStreamSynchronize(stream));
-	const FrameRec* const rec = reinterpret_cast<const FrameRec*>(h.p);
+	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p);
+	decode_pass(m, d_in, in_len, dst, hash_max, rec, stream);
 	lz4ada_batch_stats& stats = batch_stats();
-	++stats.passes;
 	for (size_t k = lo; k < hi; ++k) {
 		if (!ix.taken(k))
 			continue;
@@ -241,16 +181,11 @@ void run_device_pass(const Index& ix, size_t lo, size_t hi, uint32_t nb, uint64_
 			job_skipped(j, ix.walk[k], *base + r.out_off);
 			continue;
 		}
-		int reason = LZ4ADA_DEVFRAME_OK;
-		if (r.fail >= 0) {
-			reason = LZ4ADA_DEVFRAME_BLOCK;
-		} else if (r.verdict & FRAME_SIZE_BAD) {
-			reason = LZ4ADA_DEVFRAME_SIZE;
-		} else if (r.verdict & FRAME_GPU_HASHED) {
-			++stats.gpu_hashed;
-			if (r.hash != ix.walk[k].cksum)
-				reason = LZ4ADA_DEVFRAME_CHECKSUM;
-		} else if (r.flags & FRAME_HAS_CKSUM) {
+		bool hashed = false;
+		const FrameVerdict v = frame_verdict(r, ix.walk[k].cksum, &hashed);
+		int reason = v == FV_HOST_HASH ? LZ4ADA_DEVFRAME_OK : int(v);
+		stats.gpu_hashed += hashed && (v == FV_GOOD || v == FV_CHECKSUM) ? 1 : 0;
+		if (v == FV_HOST_HASH) {
 			// over hash_max: the host chain, the one place where decoded bytes
 			// visit the host, and only to be hashed
 			lz4ada_xxh32_state hs;
@@ -272,7 +207,7 @@ void run_device_pass(const Index& ix, size_t lo, size_t hi, uint32_t nb, uint64_
 		++stats.frames_batched;
 		add_last_path(LZ4ADA_PATH_BATCH | (ix.linked(k) ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT));
 	}
-	*base += rec[nf - 1].out_off + rec[nf - 1].out_len;
+	*base += rec[m.nf - 1].out_off + rec[m.nf - 1].out_len;
 }
 
 }  // namespace
@@ -365,8 +300,8 @@ int lz4ada_decode_frames_device_opt(const void* d_in, int64_t in_len, lz4ada_dev
 			if (hi == lo)  // one frame of 2^31 blocks or more
 				raise(LZ4ADA_CONSTRAINT_ERROR, "a frame holds more blocks than a pass takes");
 			if (real) {
-				run_device_pass(ix, lo, hi, uint32_t(nb), acc, static_cast<const uint8_t*>(d_in),
-				                uint64_t(in_len), jobs, static_cast<uint8_t*>(d_out), &base, hash_max, s);
+				run_device_pass(ix, lo, hi, acc, static_cast<const uint8_t*>(d_in), uint64_t(in_len), jobs,
+				                static_cast<uint8_t*>(d_out), &base, hash_max, s);
 			} else {  // nothing but skippable frames, if any: no launch
 				for (size_t k = lo; k < hi; ++k)
 					if (ix.taken(k))
@@ -397,7 +332,8 @@ int lz4ada_frames_index_device_debug(const void* d_in, int64_t in_len, const lz4
 			raise(LZ4ADA_CONSTRAINT_ERROR, "descriptor capacity exceeded");
 		if (n == 0 || nb == 0)
 			return;
-		const PassMeta m{ uint32_t(nb), uint32_t(n) };
+		PassArrays m;
+		reserve_pass(m, ix, 0, n, 0, uint64_t(in_len));
 		fill_pass(ix, 0, n, static_cast<const uint8_t*>(d_in), m, s);
 		d2h(descs, m.d_desc, m.desc_b, s);
 	});

@@ -24,13 +24,16 @@
 
 namespace lz4ada {
 
-// The lone-block rule (few_large_blocks, lz4ada_host_common.cpp): a frame of
-// at most WALK_LONE_BLOCKS blocks whose largest payload is in
-// [WALK_LONE_MIN_IN, WALK_LONE_MAX_IN] decodes faster one block at a time.
+// The lone-block rule's numbers, for few_large_blocks (lz4ada_host_common.cpp)
+// and the walk below: a frame of at most WALK_LONE_BLOCKS blocks whose largest
+// payload is in [WALK_LONE_MIN_IN, WALK_LONE_MAX_IN] decodes faster one block
+// at a time.
 constexpr int64_t WALK_LONE_BLOCKS = 24;
 constexpr uint32_t WALK_LONE_MIN_IN = 512u << 10;
 constexpr int64_t WALK_LONE_MAX_IN = int64_t(16) << 20;  // LONE_MAX_IN (lz4ada_internal.h)
-// The bulk decoders' largest slot (BATCH_SLOT_MAX, lz4ada_bulk_frames.cpp).
+// The bulk decoders take blocks whose slot is at most this (MAX_RUN,
+// lz4ada_idx.hip); a legacy frame may declare more.  For classify
+// (lz4ada_bulk_frames.cpp) and the walk below.
 constexpr uint32_t WALK_SLOT_MAX = 4u << 20;
 
 // What the walk adds up over a frame's blocks.

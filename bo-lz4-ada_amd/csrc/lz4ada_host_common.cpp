@@ -4,6 +4,7 @@
 // error and path bits, the frame header parser (lib/lz4ada.adb:155-375), the
 // host XXH32 chain, the device-status -> exception map, the lone-block batch
 // and the bulk paths' small helpers.
+#include "lz4ada_frame_walk.h"
 #include "lz4ada_host_common.h"
 
 #include <future>
@@ -547,12 +548,12 @@ bool lone_blocks_disabled()
 
 bool few_large_blocks(const std::vector<lz4ada_block_desc>& d)
 {
-	if (lone_blocks_disabled() || d.empty() || d.size() > 24)
+	if (lone_blocks_disabled() || d.empty() || d.size() > size_t(WALK_LONE_BLOCKS))
 		return false;
 	uint32_t mx = 0;
 	for (const auto& x : d)
 		mx = std::max(mx, x.in_len);
-	return mx >= (512u << 10) && int64_t(mx) <= LONE_MAX_IN;
+	return mx >= WALK_LONE_MIN_IN && int64_t(mx) <= LONE_MAX_IN;
 }
 
 bool decode_lone_blocks(const uint8_t* host_in, const uint8_t* d_in,

@@ -9,7 +9,8 @@
 // XXHash32 C-ABI), lz4ada_bulk.cpp (the bulk frame paths and their C-ABI),
 // lz4ada_bulk_linked.cpp (the linked-frame bulk path), lz4ada_bulk_frames.cpp
 // (many frames in one device pass), lz4ada_bulk_frames_device.cpp (the same
-// pass from device memory to device memory).  lz4ada_multi.cpp
+// pass from device memory to device memory), lz4ada_frames_pass.cpp (the
+// device half of that pass, which both share).  lz4ada_multi.cpp
 // (the multi-GPU entry) keeps a per-device cache of its own and includes
 // only lz4ada_internal.h.
 //
@@ -34,6 +35,7 @@
 
 #include "lz4ada_hip.h"
 #include "lz4ada_internal.h"
+#include "lz4ada_pass_runs.h"
 
 namespace lz4ada {
 
@@ -384,7 +386,7 @@ inline bool try_reserve(DevBuf<T>& b, size_t count)
 // 1 GiB linked frame.  lz4ada_release_device_cache() frees them.  The
 // cache is never destroyed at thread exit (the HIP runtime may be gone).
 // SC_BATCH / SC_BATCH_META: a many-frame pass's compacted output and its
-// per-block / per-frame arrays (lz4ada_bulk_frames.cpp), which outlive the
+// per-block / per-frame arrays (PassArrays below), which outlive the
 // single-frame decodes of the frames the pass did not find good.
 enum ScratchRole { SC_FRAME, SC_OUT, SC_COMPACT, SC_X, SC_Y, SC_H, SC_Z, SC_TAB, SC_P, SC_F, SC_LONE, SC_U,
 	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_N };
@@ -446,35 +448,48 @@ void partial_frame_check(int64_t left);
 // frame's exception propagates.
 void decode_stream_frames(const uint8_t* input, int64_t len, Sink& out, int64_t* committed);
 
-// What the many-frame engines share (lz4ada_bulk_frames.cpp; the device-input
-// engine is lz4ada_bulk_frames_device.cpp): a pass's slot byte budget
-// (LZ4ADA_BATCH_BYTES), the decoded length up to which a pass hashes a
-// content checksum on the GPU (LZ4ADA_BATCH_HASH_MAX), both read per call,
-// and the calling thread's counters behind lz4ada_last_batch_stats().
+// What the many-frame engines share (lz4ada_frames_pass.cpp).  Read per call:
+// a pass's slot byte budget (LZ4ADA_BATCH_BYTES), the decoded length up to
+// which it hashes a content checksum on the GPU (LZ4ADA_BATCH_HASH_MAX), the
+// slot bytes up to which a linked frame shares it (LZ4ADA_BATCH_LINKED_MAX,
+// DESIGN.md §12), the flags of the entries that take none (LZ4ADA_BATCH_LINKED=1
+// -> LZ4ADA_FRAMES_LINKED).  The thread's counters (lz4ada_last_batch_stats).
 int64_t batch_budget();
 int64_t batch_hash_max();
-lz4ada_batch_stats& batch_stats();
-// Linked frames in a pass: the slot bytes up to which a linked
-// frame shares one (LZ4ADA_BATCH_LINKED_MAX), and the flags of the entries
-// that take none (LZ4ADA_BATCH_LINKED=1 -> LZ4ADA_FRAMES_LINKED), both read
-// per call.
 int64_t batch_linked_max();
 uint32_t batch_env_flags();
-// A maximal run of frames of one kind inside a pass: blocks [b0, b1) and
-// frames [f0, f1) of the pass's arrays.
-struct PassRun {
-	uint32_t b0, b1, f0, f1;
-	bool linked;
+lz4ada_batch_stats& batch_stats();
+// A pass's device arrays in this thread's scratch.  SC_BATCH_META: descriptors
+// | frame records | statuses | dst_off | loc | part.  SC_OUT: the slots.
+// SC_TAB: the sequence index, only when a run is linked.  reserve() queues
+// nothing; null, or what had no room: "block arrays", "slots", "sequence index".
+struct PassArrays {
+	uint32_t nb = 0, nf = 0;
+	size_t desc_b = 0, rec_b = 0, st_b = 0;
+	lz4ada_block_desc* d_desc = nullptr;
+	FrameRec* d_rec = nullptr;
+	lz4ada_block_status* d_st = nullptr;
+	uint64_t *d_off = nullptr, *d_loc = nullptr, *d_part = nullptr;
+	uint8_t *d_slots = nullptr, *d_tab = nullptr;
+	std::vector<PassRun> runs;  // pass_runs(frames)
+	const char* reserve(const std::vector<PassFrame>& frames, uint64_t slots, uint64_t in_len);
 };
-// The decode launches of one run, on stream, no synchronisation.  An
-// independent run: launch_decode_checked over its blocks.  A linked run: the
-// block checksums beside launch_index over its blocks, k_decode_idx_frames
-// over its frames, then the join.  d_tab: index_table_bytes(in_len, nb) bytes
-// (may be null when no run is linked); d_desc / d_st / d_rec: the pass's
-// arrays (nb blocks).
-void decode_pass_run(const uint8_t* d_in, uint64_t in_len, const lz4ada_block_desc* d_desc, uint32_t nb,
-                     uint8_t* d_tab, uint8_t* d_slots, lz4ada_block_status* d_st, const FrameRec* d_rec,
-                     const PassRun& run, hipStream_t stream);
+// The device half of a pass, once a.d_desc and a.d_rec are queued on stream:
+// the status memset, each run's decode launches, k_frames_plan, k_compact into
+// dst, k_xxh32_spans, the frame records into the pinned h_rec, the pass's one
+// synchronisation, ++passes.  in_off must rise strictly over the whole pass
+// (frame order, block order) and in_len cover every block: the index decoder's
+// table keeps block b's records at ((in_off >> 8) + b) and is sized from in_len
+// (index_table_bytes), or two blocks' records would overlap or leave the table.
+// A linked run indexes into d_tab + b0 * 64, as one launch_index over the pass.
+void decode_pass(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, uint8_t* dst, uint64_t hash_max,
+                 FrameRec* h_rec, hipStream_t stream);
+// A frame's record after the pass, against its declared content checksum: the
+// LZ4ADA_DEVFRAME_* reason, or FV_HOST_HASH: good so far, the checksum (over
+// hash_max bytes) is the host chain's.  *gpu_hashed: the record carries a hash.
+enum FrameVerdict { FV_GOOD = LZ4ADA_DEVFRAME_OK, FV_BLOCK = LZ4ADA_DEVFRAME_BLOCK, FV_SIZE = LZ4ADA_DEVFRAME_SIZE,
+	            FV_CHECKSUM = LZ4ADA_DEVFRAME_CHECKSUM, FV_HOST_HASH };
+FrameVerdict frame_verdict(const FrameRec& r, uint32_t declared, bool* gpu_hashed);
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

@@ -1,0 +1,47 @@
+// lz4ada_pass_runs.h -- how the frames of a many-frame pass are cut into runs
+// of one kind.  Standard library only, so a plain C++ program
+// can include it (tools/pass_runs_check.cpp).
+#pragma once
+#include <stdint.h>
+#include <vector>
+
+namespace lz4ada {
+
+// A frame as the cutter sees it: its blocks in this pass (0 for one that rides
+// along: skippable, empty, or not taken by the device index) and its kind.
+struct PassFrame {
+	uint32_t nblocks;
+	bool linked;
+};
+// A maximal run of frames of one kind: blocks [b0, b1), frames [f0, f1).
+struct PassRun {
+	uint32_t b0, b1, f0, f1;
+	bool linked;
+};
+
+// The runs in order, tiling the frames and their blocks.  A run ends just
+// before the first frame with blocks of the other kind; a frame without blocks,
+// a leading one included, belongs to the run it falls into, so frames without
+// blocks alone are one run with b0 == b1, and no frames are no run.
+inline std::vector<PassRun> pass_runs(const std::vector<PassFrame>& fr)
+{
+	std::vector<PassRun> runs;
+	for (uint32_t k = 0, b = 0, nf = uint32_t(fr.size()); k < nf;) {
+		int kind = -1;
+		PassRun r{ b, b, k, k, false };
+		for (; r.f1 < nf; ++r.f1) {
+			const int kq = fr[r.f1].nblocks ? int(fr[r.f1].linked) : -1;
+			if (kind >= 0 && kq >= 0 && kq != kind)
+				break;
+			kind = kind >= 0 ? kind : kq;
+			r.b1 += fr[r.f1].nblocks;
+		}
+		r.linked = kind == 1;
+		runs.push_back(r);
+		b = r.b1;
+		k = r.f1;
+	}
+	return runs;
+}
+
+}  // namespace lz4ada

@@ -3,8 +3,11 @@ which frames a concatenated stream holds, where, and whether each can share
 a device pass -- and the argument checks of lz4ada_decode_frames, which run
 before any device call.  Streams here hold stored blocks only."""
 import ctypes
+import os
 import random
+import shutil
 import struct
+import subprocess
 
 import pytest
 
@@ -16,6 +19,7 @@ import lz4frame
 SIZES = [0, 1, 2, 3, 15, 16, 17, 4095, 65536, 65537]
 BMAX = [64 << 10, 256 << 10, 4 << 20]
 SKIP_AT, LINKED_AT = 41, 123
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def stored_frame(rng, n, bmax, **kw):
@@ -155,3 +159,19 @@ def test_batch_hash_max_override(monkeypatch):
     assert lz4ada.batch_hash_max() == 4096
     monkeypatch.delenv("LZ4ADA_BATCH_HASH_MAX")
     assert lz4ada.batch_hash_max() == g
+
+
+def test_pass_runs_against_its_definition(tmp_path):
+    """The stand-alone program, host code only, under the sanitizers: the run
+    cutter of the many-frame pass over every sequence of up to 8 frames."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "pass_runs_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-static-libasan", "-static-libubsan", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "bo-lz4-ada_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "pass_runs_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "488281 sequences: no sanitizer report, every run as defined" in r.stdout
+    assert "FAIL" not in r.stdout

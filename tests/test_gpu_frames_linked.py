@@ -317,6 +317,8 @@ def check_host(batch, out, jobs, linked, refused=()):
             assert j.path == INDEP_PATH if linked else j.path & lz4ada.PATH_INDEPENDENT, i
         elif kind == "linked" and linked:
             assert j.path == LINKED_PATH, i
+        elif kind == "skip":  # consumed by the pass, no output
+            assert j.path == lz4ada.PATH_BATCH, i
         else:  # the single way
             assert j.path and not j.path & lz4ada.PATH_BATCH, (i, kind)
     assert at == len(out)
@@ -457,3 +459,65 @@ def test_device_pass_without_the_flag(batch):
         else:
             assert (j.status, j.reason) == (lz4ada.EXACT_PATH, lz4ada.BATCH_LINKED), (i, kind)
     assert lz4ada.last_path() == INDEP_PATH
+
+
+# ------------------------------------------- frames without blocks at the seams
+
+def seam_frames():
+    """[(frame, kind)] where the runs of a pass are cut with frames without
+    blocks on both sides of every cut: kind "indep", "linked", "skip" or "bad"
+    (a bad magic, which only the device engine is given: it rides along).
+    Blocks of 300 to 5,000 bytes, but the first of the linked frame of two: the
+    wave ends a chain after a block short of the block size
+    (test_kernel_short_middle_block), so that one is full."""
+    def skip(n):
+        return struct.pack("<II", 0x184D2A53, n) + bytes(range(n))
+    empty_linked = lz4frame.build_frame([], 64 * KiB, indep=False, content_cksum=True)[0]
+    one_block = make_frame(3, [2000])[0]
+    return [(make_frame(2, [])[0], "indep"),          # empty, with a content checksum
+            (linked_frame([65536, 700], seed=61)[0], "linked"),
+            (skip(33), "skip"),
+            (linked_frame([1200], seed=62, block_cksum=True)[0], "linked"),
+            (make_frame(0, [])[0], "indep"),          # empty
+            (make_frame(7, [5000, 300])[0], "indep"),
+            (empty_linked, "linked"),
+            (one_block, "indep"),
+            (b"\x05" + one_block[1:], "bad"),
+            (linked_frame([4000], seed=63, size=True)[0], "linked"),
+            (skip(5), "skip")]
+
+
+@pytest.fixture(scope="module")
+def seams():
+    """seam_frames() with the oracle's (status, bytes, message), as `batch`."""
+    res = []
+    for f, kind in seam_frames():
+        st, ref, msg = oracle(f)
+        assert (st == O.OK) == (kind != "bad"), (kind, msg)
+        res.append((f, st, ref, msg, kind))
+    return tuple(res)
+
+
+def test_runs_cut_beside_frames_without_blocks(seams):
+    host = [b for b in seams if b[4] != "bad"]
+    out, jobs = lz4ada.decode_frames_jobs([b[0] for b in host], linked=True)
+    check_host(host, out, jobs, True)
+    assert stats() == dict(batched=len(host), single=0, passes=1)
+
+    out, jobs, data = decode_device(seams, True)
+    assert lz4ada.last_path() == lz4ada.PATH_BATCH | lz4ada.PATH_INDEPENDENT | lz4ada.PATH_LINKED
+    s = lz4ada.last_batch_stats()
+    assert (s.frames_batched, s.passes) == (len(host), 1)
+    end = 0
+    for i, (f, st, ref, msg, kind) in enumerate(seams):
+        j = jobs[i]
+        if kind != "bad":
+            assert (j.status, j.reason, j.consumed, j.out_len) == (0, 0, len(f), len(ref)), (i, kind)
+            assert j.out_off >= end, i
+            end = j.out_off + j.out_len
+            assert out[j.out_off:end] == ref, (i, kind)
+        else:
+            assert (j.status, j.reason, j.out_len, j.consumed) == \
+                (lz4ada.EXACT_PATH, lz4ada.BATCH_NOT_INDEXED, 0, 0), (i, kind)
+            got, _, exc = lz4ada.explain_frame(data, j)
+            assert got == ref and str(exc) == O.exception_information(st, msg)
