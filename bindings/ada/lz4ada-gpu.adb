@@ -101,6 +101,19 @@ package body LZ4Ada.GPU is
 		return B;
 	end Frames_Device_Bound;
 
+	function Frames_Device_Sizes(D_In:   in     System.Address;
+				In_Len: in     Interfaces.Integer_64;
+				Jobs:   in out Device_Frame_Jobs;
+				Stream: in     System.Address := System.Null_Address;
+				Linked: in     Boolean := False)
+				return Interfaces.Integer_64 is
+		T: aliased Interfaces.Integer_64;
+	begin
+		Check(C_Frames_Device_Sizes(D_In, In_Len, Jobs'Address, Jobs'Length,
+			(if Linked then Frames_Linked else 0), T'Access, Stream));
+		return T;
+	end Frames_Device_Sizes;
+
 	procedure Decode_Frames_Device(D_In:          in     System.Address;
 				In_Len:        in     Interfaces.Integer_64;
 				Jobs:          in out Device_Frame_Jobs;
@@ -108,13 +121,16 @@ package body LZ4Ada.GPU is
 				Out_Cap:       in     Interfaces.Integer_64;
 				Output_Length: out    Interfaces.Integer_64;
 				Stream:        in     System.Address := System.Null_Address;
-				Linked:        in     Boolean := False) is
+				Linked:        in     Boolean := False;
+				Exact:         in     Boolean := False) is
+		use type Interfaces.Unsigned_32;
 		L:  aliased Interfaces.Integer_64;
 		St: Interfaces.Integer_32;
 	begin
-		if Linked then
+		if Linked or Exact then
 			St := C_Decode_Frames_Device_Opt(D_In, In_Len, Jobs'Address, Jobs'Length,
-				Frames_Linked, D_Out, Out_Cap, L'Access, Stream);
+				(if Linked then Frames_Linked else 0) or (if Exact then Frames_Exact else 0),
+				D_Out, Out_Cap, L'Access, Stream);
 		else
 			St := C_Decode_Frames_Device(D_In, In_Len, Jobs'Address, Jobs'Length,
 				D_Out, Out_Cap, L'Access, Stream);

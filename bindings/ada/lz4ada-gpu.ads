@@ -98,8 +98,22 @@ package LZ4Ada.GPU is
 				Stream: in     System.Address := System.Null_Address;
 				Linked: in     Boolean := False)
 				return Interfaces.Integer_64;
+	-- lz4ada_frames_device_sizes: the exact decoded sizes, found on the
+	-- device without decoding.  Out_Len of every accepted job is its frame's
+	-- decoded length; the result is their sum, an output capacity that
+	-- suffices for Decode_Frames_Device with Exact.  Status 9 with Reason 5
+	-- or 6 (LZ4ADA_DEVFRAME_BLOCK / _SIZE): the sizes already fail the frame.
+	function Frames_Device_Sizes(D_In:   in     System.Address;
+				In_Len: in     Interfaces.Integer_64;
+				Jobs:   in out Device_Frame_Jobs;
+				Stream: in     System.Address := System.Null_Address;
+				Linked: in     Boolean := False)
+				return Interfaces.Integer_64;
 	-- Too_Little_Memory when Out_Cap is below the bound (Output_Length then
-	-- holds the bound and D_Out is untouched).
+	-- holds the bound and D_Out is untouched).  Exact: LZ4ADA_FRAMES_EXACT --
+	-- the frames are sized first and laid out by their sizes, and the bound
+	-- is Frames_Device_Sizes' total (the flags are then given as they stand:
+	-- LZ4ADA_BATCH_LINKED in the environment is not consulted).
 	procedure Decode_Frames_Device(D_In:          in     System.Address;
 				In_Len:        in     Interfaces.Integer_64;
 				Jobs:          in out Device_Frame_Jobs;
@@ -107,7 +121,8 @@ package LZ4Ada.GPU is
 				Out_Cap:       in     Interfaces.Integer_64;
 				Output_Length: out    Interfaces.Integer_64;
 				Stream:        in     System.Address := System.Null_Address;
-				Linked:        in     Boolean := False);
+				Linked:        in     Boolean := False;
+				Exact:         in     Boolean := False);
 
 	-- lz4ada_rccl_version: the RCCL this process bound (22606 = 2.26.6).
 	function RCCL_Version return Interfaces.Integer_32;
@@ -157,8 +172,9 @@ private
 			return Interfaces.Integer_32;
 	pragma Import(C, C_Decode_Frames_Device, "lz4ada_decode_frames_device");
 
-	-- the same three with flags (LZ4ADA_FRAMES_LINKED = 1)
+	-- the same three with flags (LZ4ADA_FRAMES_LINKED = 1, LZ4ADA_FRAMES_EXACT = 2)
 	Frames_Linked: constant Interfaces.Unsigned_32 := 1;
+	Frames_Exact:  constant Interfaces.Unsigned_32 := 2;
 
 	function C_Decode_Frames_Opt(Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
 			Flags: Interfaces.Unsigned_32;
@@ -181,5 +197,12 @@ private
 			Out_Len: access Interfaces.Integer_64; Stream: System.Address)
 			return Interfaces.Integer_32;
 	pragma Import(C, C_Decode_Frames_Device_Opt, "lz4ada_decode_frames_device_opt");
+
+	function C_Frames_Device_Sizes(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Flags: Interfaces.Unsigned_32;
+			Total: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, C_Frames_Device_Sizes, "lz4ada_frames_device_sizes");
 
 end LZ4Ada.GPU;

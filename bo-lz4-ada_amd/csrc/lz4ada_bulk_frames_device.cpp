@@ -12,7 +12,12 @@
 // chain (content_xxh32_d2h with no host destination).  A frame the pass does
 // not find good in every respect gets LZ4ADA_EXACT_PATH and a reason; this
 // unit invents no exception text.  With LZ4ADA_FRAMES_LINKED the walk accepts
-// linked frames up to lz4ada_batch_linked_max().
+// linked frames up to lz4ada_batch_linked_max().  With
+// LZ4ADA_FRAMES_EXACT, and in lz4ada_frames_device_sizes, a sizes stage finds
+// what every accepted frame decodes to without decoding it (lz4ada_sizes.hip,
+// one more D2H of per-frame records per call), and the passes are laid out by
+// those sizes instead of the slot capacities.
+#include "lz4ada_block_size.h"
 #include "lz4ada_frame_walk.h"
 #include "lz4ada_host_common.h"
 
@@ -37,7 +42,23 @@ struct Index {
 	bool linked(size_t k) const { return (walk[k].flags & FRAME_LINKED) != 0; }
 	bool taken(size_t k) const { return walk[k].verdict == LZ4ADA_BATCH_OK; }
 	bool skippable(size_t k) const { return walk[k].format == LZ4ADA_FORMAT_SKIPPABLE; }
+	// The sizes stage (size_jobs), when it ran: every frame's
+	// exact and tight bytes, and on the device (this thread's SC_SIZES scratch)
+	// the walk records with the tight slots, every frame's first block among
+	// the block sizes, and the block sizes of the whole call.
+	bool sized = false;
+	std::vector<FrameSizeRec> size;  // by sorted position
+	FrameWalkRec* d_tight = nullptr;
+	uint64_t* d_size_first = nullptr;
+	uint32_t* d_size = nullptr;
+	uint64_t slots(size_t k) const { return sized ? size[k].tight : walk[k].slots; }
 };
+
+// Blocks per chunk of the sizes stage: its descriptors, statuses and index
+// table are temporary, 160 bytes per block (and a quarter of the input for the
+// table, whatever the chunk).  LZ4ADA_SIZES_CHUNK_BLOCKS, read per call,
+// overrides it (the tests cut a call into many chunks with it).
+constexpr int64_t SIZES_CHUNK_BLOCKS = int64_t(1) << 20;
 
 [[noreturn]] void misuse(const char* entry, const std::string& what)
 {
@@ -120,6 +141,101 @@ int64_t report_index(const Index& ix, lz4ada_device_frame_job* jobs)
 	return int64_t(bound);
 }
 
+// The sizes stage: the exact decoded size of every block of every accepted
+// frame, without decoding (k_index's records added up, or the wave's own walk
+// of the chain: lz4ada_sizes.hip), in chunks of whole frames.  A chunk fills
+// temporary descriptors with the nominal slots (SC_BATCH_META, which a pass
+// lays out anew), indexes them (SC_TAB) and needs no output slot.  What the
+// passes need stays in SC_SIZES for the call.  One host synchronisation: the
+// per-frame size records.  A frame the sizes fail is no longer taken(), with
+// LZ4ADA_DEVFRAME_BLOCK or _SIZE as its verdict, on the host and on the device.
+void size_jobs(Index& ix, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
+{
+	const size_t n = ix.order.size();
+	ix.sized = true;
+	ix.size.assign(n, FrameSizeRec{});
+	if (n == 0)
+		return;
+	// the chunks: sorted jobs [lo, hi) and their blocks
+	struct Chunk {
+		size_t lo, hi;
+		uint64_t nb;
+	};
+	std::vector<Chunk> chunks;
+	const uint64_t chunk_blocks = uint64_t(env_bytes("LZ4ADA_SIZES_CHUNK_BLOCKS", SIZES_CHUNK_BLOCKS));
+	uint64_t nb_all = 0, nb_max = 0;
+	size_t nf_max = 0;
+	for (size_t lo = 0; lo < n;) {
+		size_t hi = lo;
+		uint64_t nb = 0;
+		for (; hi < n; ++hi) {
+			const uint64_t add = ix.taken(hi) ? ix.walk[hi].nblocks : 0;
+			if (hi > lo && nb + add > chunk_blocks)
+				break;
+			nb += add;
+		}
+		if (nb >= (uint64_t(1) << 31))  // one frame of 2^31 blocks or more
+			raise(LZ4ADA_CONSTRAINT_ERROR, "a frame holds more blocks than a pass takes");
+		chunks.push_back(Chunk{ lo, hi, nb });
+		nb_all += nb;
+		nb_max = std::max(nb_max, nb);
+		nf_max = std::max(nf_max, hi - lo);
+		lo = hi;
+	}
+	const size_t tight_b = n * sizeof(FrameWalkRec), first_b = n * 8, rec_b = n * sizeof(FrameSizeRec);
+	uint8_t* const p = scratch(SC_SIZES, tight_b + first_b + rec_b + size_t(nb_all) * 4);
+	const size_t desc_b = size_t(nb_max) * sizeof(lz4ada_block_desc), frec_b = nf_max * sizeof(FrameRec);
+	uint8_t* const t = scratch(SC_BATCH_META, desc_b + frec_b + size_t(nb_max) * sizeof(lz4ada_block_status));
+	uint8_t* const d_tab = nb_max ? scratch(SC_TAB, index_table_bytes(in_len, uint32_t(nb_max))) : nullptr;
+	if (!p || !t || (nb_max && !d_tab))
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the sizes stage");
+	ix.d_tight = reinterpret_cast<FrameWalkRec*>(p);
+	ix.d_size_first = reinterpret_cast<uint64_t*>(p + tight_b);
+	FrameSizeRec* const d_rec = reinterpret_cast<FrameSizeRec*>(p + tight_b + first_b);
+	ix.d_size = reinterpret_cast<uint32_t*>(p + tight_b + first_b + rec_b);
+	lz4ada_block_desc* const d_desc = reinterpret_cast<lz4ada_block_desc*>(t);
+	FrameRec* const d_frec = reinterpret_cast<FrameRec*>(t + desc_b);
+	lz4ada_block_status* const d_st = reinterpret_cast<lz4ada_block_status*>(t + desc_b + frec_b);
+	uint64_t base = 0;  // the chunk's first block among the call's sizes
+	for (const Chunk& c : chunks) {
+		const uint32_t nf = uint32_t(c.hi - c.lo), nb = uint32_t(c.nb);
+		HIP_OK(launch_frames_scan(ix.d_walk + c.lo, nf, ix.d_first, ix.d_slot, stream));
+		HIP_OK(launch_frames_fill(d_in, ix.d_span + c.lo, ix.d_walk + c.lo, ix.d_first, ix.d_slot, nf,
+		                          lone_blocks_disabled(), ix.take_linked, ix.linked_max, d_desc, d_frec, stream));
+		if (nb) {
+			HIP_OK(hipMemsetAsync(d_st, 0, size_t(nb) * sizeof(lz4ada_block_status), stream));
+			HIP_OK(launch_index(d_in, in_len, d_desc, nb, d_tab, d_st, stream));
+			HIP_OK(launch_block_sizes(d_in, in_len, d_desc, d_st, nb, d_tab, ix.d_size + base, stream));
+		}
+		HIP_OK(launch_frame_sizes(ix.d_walk + c.lo, ix.d_first, nf, base, d_desc, ix.d_size + base, d_rec + c.lo,
+		                          ix.d_size_first + c.lo, ix.d_tight + c.lo, stream));
+		base += nb;
+	}
+	// the stage's host synchronisation: sizes and verdicts, no frame byte
+	PinBuf& h = scratch_cache().pin;
+	h.reserve(rec_b);
+	HIP_OK(hipMemcpyAsync(h.p, d_rec, rec_b, hipMemcpyDeviceToHost, stream));
+	HIP_OK(hipStreamSynchronize(stream));
+	memcpy(ix.size.data(), h.p, rec_b);
+	for (size_t k = 0; k < n; ++k)
+		if (ix.taken(k))
+			ix.walk[k].verdict = ix.size[k].verdict;
+}
+
+// What the sizes stage says about every job: report_index with the exact
+// length of every accepted frame, and their sum.
+int64_t report_sizes(const Index& ix, lz4ada_device_frame_job* jobs)
+{
+	report_index(ix, jobs);
+	uint64_t total = 0;
+	for (size_t k = 0; k < ix.order.size(); ++k)
+		if (ix.taken(k)) {
+			jobs[ix.order[k]].out_len = int64_t(ix.size[k].exact);
+			total += ix.size[k].exact;
+		}
+	return int64_t(total);
+}
+
 // Room on the device for a pass over the sorted jobs [lo, hi), their blocks as
 // k_frames_scan counts them: a frame the index did not take rides without any.
 void reserve_pass(PassArrays& a, const Index& ix, size_t lo, size_t hi, uint64_t slots, uint64_t in_len)
@@ -136,9 +252,15 @@ void reserve_pass(PassArrays& a, const Index& ix, size_t lo, size_t hi, uint64_t
 void fill_pass(const Index& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassArrays& m,
                hipStream_t stream)
 {
-	HIP_OK(launch_frames_scan(ix.d_walk + lo, m.nf, ix.d_first, ix.d_slot, stream));
+	// sized: the scan adds up the tight slots, the fill lays the nominal ones
+	// out from each frame's tight base, and the refit puts every block where
+	// its size says (out_cap = size, steps of round256(size))
+	HIP_OK(launch_frames_scan((ix.sized ? ix.d_tight : ix.d_walk) + lo, m.nf, ix.d_first, ix.d_slot, stream));
 	HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, ix.d_walk + lo, ix.d_first, ix.d_slot, m.nf,
 	                          lone_blocks_disabled(), ix.take_linked, ix.linked_max, m.d_desc, m.d_rec, stream));
+	if (ix.sized)
+		HIP_OK(launch_frames_refit(ix.d_tight + lo, ix.d_first, ix.d_slot, ix.d_size_first + lo, ix.d_size, m.nf,
+		                           m.d_desc, stream));
 }
 
 void job_rejected(lz4ada_device_frame_job& j, int reason)
@@ -255,6 +377,25 @@ int lz4ada_frames_device_bound_opt(const void* d_in, int64_t in_len, lz4ada_devi
 	});
 }
 
+int lz4ada_frames_device_sizes(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                               uint32_t flags, int64_t* total, void* stream)
+{
+	*total = 0;
+	batch_stats() = lz4ada_batch_stats{};
+	return guarded(nullptr, [&] {
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		Index ix;
+		index_jobs("lz4ada_frames_device_sizes", d_in, in_len, jobs, njobs, flags, s, ix);
+		size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
+		*total = report_sizes(ix, jobs);
+	});
+}
+
+int64_t lz4ada_block_size_host(const uint8_t* block, int64_t n, int stored)
+{
+	return block_decoded_size(block, n, stored != 0);
+}
+
 int lz4ada_decode_frames_device(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
                                 void* d_out, int64_t out_cap, int64_t* out_len, void* stream)
 {
@@ -273,7 +414,13 @@ int lz4ada_decode_frames_device_opt(const void* d_in, int64_t in_len, lz4ada_dev
 		hipStream_t s = static_cast<hipStream_t>(stream);
 		Index ix;
 		index_jobs("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, flags, s, ix);
-		const int64_t bound = report_index(ix, jobs);
+		// LZ4ADA_FRAMES_EXACT: the sizes stage, then the frames it passed laid
+		// out by their sizes; what suffices is their sum, not the bound
+		if (flags & LZ4ADA_FRAMES_EXACT)
+			size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
+		const int64_t sizes_total = ix.sized ? report_sizes(ix, jobs) : 0;
+		const int64_t index_bound = report_index(ix, jobs);
+		const int64_t bound = ix.sized ? sizes_total : index_bound;
 		if (out_cap < bound || (bound > 0 && !d_out)) {
 			*out_len = bound;
 			raise(LZ4ADA_TOO_LITTLE_MEMORY, "lz4ada_decode_frames_device: the output holds" + img(out_cap) +
@@ -290,10 +437,10 @@ int lz4ada_decode_frames_device_opt(const void* d_in, int64_t in_len, lz4ada_dev
 			for (; hi < n; ++hi) {
 				if (!ix.taken(hi))
 					continue;
-				if ((acc && acc + ix.walk[hi].slots > budget) ||
+				if ((acc && acc + ix.slots(hi) > budget) ||
 				    nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
 					break;
-				acc += ix.walk[hi].slots;
+				acc += ix.slots(hi);
 				nb += ix.walk[hi].nblocks;
 				real += ix.skippable(hi) ? 0 : 1;
 			}

@@ -388,8 +388,10 @@ inline bool try_reserve(DevBuf<T>& b, size_t count)
 // SC_BATCH / SC_BATCH_META: a many-frame pass's compacted output and its
 // per-block / per-frame arrays (PassArrays below), which outlive the
 // single-frame decodes of the frames the pass did not find good.
+// SC_SIZES: what the sizes stage of a device call leaves for its passes
+// (lz4ada_bulk_frames_device.cpp).
 enum ScratchRole { SC_FRAME, SC_OUT, SC_COMPACT, SC_X, SC_Y, SC_H, SC_Z, SC_TAB, SC_P, SC_F, SC_LONE, SC_U,
-	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_N };
+	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_SIZES, SC_N };
 struct ScratchCache {
 	DevBuf<uint8_t> b[SC_N];
 	PinBuf pin;  // the linked path's small host transfers (pinned: no staging copy)

@@ -396,4 +396,38 @@ hipError_t launch_frames_fill(const uint8_t* d_in, const FrameSpan* d_span, cons
                               bool no_lone, bool take_linked, uint64_t linked_max, lz4ada_block_desc* d_desc,
                               FrameRec* d_rec, hipStream_t stream);
 
+// ---- exact decoded sizes (lz4ada_sizes.hip) ----
+// What k_frame_sizes found out about one frame.
+struct FrameSizeRec {
+	uint64_t exact;   // its decoded bytes
+	uint64_t tight;   // sum of round256(block size): its slots when a pass lays it out by size
+	int32_t verdict;  // the walk's, or LZ4ADA_DEVFRAME_BLOCK / _SIZE; exact = tight = 0 unless 0
+	uint32_t pad;
+};
+// One wave per block, after a launch_index over the same descriptors into
+// d_tab and d_status: d_size[b] gets block b's decoded length, 0xFFFFFFFF when
+// its chain is malformed (block_decoded_size, lz4ada_block_size.h).  Reads no
+// byte outside a block's payload and writes nothing but d_size.
+hipError_t launch_block_sizes(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
+                              const lz4ada_block_status* d_status, uint32_t nblocks, const uint8_t* d_tab,
+                              uint32_t* d_size, hipStream_t stream);
+// One lane per frame, over the frames of a launch_frames_scan / _fill with the
+// nominal slots (d_first, d_desc) and their blocks' d_size: d_rec[i] as above.
+// A frame is LZ4ADA_DEVFRAME_BLOCK when a block's size is unknown or over its
+// slot_cap, or when a linked frame's middle block does not fill its slot, and
+// LZ4ADA_DEVFRAME_SIZE when the sizes do not add up to a declared content
+// size; d_walk[i].verdict then says so too, so that later scans and fills
+// give the frame no block and no slot.  d_size_first[i]: size_base + its first
+// block; d_tight[i]: d_walk[i] with the tight bytes as its slots.
+hipError_t launch_frame_sizes(FrameWalkRec* d_walk, const uint64_t* d_first, uint32_t nframes, uint64_t size_base,
+                              const lz4ada_block_desc* d_desc, const uint32_t* d_size, FrameSizeRec* d_rec,
+                              uint64_t* d_size_first, FrameWalkRec* d_tight, hipStream_t stream);
+// One lane per frame, over descriptors from launch_frames_fill whose d_first /
+// d_slot come from a launch_frames_scan over d_tight: block k of frame i gets
+// out_cap = its size and out_off from d_slot[i] in steps of round256(size).
+// Never places a block past d_slot[i + 1].
+hipError_t launch_frames_refit(const FrameWalkRec* d_tight, const uint64_t* d_first, const uint64_t* d_slot,
+                               const uint64_t* d_size_first, const uint32_t* d_size, uint32_t nframes,
+                               lz4ada_block_desc* d_desc, hipStream_t stream);
+
 }  // namespace lz4ada

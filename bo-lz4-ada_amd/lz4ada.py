@@ -205,6 +205,8 @@ BATCH_OK, BATCH_LINKED, BATCH_BIG_BLOCK, BATCH_OVER_BUDGET, BATCH_NOT_INDEXED = 
 # flags of the many-frame calls (the `linked` keyword): linked frames up to
 # batch_linked_max() share the pass
 FRAMES_LINKED = 1
+# (the `exact` keyword): the passes are laid out by the exact decoded sizes
+FRAMES_EXACT = 2
 
 _P = ctypes.POINTER
 _sig = {
@@ -229,6 +231,8 @@ _sig = {
                                         ctypes.c_int),
     "lz4ada_frame_walk_host_opt": ([_vp, _i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo), _vp, _i64],
                                    ctypes.c_int),
+    "lz4ada_frames_device_sizes": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _pi64, _vp], ctypes.c_int),
+    "lz4ada_block_size_host": ([_vp, _i64, ctypes.c_int], _i64),
     "lz4ada_batch_linked_max": ([], ctypes.c_int64),
     "lz4ada_decode_idx_frames_debug": ([_vp, ctypes.c_uint64, _vp, _i64, _pi64, _vp, _i64, _vp, _vp, _vp],
                                        ctypes.c_int),
@@ -618,10 +622,14 @@ def _device_jobs(spans):
     return jobs
 
 
-def _device_entry(linked, plain, opt):
-    if not linked:
+def _device_entry(linked, plain, opt, exact=False):
+    if not linked and not exact:
         return plain
-    return lambda *a: opt(*a[:4], FRAMES_LINKED, *a[4:])
+    flags = (FRAMES_LINKED if linked else 0) | (FRAMES_EXACT if exact else 0)
+    if exact and not linked:  # as the plain entry reads it
+        e = os.environ.get("LZ4ADA_BATCH_LINKED", "")
+        flags |= FRAMES_LINKED if e and e[0] != "0" else 0
+    return lambda *a: opt(*a[:4], flags, *a[4:])
 
 
 def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0, linked=False):
@@ -635,16 +643,40 @@ def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0, linked=F
     return bound.value, jobs
 
 
+def frames_device_sizes(d_in: int, in_len: int, spans, stream: int = 0, linked=False):
+    """The exact decoded sizes of the frames at spans [(in_off, in_len)] of the
+    device buffer d_in (raw pointer), found on the device without decoding ->
+    (total: an out_cap that suffices for decode_frames_device(exact=True), the
+    DeviceFrameJob array: out_len is a frame's decoded length; status and
+    reason as frames_device_bound gives them, or EXACT_PATH with
+    DEVFRAME_BLOCK / DEVFRAME_SIZE from the sizes)."""
+    jobs = _device_jobs(spans)
+    total = _i64()
+    _check(_lib.lz4ada_frames_device_sizes(d_in, in_len, jobs, len(spans), FRAMES_LINKED if linked else 0,
+                                           ctypes.byref(total), stream), _thread_error())
+    return total.value, jobs
+
+
+def block_size_host(block, stored=False) -> int:
+    """Test-only: the size rule on the host -> the decoded length of one
+    block payload, or -1 when its sequence chain is malformed."""
+    return int(_lib.lz4ada_block_size_host(_addr(block, 0) if len(block) else None, len(block),
+                                           1 if stored else 0))
+
+
 def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0,
-                         linked=False):
+                         linked=False, exact=False):
     """Decode the frames at spans [(in_off, in_len)] of the device buffer d_in
     into the device buffer d_out (raw pointers) -> (bytes written, the
     DeviceFrameJob array: out_off, out_len, consumed, status, reason).  A
     frame with status EXACT_PATH was not decoded: explain_frame gives the
-    reference's verdict.  TooLittleMemory carries the needed size as .bound."""
+    reference's verdict.  TooLittleMemory carries the needed size as .bound.
+    exact: the frames are sized first (frames_device_sizes) and laid out by
+    their sizes, so out_cap need only be that call's total."""
     jobs = _device_jobs(spans)
     n = _i64()
-    call = _device_entry(linked, _lib.lz4ada_decode_frames_device, _lib.lz4ada_decode_frames_device_opt)
+    call = _device_entry(linked, _lib.lz4ada_decode_frames_device, _lib.lz4ada_decode_frames_device_opt,
+                         exact)
     st = call(d_in, in_len, jobs, len(spans), d_out, out_cap, ctypes.byref(n), stream)
     if st:
         exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
@@ -653,11 +685,12 @@ def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int
     return n.value, jobs
 
 
-def decode_frames_tensor(t, spans, out=None, linked=False):
+def decode_frames_tensor(t, spans, out=None, linked=False, exact=False):
     """decode_frames_device for a CUDA torch.uint8 tensor holding the frames,
     on torch's current stream -> (the decoded bytes as a uint8 tensor on the
     same device, the DeviceFrameJob array).  out: a uint8 tensor there to
-    decode into; by default one is allocated from frames_device_bound."""
+    decode into; by default one is allocated from frames_device_bound, or,
+    exact, from frames_device_sizes."""
     if torch is None:
         raise RuntimeError("decode_frames_tensor needs torch")
     if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
@@ -665,13 +698,14 @@ def decode_frames_tensor(t, spans, out=None, linked=False):
     with torch.cuda.device(t.device):
         stream = torch.cuda.current_stream().cuda_stream
         if out is None:
-            bound, _ = frames_device_bound(t.data_ptr(), t.numel(), spans, stream, linked)
+            size_of = frames_device_sizes if exact else frames_device_bound
+            bound, _ = size_of(t.data_ptr(), t.numel(), spans, stream, linked)
             out = torch.empty(max(bound, 1), dtype=torch.uint8, device=t.device)
         elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8
                   and out.is_contiguous()):
             raise ValueError("out must be a contiguous CUDA uint8 tensor on the frames' device")
         n, jobs = decode_frames_device(t.data_ptr(), t.numel(), spans, out.data_ptr(), out.numel(),
-                                       stream, linked)
+                                       stream, linked, exact)
     return out[:n], jobs
 
 

@@ -552,7 +552,50 @@ int lz4ada_decode_frames_device_opt(const void *d_in, int64_t in_len,
                                     lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
                                     void *d_out, int64_t out_cap, int64_t *out_len, void *stream);
 
+/* ------------------------------ exact decoded sizes, and a decode that fits */
+/*
+ * The bound above counts every block at its slot capacity: 255 times its
+ * payload, or the frame's block maximum.  The exact sizes cost one parse and
+ * no output traffic: pass 1 of the index decoder
+ * records the output bytes of every 32 payload bytes, a kernel adds them up
+ * per block (k_block_sizes; a block pass 1 declines is walked by the wave,
+ * a stored one is its payload), another per frame (k_frame_sizes).  One more
+ * host synchronisation on `stream` per call: the per-frame size records.
+ *
+ * lz4ada_frames_device_sizes: per job status and reason as
+ * lz4ada_frames_device_bound_opt gives them, and also LZ4ADA_EXACT_PATH with
+ * LZ4ADA_DEVFRAME_BLOCK (a block's sequence chain is malformed, a block
+ * decodes to more than its slot capacity, a linked frame's middle block is
+ * short) or LZ4ADA_DEVFRAME_SIZE (the sizes do not add up to the declared
+ * content size).  out_len is the exact decoded length of an accepted frame
+ * (0 for a skippable one); out_off and consumed are 0.  *total is their sum:
+ * an out_cap that suffices for the decode with LZ4ADA_FRAMES_EXACT, and its
+ * *out_len when every frame is committed.  A size is a statement about the
+ * sequence chain alone: a frame whose offsets or checksums are bad has a size
+ * here and fails in the decode.  flags: LZ4ADA_FRAMES_LINKED as elsewhere.
+ *
+ * LZ4ADA_FRAMES_EXACT in the flags of lz4ada_decode_frames_device_opt: the
+ * same stage runs first; out_cap below *total is LZ4ADA_TOO_LITTLE_MEMORY with
+ * *out_len = the total and d_out untouched; a frame the stage fails is
+ * rejected with its reason and takes no slot; the passes are split and the
+ * library's scratch is sized by the slots the sizes need (each block's size
+ * rounded up to 256), not by the capacities.  Results are those of the call
+ * without the flag.  (A frame whose capacities alone exceed LZ4ADA_BATCH_BYTES
+ * keeps LZ4ADA_BATCH_OVER_BUDGET: the walk judges that before any size is
+ * known.)
+ */
+#define LZ4ADA_FRAMES_EXACT 2u /* flags: lay the passes out by the exact sizes */
+int lz4ada_frames_device_sizes(const void *d_in, int64_t in_len,
+                               lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
+                               int64_t *total, void *stream);
+
 /* Test-only, in the spirit of lz4ada_index_table_debug. */
+/* The size rule on the host (block_decoded_size, the serial statement that
+ * k_block_sizes is tested against): the decoded length of the block payload
+ * at block[0 .. n), stored or compressed, or -1 when its sequence chain is
+ * one Decompress_Full_Block (lz4ada.adb:716-788) raises on; offsets are not
+ * judged.  Host only, no HIP call. */
+int64_t lz4ada_block_size_host(const uint8_t *block, int64_t n, int stored);
 /* The walk on the host: verdict as return value (LZ4ADA_DEVFRAME_* 0..4), info
  * and descs as lz4ada_frame_index lays them out (descs may be NULL; at most
  * desc_cap are written, info->nblocks counts them all).  info is complete
