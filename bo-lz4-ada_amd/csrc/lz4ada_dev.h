@@ -76,6 +76,40 @@ __device__ __forceinline__ int32_t wave_incl_max(int32_t v)
 	return v;
 }
 
+// Lane `lane`'s v in every lane, as a scalar: one v_readlane_b32 into an
+// SGPR, where __shfl(v, lane) is a ds_bpermute_b32 (an LDS-pipe round trip
+// and an lgkmcnt wait) whose result, and all computed from it, stays in
+// VGPRs.  Two conditions __shfl does not have:
+//  * lane must be wave-uniform (a constant, or computed from ballots and
+//    other scalars);
+//  * the read ignores EXEC: it returns whatever lane `lane`'s register
+//    holds, so every lane it may name must have executed the instruction
+//    that produced v.  In practice: a total or cut position taken right
+//    after a scan every lane runs, in wave-uniform control flow.
+// Anything else -- a per-lane source, a value produced under a divergent
+// branch -- stays a shuffle.
+__device__ __forceinline__ int32_t wave_get(int32_t v, int32_t lane)
+{
+	return __builtin_amdgcn_readlane(v, lane);
+}
+
+// Lane 63's v: the total of an inclusive scan (wave_get's conditions).
+__device__ __forceinline__ int32_t wave_last(int32_t v) { return __builtin_amdgcn_readlane(v, 63); }
+
+// A value every lane holds alike (loaded from a wave-uniform address, say),
+// moved to an SGPR at the point it becomes uniform, so that what is computed
+// from it -- loop bounds, base addresses, compares -- runs on the scalar unit
+// once instead of on the VALU in 64 copies.
+__device__ __forceinline__ int32_t wave_uniform(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v)
+{
+	return uint32_t(__builtin_amdgcn_readfirstlane(int32_t(v)));
+}
+__device__ __forceinline__ uint64_t wave_uniform(uint64_t v)
+{
+	return uint64_t(wave_uniform(uint32_t(v))) | (uint64_t(wave_uniform(uint32_t(v >> 32))) << 32);
+}
+
 // wave_incl_scan on 64-bit sums: a tile of 4 MiB blocks already reaches 2^32
 // bytes.  The two halves move by the same DPP control.
 template <int CTRL, int ROW_MASK, bool BOUND>

@@ -760,8 +760,8 @@ __device__ __forceinline__ void index_block(IdxLds<W>& X, const uint8_t* __restr
 		                                       epos, nst)
 		                    : ein;
 		ISTAMP(I_WALK0);
-		ICOUNT(I_STEPS, __shfl(wave_incl_scan(nst), 63));
-		ICOUNT(I_MAXST, __shfl(wave_incl_max(nst), 63));
+		ICOUNT(I_STEPS, wave_last(wave_incl_scan(nst)));
+		ICOUNT(I_MAXST, wave_last(wave_incl_max(nst)));
 		// this wave's lane-0 entry: the exact one, but for wave 1 its lead-in
 		// guess until wave 0's largest exit is known
 		int32_t e0 = E;
@@ -787,13 +787,13 @@ __device__ __forceinline__ void index_block(IdxLds<W>& X, const uint8_t* __restr
 						err = false;
 					}
 				}
-				ICOUNT(I_STEPS, __shfl(wave_incl_scan(nst), 63));
-				ICOUNT(I_MAXST, __shfl(wave_incl_max(nst), 63));
+				ICOUNT(I_STEPS, wave_last(wave_incl_scan(nst)));
+				ICOUNT(I_MAXST, wave_last(wave_incl_max(nst)));
 			}
 		};
 		converge();
 		if constexpr (W == 2) {
-			const int32_t mx = __shfl(wave_incl_max(y), 63);
+			const int32_t mx = wave_last(wave_incl_max(y));
 			if (tid == 0)
 				X.xa[0] = mx;
 			__syncthreads();
@@ -832,13 +832,13 @@ __device__ __forceinline__ void index_block(IdxLds<W>& X, const uint8_t* __restr
 		// blocks only: a short one costs a few chunks either way).
 		const bool sparse_test = C == 0 && n >= 4 * CHUNK;
 		int32_t used = 0;  // sub-segments holding a sequence start
-		E = __shfl(wave_incl_max(y), 63);
-		starts = __shfl(wave_incl_scan(starts), 63);
+		E = wave_last(wave_incl_max(y));
+		starts = wave_last(wave_incl_scan(starts));
 		if (sparse_test) {
 			if (s < n)
 				for (int k = 0; k < NSUB; ++k)
 					used += X.rbm[tid][k] ? 1 : 0;
-			used = __shfl(wave_incl_scan(used), 63);
+			used = wave_last(wave_incl_scan(used));
 		}
 		if constexpr (W == 2) {  // the chunk's totals over both waves
 			if (lane == 0) {
@@ -1531,9 +1531,9 @@ __device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX
 	{
 		const int32_t np0 = ring_piece_count(off[0], ml[0]), np1 = ring_piece_count(off[1], ml[1]);
 		const int32_t inc0 = wave_incl_scan(np0);
-		const int32_t tot0 = __shfl(inc0, 63);
+		const int32_t tot0 = wave_last(inc0);
 		const int32_t inc1 = tot0 + wave_incl_scan(np1);
-		tot = __shfl(inc1, 63);
+		tot = wave_last(inc1);
 		auto pack = [&](int32_t md, int32_t of, int32_t m, int32_t excl) -> uint64_t {
 			return uint64_t(uint16_t(md - o_batch)) | (uint64_t(uint16_t(of)) << 16) |
 			       (uint64_t(uint16_t(m)) << 32) | (uint64_t(uint16_t(excl)) << 48);
@@ -1572,7 +1572,7 @@ __device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX
 		// back a source that only starts after it)
 		const int32_t pe = act ? pe_ : INT32_MAX, ps = act ? pd : INT32_MAX;
 		int32_t fj1 = 64, fj2 = -1;  // the chunk's pieces that write this one's source (none)
-		if (!__all(!act || s_hi <= __shfl(ps, 0))) {
+		if (!__all(!act || s_hi <= wave_get(ps, 0))) {
 			int32_t j1 = 0, c2 = 0;
 #pragma unroll
 			for (int st = 32; st >= 1; st >>= 1) {
@@ -1846,6 +1846,22 @@ __device__ __forceinline__ void put_status(lz4ada_block_status& st, int32_t code
 	st.out_len = code == DS_OK ? uint32_t(len) : 0u;
 }
 
+// Block b's descriptor (b wave-uniform) in SGPRs.  It is one per wave, but
+// pass 2 loads it with a vector load (the kernel may have stored to HBM
+// before, which rules a scalar load out), and from VGPRs every bound, base
+// address and cursor of the batch loop computed from it would run on the
+// VALU in 64 copies.
+__device__ __forceinline__ lz4ada_block_desc wave_desc(const lz4ada_block_desc* __restrict__ desc, uint32_t b)
+{
+	lz4ada_block_desc d = desc[b];
+	d.in_off = wave_uniform(d.in_off);
+	d.in_len = wave_uniform(d.in_len);
+	d.flags = wave_uniform(d.flags);
+	d.out_off = wave_uniform(d.out_off);
+	d.out_cap = wave_uniform(d.out_cap);
+	return d;
+}
+
 // One block.  hist: output bytes right before this block's slot that its
 // matches may read -- 0 for independent blocks; in a linked frame, the
 // earlier blocks' output, contiguous when every one of them is full.
@@ -1870,9 +1886,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
                                                 const bool D1E = false)
 {
 	const int32_t lane = int32_t(lane_id());
-	const lz4ada_block_desc d = desc[b];
+	const lz4ada_block_desc d = wave_desc(desc, b);
 	out_len = 0;
-	if (status[b].code != DS_OK)
+	if (wave_uniform(int32_t(status[b].code)) != DS_OK)
 		return DS_RETRY;  // pass 1 declined it
 	cg8* in = gptr(frame) + d.in_off;
 	g8* ob = gptr(out) + d.out_off;
@@ -2011,7 +2027,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				break;
 			}
 			// oversized: all 64 sub-segments straight to HBM
-			const int32_t total = __shfl(incl, 63);
+			const int32_t total = wave_last(incl);
 			if (o_batch + total > cap) {
 				bad = true;
 				break;
@@ -2039,7 +2055,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			continue;
 		}
 
-		const int32_t o_end = o_batch + __shfl(incl, m - 1);
+		const int32_t o_end = o_batch + wave_get(incl, m - 1);
 		if (o_end > cap) {
 			bad = true;
 			break;
@@ -2053,7 +2069,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				D.cst[e++] = uint16_t(rel + __builtin_ctz(bm));
 		}
 		wave_lds_fence();
-		const int32_t N = __shfl(incl_s, m - 1);
+		const int32_t N = wave_get(incl_s, m - 1);
 		// HBM holds every byte below align_down(o_batch, 16) (earlier
 		// flushes); a match reading below glo reads HBM (its source ends
 		// before o_batch - 16), anything newer is in the ring
@@ -2104,7 +2120,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 					const int32_t len = rL[r] + rml[r];
 					const int32_t inc = wave_incl_scan(len);
 					rdst[r] = o_round + inc - len;  // literal destination
-					o_round += __shfl(inc, 63);
+					o_round += wave_last(inc);
 					const int32_t mdst = rdst[r] + rL[r];
 					if (d1p) {
 						// the previous sequence's match: lane - 1, lane 0 the
@@ -2112,8 +2128,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 						int32_t pmd = __shfl(mdst, (lane + 63) & 63), pof = __shfl(roff[r], (lane + 63) & 63),
 						        pml = __shfl(rml[r], (lane + 63) & 63);
 						if (r > 0) {
-							const int32_t a = __shfl(rdst[0] + rL[0], 63), b = __shfl(roff[0], 63),
-							              c = __shfl(rml[0], 63);
+							// (round 0 is full here: lane 63 parsed a sequence)
+							const int32_t a = wave_last(rdst[0] + rL[0]), b = wave_last(roff[0]),
+							              c = wave_last(rml[0]);
 							if (lane == 0) {
 								pmd = a;
 								pof = b;
@@ -2150,9 +2167,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		if (d1p) {  // the batch's last sequence, for the next batch's lane 0
 			const int32_t l = (N - 1) & 63;
 			const bool r1 = N > 64;
-			pmd_b = __shfl(r1 ? rdst[1] + rL[1] : rdst[0] + rL[0], l);
-			pof_b = __shfl(r1 ? roff[1] : roff[0], l);
-			pml_b = __shfl(r1 ? rml[1] : rml[0], l);
+			pmd_b = wave_get(r1 ? rdst[1] + rL[1] : rdst[0] + rL[0], l);
+			pof_b = wave_get(r1 ? roff[1] : roff[0], l);
+			pml_b = wave_get(r1 ? rml[1] : rml[0], l);
 		}
 		ISTAMP(D_WALK2);
 
@@ -2206,9 +2223,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			static_assert(RMAX == 2, "HBM piece dealing pairs two rounds");
 			if (__any(nc[0] > 0 || nc[1] > 0)) {
 				const int32_t inc0 = wave_incl_scan(nc[0]);
-				const int32_t tot0 = __shfl(inc0, 63);
+				const int32_t tot0 = wave_last(inc0);
 				const int32_t inc1 = tot0 + wave_incl_scan(nc[1]);
-				const int32_t tot = __shfl(inc1, 63);
+				const int32_t tot = wave_last(inc1);
 				rtot[0] = tot0;
 				rtot[1] = tot - tot0;
 				rfirst[0] = 64;
@@ -2287,9 +2304,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			const int32_t nc1 = rL[1] > 16 ? (rL[1] - 1) >> 4 : 0;
 			if (__any(nc0 > 0 || nc1 > 0)) {
 				const int32_t inc0 = wave_incl_scan(nc0);
-				const int32_t tot0 = __shfl(inc0, 63);
+				const int32_t tot0 = wave_last(inc0);
 				const int32_t inc1 = tot0 + wave_incl_scan(nc1);
-				const int32_t tot = __shfl(inc1, 63);
+				const int32_t tot = wave_last(inc1);
 				auto pack = [&](int32_t lit, int32_t dst, int32_t L, int32_t excl) -> uint64_t {
 					return uint64_t(uint16_t(lit - base)) | (uint64_t(uint16_t(dst - o_batch)) << 16) |
 					       (uint64_t(uint16_t(L)) << 32) | (uint64_t(uint16_t(excl)) << 48);
@@ -2425,8 +2442,8 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			ICOUNT(D_ROUNDS, st);
 #ifdef LZ4ADA_IDX_STAMPS
 			{
-				const int32_t tot = __shfl(wave_incl_scan(ring_piece_count(oring[0], lring[0]) +
-				                                          ring_piece_count(oring[1], lring[1])), 63);
+				const int32_t tot = wave_last(wave_incl_scan(ring_piece_count(oring[0], lring[0]) +
+				                                             ring_piece_count(oring[1], lring[1])));
 				ICOUNT(D_RCHUNKS, (tot + 63) >> 6);
 				ICOUNT(D_ROVF_B, tot > 64);
 				ICOUNT(D_ROVF_P, max(tot - 64, 0));
@@ -2466,7 +2483,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 	d1 = __any(d1);
 	deep = __any(deep);
 	if (ZL)
-		hcnt = __shfl(wave_incl_scan(hcnt), 63);
+		hcnt = wave_last(wave_incl_scan(hcnt));
 	if (!bad && lane == 0 && (o_batch & 15))  // last partial unit
 		gstore_n(ob + (o_batch & ~15), *reinterpret_cast<const u32x4*>(&D.oring[(o_batch & ~15) & OMASK]),
 		         o_batch & 15);
@@ -2773,7 +2790,7 @@ __device__ __forceinline__ PpCut pp_cut(const PpLds2& L, int32_t k0, int32_t nsu
 	c.m = __popcll(__ballot(incl <= OW && incl_s <= MAXSEQ));
 	c.over = c.m == 0;
 	c.m = c.over ? 64 : c.m;
-	c.bytes = __shfl(incl, c.m - 1);
+	c.bytes = wave_get(incl, c.m - 1);
 	return c;
 }
 
@@ -2807,7 +2824,7 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 {
 	const int32_t tid = int32_t(threadIdx.x), w = tid >> 6, lane = tid & 63;
 	WP2 V{ L, w };
-	const lz4ada_block_desc d = desc[b];
+	const lz4ada_block_desc d = wave_desc(desc, b);
 	cg8* in = gptr(frame) + d.in_off;
 	g8* ob = gptr(out) + d.out_off;
 	const int32_t n = int32_t(d.in_len);
@@ -2968,7 +2985,7 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 				for (; bm; bm &= bm - 1)
 					L.cst[w][e++] = uint16_t(rel + __builtin_ctz(bm));
 			}
-			N = __shfl(incl_s, cb.m - 1);
+			N = wave_get(incl_s, cb.m - 1);
 		}
 		wave_lds_fence();
 		const int32_t gl = glo & ~127;  // HBM pieces end in whole lines below this
@@ -3016,7 +3033,7 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 					const int32_t len = rL[r] + rml[r];
 					const int32_t inc = wave_incl_scan(len);
 					rdst[r] = o_round + inc - len;
-					o_round += __shfl(inc, 63);
+					o_round += wave_last(inc);
 					const int32_t mdst = rdst[r] + rL[r];
 					if (rml[r] > 0) {
 						if (roff[r] > mdst)
@@ -3070,9 +3087,9 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 			}
 			if (__any(nc[0] > 0 || nc[1] > 0)) {
 				const int32_t inc0 = wave_incl_scan(nc[0]);
-				const int32_t tot0 = __shfl(inc0, 63);
+				const int32_t tot0 = wave_last(inc0);
 				const int32_t inc1 = tot0 + wave_incl_scan(nc[1]);
-				const int32_t tot = __shfl(inc1, 63);
+				const int32_t tot = wave_last(inc1);
 				rtot[0] = tot0;
 				rtot[1] = tot - tot0;
 				rfirst[0] = 64;
@@ -3109,9 +3126,9 @@ __device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __
 			const int32_t nc1 = rL[1] > 16 ? (rL[1] - 1) >> 4 : 0;
 			if (__any(nc0 > 0 || nc1 > 0)) {
 				const int32_t inc0 = wave_incl_scan(nc0);
-				const int32_t tot0 = __shfl(inc0, 63);
+				const int32_t tot0 = wave_last(inc0);
 				const int32_t inc1 = tot0 + wave_incl_scan(nc1);
-				const int32_t tot = __shfl(inc1, 63);
+				const int32_t tot = wave_last(inc1);
 				auto pack = [&](int32_t lit, int32_t dst, int32_t Lx, int32_t excl) -> uint64_t {
 					return uint64_t(uint16_t(lit - base)) | (uint64_t(uint16_t(dst - ob0)) << 16) |
 					       (uint64_t(uint16_t(Lx)) << 32) | (uint64_t(uint16_t(excl)) << 48);
