@@ -28,32 +28,6 @@ namespace {
 
 static_assert(WALK_LONE_MAX_IN == LONE_MAX_IN, "the walk states the lone-block rule a second time");
 
-// The jobs in rising in_off, indexed on the device.  The device arrays live
-// in this thread's SC_FRAME scratch (a device pass stages nothing there).
-struct Index {
-	std::vector<uint32_t> order;     // sorted position -> job
-	std::vector<FrameWalkRec> walk;  // by sorted position
-	std::vector<FrameSpan> span;     // by sorted position
-	FrameSpan* d_span = nullptr;
-	FrameWalkRec* d_walk = nullptr;
-	uint64_t *d_first = nullptr, *d_slot = nullptr;  // n + 1 entries each
-	bool take_linked = false;                        // LZ4ADA_FRAMES_LINKED, and its cap
-	uint64_t linked_max = 0;
-	bool linked(size_t k) const { return (walk[k].flags & FRAME_LINKED) != 0; }
-	bool taken(size_t k) const { return walk[k].verdict == LZ4ADA_BATCH_OK; }
-	bool skippable(size_t k) const { return walk[k].format == LZ4ADA_FORMAT_SKIPPABLE; }
-	// The sizes stage (size_jobs), when it ran: every frame's
-	// exact and tight bytes, and on the device (this thread's SC_SIZES scratch)
-	// the walk records with the tight slots, every frame's first block among
-	// the block sizes, and the block sizes of the whole call.
-	bool sized = false;
-	std::vector<FrameSizeRec> size;  // by sorted position
-	FrameWalkRec* d_tight = nullptr;
-	uint64_t* d_size_first = nullptr;
-	uint32_t* d_size = nullptr;
-	uint64_t slots(size_t k) const { return sized ? size[k].tight : walk[k].slots; }
-};
-
 // Blocks per chunk of the sizes stage: its descriptors, statuses and index
 // table are temporary, 160 bytes per block (and a quarter of the input for the
 // table, whatever the chunk).  LZ4ADA_SIZES_CHUNK_BLOCKS, read per call,
@@ -65,10 +39,12 @@ constexpr int64_t SIZES_CHUNK_BLOCKS = int64_t(1) << 20;
 	raise(LZ4ADA_ASSERTION_ERROR, std::string(entry) + ": " + what);
 }
 
+}  // namespace
+
 // The argument checks (nothing is launched before they pass), the sort, and
 // the walk of every job's frame with its one host synchronisation.
 void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ada_device_frame_job* jobs,
-                int64_t njobs, uint32_t flags, hipStream_t stream, Index& ix)
+                int64_t njobs, uint32_t flags, hipStream_t stream, FramesIndex& ix)
 {
 	ix.take_linked = (flags & LZ4ADA_FRAMES_LINKED) != 0;
 	ix.linked_max = uint64_t(batch_linked_max());
@@ -127,7 +103,7 @@ void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ad
 
 // What the index alone says about every job, and the bound: what the frames
 // a pass takes can decode to.
-int64_t report_index(const Index& ix, lz4ada_device_frame_job* jobs)
+int64_t report_index(const FramesIndex& ix, lz4ada_device_frame_job* jobs)
 {
 	uint64_t bound = 0;
 	for (size_t k = 0; k < ix.order.size(); ++k) {
@@ -149,7 +125,7 @@ int64_t report_index(const Index& ix, lz4ada_device_frame_job* jobs)
 // passes need stays in SC_SIZES for the call.  One host synchronisation: the
 // per-frame size records.  A frame the sizes fail is no longer taken(), with
 // LZ4ADA_DEVFRAME_BLOCK or _SIZE as its verdict, on the host and on the device.
-void size_jobs(Index& ix, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
+void size_jobs(FramesIndex& ix, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
 {
 	const size_t n = ix.order.size();
 	ix.sized = true;
@@ -224,7 +200,7 @@ void size_jobs(Index& ix, const uint8_t* d_in, uint64_t in_len, hipStream_t stre
 
 // What the sizes stage says about every job: report_index with the exact
 // length of every accepted frame, and their sum.
-int64_t report_sizes(const Index& ix, lz4ada_device_frame_job* jobs)
+int64_t report_sizes(const FramesIndex& ix, lz4ada_device_frame_job* jobs)
 {
 	report_index(ix, jobs);
 	uint64_t total = 0;
@@ -236,9 +212,12 @@ int64_t report_sizes(const Index& ix, lz4ada_device_frame_job* jobs)
 	return int64_t(total);
 }
 
+namespace {
+
 // Room on the device for a pass over the sorted jobs [lo, hi), their blocks as
 // k_frames_scan counts them: a frame the index did not take rides without any.
-void reserve_pass(PassArrays& a, const Index& ix, size_t lo, size_t hi, uint64_t slots, uint64_t in_len)
+void reserve_pass(PassArrays& a, const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots,
+                  uint64_t in_len)
 {
 	std::vector<PassFrame> frames;
 	for (size_t k = lo; k < hi; ++k)
@@ -249,7 +228,7 @@ void reserve_pass(PassArrays& a, const Index& ix, size_t lo, size_t hi, uint64_t
 
 // The scan and the fill over the sorted jobs [lo, hi): descriptors and frame
 // records of a pass, on the device.
-void fill_pass(const Index& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassArrays& m,
+void fill_pass(const FramesIndex& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassArrays& m,
                hipStream_t stream)
 {
 	// sized: the scan adds up the tight slots, the fill lays the nominal ones
@@ -281,9 +260,9 @@ void job_skipped(lz4ada_device_frame_job& j, const FrameWalkRec& w, uint64_t at)
 // One pass over the sorted jobs [lo, hi) (`slots` slot bytes): their bytes go
 // to d_out from *base on, which then moves past them.  The jobs are sorted and
 // their frames disjoint, and in_len covers every block, as decode_pass asks.
-void run_device_pass(const Index& ix, size_t lo, size_t hi, uint64_t slots, const uint8_t* d_in, uint64_t in_len,
-                     lz4ada_device_frame_job* jobs, uint8_t* d_out, uint64_t* base, uint64_t hash_max,
-                     hipStream_t stream)
+void run_device_pass(const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots, const uint8_t* d_in,
+                     uint64_t in_len, lz4ada_device_frame_job* jobs, uint8_t* d_out, uint64_t* base,
+                     uint64_t hash_max, hipStream_t stream)
 {
 	PassArrays m;
 	reserve_pass(m, ix, lo, hi, slots, in_len);
@@ -370,7 +349,7 @@ int lz4ada_frames_device_bound_opt(const void* d_in, int64_t in_len, lz4ada_devi
 	*bound = 0;
 	batch_stats() = lz4ada_batch_stats{};
 	return guarded(nullptr, [&] {
-		Index ix;
+		FramesIndex ix;
 		index_jobs("lz4ada_frames_device_bound", d_in, in_len, jobs, njobs, flags,
 		           static_cast<hipStream_t>(stream), ix);
 		*bound = report_index(ix, jobs);
@@ -384,7 +363,7 @@ int lz4ada_frames_device_sizes(const void* d_in, int64_t in_len, lz4ada_device_f
 	batch_stats() = lz4ada_batch_stats{};
 	return guarded(nullptr, [&] {
 		hipStream_t s = static_cast<hipStream_t>(stream);
-		Index ix;
+		FramesIndex ix;
 		index_jobs("lz4ada_frames_device_sizes", d_in, in_len, jobs, njobs, flags, s, ix);
 		size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
 		*total = report_sizes(ix, jobs);
@@ -412,7 +391,7 @@ int lz4ada_decode_frames_device_opt(const void* d_in, int64_t in_len, lz4ada_dev
 	set_last_path(0);
 	return guarded(nullptr, [&] {
 		hipStream_t s = static_cast<hipStream_t>(stream);
-		Index ix;
+		FramesIndex ix;
 		index_jobs("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, flags, s, ix);
 		// LZ4ADA_FRAMES_EXACT: the sizes stage, then the frames it passed laid
 		// out by their sizes; what suffices is their sum, not the bound
@@ -466,7 +445,7 @@ int lz4ada_frames_index_device_debug(const void* d_in, int64_t in_len, const lz4
 {
 	return guarded(nullptr, [&] {
 		hipStream_t s = static_cast<hipStream_t>(stream);
-		Index ix;
+		FramesIndex ix;
 		index_jobs("lz4ada_frames_index_device_debug", d_in, in_len, jobs, njobs, batch_env_flags(), s, ix);
 		const size_t n = ix.order.size();
 		uint64_t nb = 0;

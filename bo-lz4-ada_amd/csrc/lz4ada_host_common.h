@@ -10,7 +10,9 @@
 // lz4ada_bulk_linked.cpp (the linked-frame bulk path), lz4ada_bulk_frames.cpp
 // (many frames in one device pass), lz4ada_bulk_frames_device.cpp (the same
 // pass from device memory to device memory), lz4ada_frames_pass.cpp (the
-// device half of that pass, which both share).  lz4ada_multi.cpp
+// device half of that pass, which both share), lz4ada_bulk_ranges.cpp (the
+// seek index over device-resident frames and the ranged decode, which begins
+// with the device engine's index and sizes stages).  lz4ada_multi.cpp
 // (the multi-GPU entry) keeps a per-device cache of its own and includes
 // only lz4ada_internal.h.
 //
@@ -492,6 +494,47 @@ void decode_pass(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, uint
 enum FrameVerdict { FV_GOOD = LZ4ADA_DEVFRAME_OK, FV_BLOCK = LZ4ADA_DEVFRAME_BLOCK, FV_SIZE = LZ4ADA_DEVFRAME_SIZE,
 	            FV_CHECKSUM = LZ4ADA_DEVFRAME_CHECKSUM, FV_HOST_HASH };
 FrameVerdict frame_verdict(const FrameRec& r, uint32_t declared, bool* gpu_hashed);
+
+// ------------------------------- frames indexed where they lie, on the device
+
+// The jobs of a device call in rising in_off, indexed on the device
+// (lz4ada_bulk_frames_device.cpp; the seek index of lz4ada_bulk_ranges.cpp is
+// built from one).  The device arrays live in this thread's SC_FRAME scratch
+// (a device pass stages nothing there).
+struct FramesIndex {
+	std::vector<uint32_t> order;     // sorted position -> job
+	std::vector<FrameWalkRec> walk;  // by sorted position
+	std::vector<FrameSpan> span;     // by sorted position
+	FrameSpan* d_span = nullptr;
+	FrameWalkRec* d_walk = nullptr;
+	uint64_t *d_first = nullptr, *d_slot = nullptr;  // n + 1 entries each
+	bool take_linked = false;                        // LZ4ADA_FRAMES_LINKED, and its cap
+	uint64_t linked_max = 0;
+	bool linked(size_t k) const { return (walk[k].flags & FRAME_LINKED) != 0; }
+	bool taken(size_t k) const { return walk[k].verdict == LZ4ADA_BATCH_OK; }
+	bool skippable(size_t k) const { return walk[k].format == LZ4ADA_FORMAT_SKIPPABLE; }
+	// The sizes stage (size_jobs), when it ran: every frame's
+	// exact and tight bytes, and on the device (this thread's SC_SIZES scratch)
+	// the walk records with the tight slots, every frame's first block among
+	// the block sizes, and the block sizes of the whole call.
+	bool sized = false;
+	std::vector<FrameSizeRec> size;  // by sorted position
+	FrameWalkRec* d_tight = nullptr;
+	uint64_t* d_size_first = nullptr;
+	uint32_t* d_size = nullptr;
+	uint64_t slots(size_t k) const { return sized ? size[k].tight : walk[k].slots; }
+};
+// The two stages and what each says about every job (bodies and comments in
+// lz4ada_bulk_frames_device.cpp).  index_jobs: the argument checks, the sort
+// and the walk, one host synchronisation; `entry` names the caller in a
+// misuse's text.  size_jobs: the exact sizes, one more.  report_index /
+// report_sizes: status, reason and (sizes) out_len of every job; they return
+// the bound / the total.
+void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ada_device_frame_job* jobs,
+                int64_t njobs, uint32_t flags, hipStream_t stream, FramesIndex& ix);
+void size_jobs(FramesIndex& ix, const uint8_t* d_in, uint64_t in_len, hipStream_t stream);
+int64_t report_index(const FramesIndex& ix, lz4ada_device_frame_job* jobs);
+int64_t report_sizes(const FramesIndex& ix, lz4ada_device_frame_job* jobs);
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

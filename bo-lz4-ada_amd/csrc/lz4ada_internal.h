@@ -1,6 +1,7 @@
 // lz4ada_internal.h -- what the host units (lz4ada_host_common.h/.cpp,
 // lz4ada_facade.cpp, lz4ada_bulk.cpp, lz4ada_bulk_linked.cpp,
-// lz4ada_bulk_frames.cpp, lz4ada_bulk_frames_device.cpp, lz4ada_multi.cpp)
+// lz4ada_bulk_frames.cpp, lz4ada_bulk_frames_device.cpp, lz4ada_bulk_ranges.cpp,
+// lz4ada_multi.cpp)
 // share with the gfx950 kernel files (lz4ada_*.hip): the device status codes
 // and the launchers' declarations.  Not part of the public C-ABI.
 #pragma once
@@ -429,5 +430,72 @@ hipError_t launch_frame_sizes(FrameWalkRec* d_walk, const uint64_t* d_first, uin
 hipError_t launch_frames_refit(const FrameWalkRec* d_tight, const uint64_t* d_first, const uint64_t* d_slot,
                                const uint64_t* d_size_first, const uint32_t* d_size, uint32_t nframes,
                                lz4ada_block_desc* d_desc, hipStream_t stream);
+
+// ---- seek index and ranged decode (lz4ada_ranges.hip) ----
+// The device arrays of a seek index over nframes frames in rising in_off, as
+// the kernels see them.  first: n + 1 entries, frame k's blocks are
+// [first[k], first[k + 1]) among desc (a frame the index did not accept holds
+// none).  start / slotp: frame k's nb + 1 entries begin at first[k] + k: the
+// decoded offset at which each block starts and the frame's size, and the same
+// prefix over round256(size), the blocks' tight slots.
+struct SeekView {
+	const lz4ada_block_desc* desc;
+	const uint64_t* first;
+	const uint64_t* start;
+	const uint64_t* slotp;
+	uint32_t nframes;
+};
+// One range with bytes to deliver, as the host hands it to the kernels.
+struct RangeRec {
+	uint32_t frame, pad;  // sorted position of its frame
+	uint64_t off, want;   // decoded bytes [off, off + want) of it, clipped: want > 0
+	uint64_t out_off;     // where they go in d_out
+	uint64_t tile0;       // its first tile among the gather's, counted over the call
+};
+// What k_ranges_select found for it, and k_ranges_verdict after the decode.
+struct RangeSel {
+	uint32_t first, count;      // the blocks it touches, frame-relative
+	uint64_t slot_lo, slot_hi;  // slotp at first and at first + count
+	int32_t fail;               // first failing block among them (frame-relative), -1: none
+	int32_t pad;
+};
+// Bytes of a range that one workgroup of k_ranges_gather copies.
+constexpr uint64_t GATHER_TILE = 16384;
+// One wave per frame: start / slotp of SeekView from the sizes stage's arrays
+// (d_size_first[k]: frame k's first block among d_size).  d_first: the scan
+// over the final verdicts, n + 1 entries.  Writes first[k] + k .. + nb per frame.
+hipError_t launch_block_starts(const uint64_t* d_first, const uint64_t* d_size_first, const uint32_t* d_size,
+                               uint32_t nframes, uint64_t* d_start, uint64_t* d_slotp, hipStream_t stream);
+// One wave per range.  d_sel not null: every range's RangeSel (fail -1).
+// d_mark not null: mark[b - span_lo] = 1 + round256(size) / 256 for every block
+// b the range touches inside [span_lo, span_lo + span_n) (the same value from
+// every writer).  Reads the index alone.
+hipError_t launch_ranges_select(const SeekView& v, const RangeRec* d_ranges, uint32_t nranges, RangeSel* d_sel,
+                                uint32_t* d_mark, uint64_t span_lo, uint32_t span_n, hipStream_t stream);
+// One workgroup: d_cnt[i] / d_slot[i] get the marked blocks / their slot bytes
+// before span block i, entry span_n the totals.
+hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint32_t* d_cnt, uint64_t* d_slot,
+                              hipStream_t stream);
+// One lane per span block: a marked block's descriptor goes to d_desc[d_cnt[i]]
+// with out_off = d_slot[i] and out_cap = its exact size.  Writes no descriptor
+// at or past nsel and places no block past slots (an empty one instead).
+hipError_t launch_ranges_fill(const SeekView& v, const uint32_t* d_mark, const uint32_t* d_cnt,
+                              const uint64_t* d_slot, uint64_t span_lo, uint32_t span_n, uint32_t nsel,
+                              uint64_t slots, lz4ada_block_desc* d_desc, hipStream_t stream);
+// One wave per range, after the decode: d_sel[i].fail = the first block the
+// range touches whose status is non-zero, whose length is not its size or
+// whose block checksum differs.
+hipError_t launch_ranges_verdict(const SeekView& v, const RangeRec* d_ranges, uint32_t nranges, RangeSel* d_sel,
+                                 const uint32_t* d_cnt, uint64_t span_lo, uint32_t span_n,
+                                 const lz4ada_block_desc* d_desc, const lz4ada_block_status* d_status,
+                                 uint32_t nsel, hipStream_t stream);
+// One workgroup per GATHER_TILE bytes of a range (tiles tile_lo .. tile_lo +
+// ntiles of the call, which are those of d_ranges[0 .. nranges)): the range's
+// bytes from the blocks' slots to d_out + out_off.  Reads d_slots inside
+// [0, slots) and writes inside [out_off, out_off + want) only.
+hipError_t launch_ranges_gather(const SeekView& v, const RangeRec* d_ranges, uint32_t nranges,
+                                const RangeSel* d_sel, uint64_t tile_lo, uint32_t ntiles, const uint32_t* d_mark,
+                                const uint64_t* d_slot, uint64_t span_lo, uint32_t span_n, const uint8_t* d_slots,
+                                uint64_t slots, uint8_t* d_out, hipStream_t stream);
 
 }  // namespace lz4ada

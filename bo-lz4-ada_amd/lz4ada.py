@@ -193,6 +193,13 @@ class DeviceFrameJob(ctypes.Structure):
                 ("status", ctypes.c_int32), ("reason", ctypes.c_int32)]
 
 
+class FrameRange(ctypes.Structure):
+    """One range of decode_ranges_device: decoded bytes [off, off + len) of job."""
+    _fields_ = [("job", ctypes.c_int64), ("off", ctypes.c_int64), ("len", ctypes.c_int64),
+                ("out_off", ctypes.c_int64), ("out_len", ctypes.c_int64),
+                ("status", ctypes.c_int32), ("reason", ctypes.c_int32)]
+
+
 # DeviceFrameJob.reason: 1..4 are the BATCH_* reasons
 DEVFRAME_OK, DEVFRAME_BLOCK, DEVFRAME_SIZE, DEVFRAME_CHECKSUM = 0, 5, 6, 7
 EXACT_PATH = 9  # DeviceFrameJob.status of a frame the device pass did not decode
@@ -209,6 +216,7 @@ FRAMES_LINKED = 1
 FRAMES_EXACT = 2
 
 _P = ctypes.POINTER
+_len = len  # range_blocks_host has a parameter named len, as the C-ABI has
 _sig = {
     "lz4ada_stream_index": ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                              ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
@@ -233,6 +241,14 @@ _sig = {
                                    ctypes.c_int),
     "lz4ada_frames_device_sizes": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _pi64, _vp], ctypes.c_int),
     "lz4ada_block_size_host": ([_vp, _i64, ctypes.c_int], _i64),
+    "lz4ada_seek_index_build": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_seek_index_free": ([_vp], None),
+    "lz4ada_seek_index_bytes": ([_vp], _i64),
+    "lz4ada_decode_ranges_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_range_blocks_host": ([_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp], ctypes.c_int),
+    "lz4ada_seek_index_debug": ([_vp, _i64, ctypes.POINTER(ctypes.c_int32), _pi64, _vp, _i64, _vp],
+                                ctypes.c_int),
+    "lz4ada_ranges_select_debug": ([_vp, _vp, _i64, _pi64, _pi64, _pi64, _vp], ctypes.c_int),
     "lz4ada_batch_linked_max": ([], ctypes.c_int64),
     "lz4ada_decode_idx_frames_debug": ([_vp, ctypes.c_uint64, _vp, _i64, _pi64, _vp, _i64, _vp, _vp, _vp],
                                        ctypes.c_int),
@@ -707,6 +723,168 @@ def decode_frames_tensor(t, spans, out=None, linked=False, exact=False):
         n, jobs = decode_frames_device(t.data_ptr(), t.numel(), spans, out.data_ptr(), out.numel(),
                                        stream, linked, exact)
     return out[:n], jobs
+
+
+# ----------------------------- seek index and ranged decode
+
+class SeekIndex:
+    """A seek index over frames lying in device memory: per accepted frame its
+    block descriptors and the decoded offset at which each block starts, in
+    device memory the index owns (it survives release_device_cache()).  Built
+    once and never changed, so any number of threads may decode ranges through
+    it.  .jobs: the DeviceFrameJob array of the build (status, reason, out_len
+    = exact decoded size, as frames_device_sizes gives them); .in_len: the
+    input it was built over.  free() releases it; also a context manager."""
+
+    def __init__(self, ptr, jobs, njobs, in_len):
+        self._ptr, self.jobs, self.njobs, self.in_len = ptr, jobs, njobs, in_len
+
+    @classmethod
+    def build(cls, d_in: int, in_len: int, spans, stream: int = 0, flags: int = 0):
+        """Index the frames at spans [(in_off, in_len)] of the device buffer
+        d_in (raw pointer).  Linked frames are refused (BATCH_LINKED)."""
+        jobs = _device_jobs(spans)
+        ptr = _vp()
+        _check(_lib.lz4ada_seek_index_build(d_in, in_len, jobs, len(spans), flags, ctypes.byref(ptr), stream),
+               _thread_error())
+        return cls(ptr.value, jobs, len(spans), in_len)
+
+    @classmethod
+    def build_tensor(cls, t, spans):
+        """build for a CUDA torch.uint8 tensor, on torch's current stream."""
+        _frames_tensor(t)
+        with torch.cuda.device(t.device):
+            return cls.build(t.data_ptr(), t.numel(), spans, torch.cuda.current_stream().cuda_stream)
+
+    @property
+    def device_bytes(self) -> int:
+        return int(_lib.lz4ada_seek_index_bytes(self._ptr))
+
+    def free(self):
+        if self._ptr:
+            _lib.lz4ada_seek_index_free(self._ptr)
+        self._ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _frames_tensor(t):
+    if torch is None:
+        raise RuntimeError("this call needs torch")
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise ValueError("the frames must be a contiguous CUDA uint8 tensor")
+
+
+def _frame_ranges(ranges):
+    """[(job, off, len)] or a FrameRange array -> (FrameRange array, count)."""
+    if isinstance(ranges, ctypes.Array):
+        return ranges, len(ranges)
+    arr = (FrameRange * max(len(ranges), 1))()
+    for r, (job, off, n) in zip(arr, ranges):
+        r.job, r.off, r.len = job, off, n
+    return arr, len(ranges)
+
+
+def decode_ranges_device(idx: SeekIndex, d_in: int, in_len: int, ranges, d_out: int, out_cap: int,
+                         stream: int = 0):
+    """Decode the ranges [(job, off, len)] of the decoded frames of idx: only
+    the blocks they touch are decoded, and their bytes land back to back in
+    the device buffer d_out in the order given -> (bytes written, the
+    FrameRange array: out_off, out_len, status, reason).  A range is clipped to
+    its frame; one with status EXACT_PATH was not delivered (its frame was not
+    accepted, or a block it touches failed: DEVFRAME_BLOCK).  TooLittleMemory
+    carries the clipped total as .bound (out_cap = 0 asks for it)."""
+    arr, n = _frame_ranges(ranges)
+    got = _i64()
+    st = _lib.lz4ada_decode_ranges_device(idx._ptr, d_in, in_len, arr, n, d_out, out_cap, ctypes.byref(got),
+                                          stream)
+    if st:
+        exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
+        exc.bound = got.value
+        raise exc
+    return got.value, arr
+
+
+def decode_ranges_tensor(idx: SeekIndex, t, ranges, out=None):
+    """decode_ranges_device for the CUDA torch.uint8 tensor the index was
+    built over, on torch's current stream -> (the ranges' bytes as a uint8
+    tensor on the same device, the FrameRange array).  out: a uint8 tensor
+    there to decode into; by default the clipped total is allocated."""
+    _frames_tensor(t)
+    arr, n = _frame_ranges(ranges)
+    with torch.cuda.device(t.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        if out is None:
+            try:
+                total, _ = decode_ranges_device(idx, t.data_ptr(), t.numel(), arr, None, 0, stream)
+            except TooLittleMemory as e:
+                total = e.bound
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=t.device)
+        elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8
+                  and out.is_contiguous()):
+            raise ValueError("out must be a contiguous CUDA uint8 tensor on the frames' device")
+        got, arr = decode_ranges_device(idx, t.data_ptr(), t.numel(), arr, out.data_ptr(), out.numel(), stream)
+    return out[:got], arr
+
+
+def range_blocks_host_many(starts, offs, lens):
+    """Test-only: the block search on the host for many ranges of one frame.
+    starts: the frame's exclusive prefix sum of block sizes and its size
+    (nblocks + 1 entries) -> ctypes int64 arrays (first touched block, count,
+    clipped length), one entry per range."""
+    def i64(seq, kind=_i64):  # a list, or a numpy array of 64-bit integers
+        if hasattr(seq, "tobytes"):
+            return (kind * max(_len(seq), 1)).from_buffer_copy(seq.tobytes().ljust(8, b"\0"))
+        return (kind * max(_len(seq), 1))(*seq)
+    nb, n = _len(starts) - 1, _len(offs)
+    a, off, ln = i64(starts, ctypes.c_uint64), i64(offs), i64(lens)
+    first, count, want = (_i64 * max(n, 1))(), (_i64 * max(n, 1))(), (_i64 * max(n, 1))()
+    _check(_lib.lz4ada_range_blocks_host(a, nb, off, ln, n, first, count, want),
+           "range_blocks_host: a NULL or negative argument")
+    return first, count, want
+
+
+def range_blocks_host(starts, off: int, len: int):
+    """Test-only: range_blocks_host_many for one range -> (first touched
+    block, count, clipped length)."""
+    first, count, want = range_blocks_host_many(starts, [off], [len])
+    return first[0], count[0], want[0]
+
+
+def seek_index_debug(idx: SeekIndex, stream: int = 0):
+    """Test-only: per job of the index (reason, start[] copied to the host: the
+    decoded offset at which each block starts, and the frame's size; [0] for a
+    frame the index did not accept)."""
+    res = []
+    for job in range(idx.njobs):
+        reason, nb = ctypes.c_int32(), _i64()
+        _check(_lib.lz4ada_seek_index_debug(idx._ptr, job, ctypes.byref(reason), ctypes.byref(nb), None, 0,
+                                            stream), _thread_error())
+        start = (ctypes.c_uint64 * (nb.value + 1))()
+        _check(_lib.lz4ada_seek_index_debug(idx._ptr, job, ctypes.byref(reason), ctypes.byref(nb), start,
+                                            nb.value + 1, stream), _thread_error())
+        res.append((reason.value, list(start)))
+    return res
+
+
+def ranges_select_debug(idx: SeekIndex, ranges, stream: int = 0):
+    """Test-only: the selection alone -> ([(first block, count)] per range,
+    blocks marked once shared ones count once)."""
+    arr, n = _frame_ranges(ranges)
+    first, count, marked = (_i64 * max(n, 1))(), (_i64 * max(n, 1))(), _i64()
+    _check(_lib.lz4ada_ranges_select_debug(idx._ptr, arr, n, first, count, ctypes.byref(marked), stream),
+           _thread_error())
+    return [(first[i], count[i]) for i in range(n)], marked.value
 
 
 def explain_frame(t_or_bytes, job):

@@ -616,6 +616,122 @@ int lz4ada_frames_index_device_debug(const void *d_in, int64_t in_len,
                                      int32_t *verdict, int64_t *nblocks,
                                      lz4ada_block_desc *descs, int64_t desc_cap, void *stream);
 
+/* --------------------- seek index and ranged decode of device-resident frames */
+/*
+ * The exact sizes above are one prefix sum away from a seek table.  A seek
+ * index keeps, for a set of frames lying in device memory, every accepted
+ * frame's block descriptors and the decoded offset at which each block starts
+ * (DESIGN.md section 14): 48 bytes of device memory per block, which the index
+ * owns -- it is not the per-thread scratch and survives
+ * lz4ada_release_device_cache().  A ranged decode then takes many byte ranges
+ * of the *decoded* frames in one call, decodes only the blocks those ranges
+ * touch, and lays the requested bytes back to back in the caller's device
+ * buffer.  There is no reference twin: like lz4ada_decode_frames_device it
+ * replaces a loop the caller would otherwise write.
+ *
+ * lz4ada_seek_index_build: the index and sizes stages over jobs, as
+ * lz4ada_frames_device_sizes runs them -- every job gets the same status,
+ * reason and out_len = exact decoded size -- and then the table is kept.
+ * flags must be 0: a linked frame is refused with LZ4ADA_BATCH_LINKED, since a
+ * block of a linked frame needs every block before it.  njobs == 0 builds an
+ * empty index without a device call.  On failure *idx is NULL.  Synchronous
+ * on stream; host synchronisations: the two of lz4ada_frames_device_sizes and
+ * one that ends the build, after which the index never changes.  Any number of
+ * threads may then run ranged calls on it at once, each in its own thread's
+ * scratch.  lz4ada_seek_index_free(NULL) is a no-op;
+ * lz4ada_seek_index_bytes is the device memory held (no HIP call).
+ *
+ * lz4ada_decode_ranges_device.  d_in / in_len must be the input the index was
+ * built over: another in_len is LZ4ADA_ASSERTION_ERROR; the pointer may differ
+ * (descriptors are relative to d_in).  If the bytes changed since the build,
+ * blocks fail or decode to other bytes; nothing is read outside
+ * [d_in, d_in + in_len) and nothing written outside the library's scratch and
+ * the ranges' own bytes, since every bound comes from the index and in_len.
+ *  - A range is clipped to its frame: want = max(0, min(off + len, size) - off).
+ *    off at or past the end, len == 0, a skippable frame and an empty frame
+ *    give LZ4ADA_OK with out_len == 0.
+ *  - The ranges' bytes lie in d_out back to back in the order of the ranges
+ *    array: out_off of range i is the sum of want over the ranges before it.
+ *    Ranges may overlap, repeat and come in any order of job and offset.
+ *    *out_len is the sum of all want.  out_cap below it is
+ *    LZ4ADA_TOO_LITTLE_MEMORY with *out_len = that sum and d_out untouched, so
+ *    out_cap = 0 is how a caller learns the clipped total.  Nothing at or
+ *    beyond *out_len is ever written.
+ *  - A range of a frame the index did not accept: LZ4ADA_EXACT_PATH, the
+ *    frame's reason, out_len 0; it takes no room.
+ *  - A range one of whose touched blocks fails -- a non-zero decode status (a
+ *    match that reaches before the block start included), a decoded length
+ *    unequal to its indexed size, a declared block checksum unequal to the
+ *    computed one: LZ4ADA_EXACT_PATH / LZ4ADA_DEVFRAME_BLOCK with out_len 0.
+ *    The range keeps its place: the want bytes at out_off are unspecified and
+ *    nothing outside them is touched.  A failing block costs only the ranges
+ *    that touch it.  A block is touched when it shares a byte with the clipped
+ *    range; an empty block between two touched ones rides along.
+ *  - A single range whose blocks' slots (their sizes rounded up to 256) exceed
+ *    LZ4ADA_BATCH_BYTES: LZ4ADA_EXACT_PATH / LZ4ADA_BATCH_OVER_BUDGET, likewise
+ *    in place.
+ *  - What a delivered range asserts: the whole frame's header and size words
+ *    indexed; every block's sequence chain adds up, and to the declared
+ *    content size if there is one (the sizes stage); the touched blocks
+ *    decoded and their block checksums hold.  It does NOT assert the content
+ *    checksum, nor the offsets and block checksums of blocks it did not touch.
+ *    So a frame that lz4ada_decode_frames_device rejects with
+ *    LZ4ADA_DEVFRAME_CHECKSUM, or whose corrupt block lies outside the range,
+ *    still serves the range.  That is the point of random access.
+ *  - API misuse, LZ4ADA_ASSERTION_ERROR before any device call: NULL idx,
+ *    ranges, out_len or d_in; a job outside [0, njobs); a negative off or len;
+ *    off + len overflowing; nranges < 0; and flags != 0 in the build.
+ *    nranges == 0 is a call that worked and launches nothing.
+ *  - Synchronous on stream.  Host synchronisations: one for the selection
+ *    records and one per pass; a call whose ranges are all empty makes none.
+ *    lz4ada_last_batch_stats().passes counts the passes (the other counters
+ *    stay 0); lz4ada_last_path() is LZ4ADA_PATH_BATCH | LZ4ADA_PATH_INDEPENDENT
+ *    when a range was delivered through a pass.
+ */
+typedef struct lz4ada_seek_index lz4ada_seek_index;
+
+int lz4ada_seek_index_build(const void *d_in, int64_t in_len,
+                            lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
+                            lz4ada_seek_index **idx, void *stream);
+void lz4ada_seek_index_free(lz4ada_seek_index *idx);
+int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index *idx);
+
+typedef struct {
+	int64_t job;              /* in: which of the njobs frames the index was built over */
+	int64_t off, len;         /* in: decoded bytes [off, off + len) of that frame */
+	int64_t out_off, out_len; /* out: where its bytes lie in d_out, and how many */
+	int32_t status;           /* out: LZ4ADA_OK, or LZ4ADA_EXACT_PATH: not delivered */
+	int32_t reason;           /* out: LZ4ADA_DEVFRAME_* */
+} lz4ada_frame_range;
+
+int lz4ada_decode_ranges_device(const lz4ada_seek_index *idx, const void *d_in, int64_t in_len,
+                                lz4ada_frame_range *ranges, int64_t nranges,
+                                void *d_out, int64_t out_cap, int64_t *out_len, void *stream);
+
+/* Test-only, as above. */
+/* The block search on the host (range_blocks, lz4ada_range_blocks.h, the
+ * statement k_ranges_select runs), for n ranges of one frame: start[0 ..
+ * nblocks] is the frame's exclusive prefix sum of block sizes and its size.
+ * first[i] / count[i]: the blocks the clipped range i touches (count 0: none);
+ * want[i]: its clipped length.  LZ4ADA_ASSERTION_ERROR on a NULL or negative
+ * argument.  Host only, no HIP call. */
+int lz4ada_range_blocks_host(const uint64_t *start, int64_t nblocks, const int64_t *off,
+                             const int64_t *len, int64_t n, int64_t *first, int64_t *count,
+                             int64_t *want);
+/* One job of an index: its reason (0: accepted), its block count, and, when
+ * start is not NULL, its start[0 .. nblocks] copied to the host (start_cap
+ * entries of room). */
+int lz4ada_seek_index_debug(const lz4ada_seek_index *idx, int64_t job, int32_t *reason,
+                            int64_t *nblocks, uint64_t *start, int64_t start_cap, void *stream);
+/* k_ranges_select and the marks of one pass over all the ranges, nothing
+ * decoded: per range its first touched block and their count (frame-relative;
+ * 0, 0 for an empty range), and *marked: the blocks marked once shared ones
+ * count once.  ranges gets out_off, out_len, status and reason as the index
+ * alone gives them. */
+int lz4ada_ranges_select_debug(const lz4ada_seek_index *idx, lz4ada_frame_range *ranges,
+                               int64_t nranges, int64_t *first, int64_t *count, int64_t *marked,
+                               void *stream);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
