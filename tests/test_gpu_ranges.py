@@ -6,7 +6,7 @@ and destination; block counts and range counts around the scan steps; full
 blocks through the real decoders and what the selection marks; a failing block
 that costs only the ranges that touch it; what a range does not assert; linked
 frames; the output bound; the byte budget; reuse, threads' scratch and the
-index's lifetime."""
+index's lifetime; an index used after a block of its input changed."""
 import random
 import struct
 
@@ -15,6 +15,7 @@ import torch
 
 import lz4ada
 import lz4frame
+from _lz4build import encode
 from conftest import read_vector
 from test_block_size_cpu import MALFORMED, oracle_block_lengths
 from test_gpu_frames_batch import bad_frame, three_blocks
@@ -397,3 +398,81 @@ def test_reuse_and_lifetime():
     idx.free()
     lz4ada.release_device_cache()
     assert idle() == before
+
+
+# ------------------------------------------- an index used after its input changed
+
+CHANGES = ("same_size", "larger", "smaller", "malformed")
+
+
+def changed_block(variant, seed=0):
+    """Block 2 of the changed frame and its variants, all of one payload length:
+    600 literals, a match, five last literals (1,000 bytes decoded; the match
+    40 bytes longer or shorter: the same number of extension bytes); the
+    malformed one is a valid sequence, then MALFORMED's literals one past the
+    end.  -> (payload, decoded bytes or None)."""
+    rng = random.Random(1400 + seed)
+    if variant == "malformed":
+        head = encode([(rng.randbytes(600 - len(MALFORMED["literals_one_past_the_end"]) + 6), 3, 395)])[0]
+        return head + MALFORMED["literals_one_past_the_end"], None
+    ml = dict(larger=435, smaller=355).get(variant, 395)
+    return encode([(rng.randbytes(600), 3 if variant is None else 7, ml)], rng.randbytes(5))
+
+
+@pytest.fixture(scope="module")
+def changed():
+    """A frame of four blocks without block checksums between two other
+    frames, indexed once: (data, spans, tensor, index, the original bytes per
+    frame, block 2's payload position, the variants, block 2's extent in the
+    frame's plaintext).  The parts a CPU can check are checked here."""
+    blocks = [(*lz4ada.gen_block(1, 830 + k, n), False) for k, n in enumerate(FOUR)]
+    blocks[2] = (*changed_block(None), False)
+    frame = lz4frame.build_frame(blocks, 64 << 10)[0]
+    info, descs = lz4ada.frame_index(frame)
+    assert info.nblocks == 4 and not any(d.flags & lz4ada.BLOCK_HAS_CKSUM for d in descs[:4])
+    variants = {v: changed_block(v, 1 + k) for k, v in enumerate(CHANGES)}
+    n = len(blocks[2][0])
+    assert descs[2].in_len == n and all(len(p) == n for p, _ in variants.values())
+    assert lz4ada.block_size_host(blocks[2][0]) == 1000 == len(blocks[2][1])
+    assert [lz4ada.block_size_host(variants[v][0]) for v in CHANGES] == [1000, 1040, 960, -1]
+    assert variants["same_size"][1] != blocks[2][1]
+    frames = [full_frame(lz4ada.GEN_MIXED, 930), frame, four_blocks(None)[0]]
+    raws = [oracle_alone(f) for f in frames]
+    assert raws[1] == b"".join(b[1] for b in blocks)
+    same = frame[:descs[2].in_off] + variants["same_size"][0] + frame[descs[2].in_off + n:]
+    lo, hi = sum(FOUR[:2]), sum(FOUR[:2]) + 1000
+    assert oracle_alone(same) == raws[1][:lo] + variants["same_size"][1] + raws[1][hi:]
+    data, spans = layout(frames)
+    t = to_device(data)
+    idx = lz4ada.SeekIndex.build_tensor(t, spans)
+    assert [(j.status, j.reason, j.out_len) for j in idx.jobs[:3]] == [(0, 0, len(r)) for r in raws]
+    yield data, spans, t, idx, raws, spans[1][0] + descs[2].in_off, variants, (lo, hi)
+    idx.free()
+
+
+@pytest.mark.parametrize("variant", CHANGES)
+def test_an_index_used_after_its_input_changed(changed, variant):
+    """DESIGN.md §14, "If the input changed since the build": a block whose
+    bytes changed under the index decodes to other bytes inside its own slot
+    or fails its size, and costs only the ranges that touch it."""
+    data, spans, t, idx, raws, at, variants, (lo, hi) = changed
+    payload, new = variants[variant]
+    t2 = t.clone()
+    t2[at:at + len(payload)] = to_device(payload)
+    assert to_host(t2) == data[:at] + payload + data[at + len(payload):]
+    raws = list(raws)
+    size = len(raws[1])
+    mine = [(0, lo), (lo - 1, 1), (lo - 1, 2), (lo, 1), (hi - 1, 1), (hi - 1, 2), (hi, 1), (hi, 1 << 30),
+            (0, size), (10, 5), (lo + 3, 2), (0, lo + 1), (lo, hi - lo), (hi, size - hi)]
+    touching = {k for k, (off, n) in enumerate(mine) if off < hi and off + n > lo}
+    assert len(touching) == 8 and len(mine) - len(touching) == 6
+    ranges = [(0, 0, len(raws[0]) + 1), (0, 65535, 2)] + [(1, off, n) for off, n in mine] + \
+        [(2, 0, 1 << 20), (2, 2999, 2), (0, len(raws[0]) - 1, 1)]
+    failed = set()
+    if variant == "same_size":
+        raws[1] = raws[1][:lo] + new + raws[1][hi:]
+    else:
+        failed = {2 + k for k in touching}
+    out, arr, _ = ranged(idx, t2, ranges)
+    check(out, arr, ranges, raws, failed=failed)
+    assert passes() == 1 and lz4ada.last_path() == OK_PATH
