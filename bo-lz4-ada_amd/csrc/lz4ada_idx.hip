@@ -1323,9 +1323,15 @@ __device__ __forceinline__ void pattern_lut_init(uint32_t* plut)
 // The phase-0 period-off (1..15) pattern of the 16 source bytes v (the
 // first off of them valid): make_pattern16's value in one LDS read, two
 // selects and four v_perm_b32 instead of its 64-bit shift network.
-__device__ __forceinline__ u32x4 pattern_perm(u32x4 v, int32_t off, const uint32_t* plut)
+// (pattern_sel is the LDS read: it needs off alone, so a caller issues it
+// beside the source read and applies it once both have arrived)
+__device__ __forceinline__ u32x4 pattern_sel(int32_t off, const uint32_t* plut)
 {
-	const u32x4 sel = *reinterpret_cast<const u32x4*>(plut + 4 * off);
+	return *reinterpret_cast<const u32x4*>(plut + 4 * off);
+}
+
+__device__ __forceinline__ u32x4 pattern_perm(u32x4 v, int32_t off, u32x4 sel)
+{
 	const uint32_t h2 = off <= 8 ? v.y : v.z, h3 = off <= 11 ? v.y : v.w;
 	u32x4 o;
 	o.x = __builtin_amdgcn_perm(v.y, v.x, sel.x);
@@ -1351,7 +1357,7 @@ __device__ __forceinline__ void ring_match(LD& L, int32_t dst, int32_t off, int3
 	const bool pat = off < 16 && off < len;
 	if (pat) {
 		if constexpr (lds_fast<LD>::value) {
-			pv = pattern_perm(pv, off, plut_of(L));
+			pv = pattern_perm(pv, off, pattern_sel(off, plut_of(L)));
 			stp = pattern_step(off);
 		} else {
 			make_pattern16(uint64_t(pv.x) | (uint64_t(pv.y) << 32), uint64_t(pv.z) | (uint64_t(pv.w) << 32),
@@ -1573,9 +1579,13 @@ __device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX
 		const int32_t pe = act ? pe_ : INT32_MAX, ps = act ? pd : INT32_MAX;
 		int32_t fj1 = 64, fj2 = -1;  // the chunk's pieces that write this one's source (none)
 		if (!__all(!act || s_hi <= wave_get(ps, 0))) {
-			int32_t j1 = 0, c2 = 0;
+			// the first probe's source is lane 31 in every lane: a readlane, not
+			// an LDS shuffle.  wave_get's conditions hold: 31 is a constant, and
+			// every lane computed pe and ps above (the chunk loop and this
+			// branch are wave-uniform)
+			int32_t j1 = wave_get(pe, 31) <= s_lo ? 32 : 0, c2 = wave_get(ps, 31) < s_hi ? 32 : 0;
 #pragma unroll
-			for (int st = 32; st >= 1; st >>= 1) {
+			for (int st = 16; st >= 1; st >>= 1) {
 				if (__shfl(pe, j1 + st - 1) <= s_lo)
 					j1 += st;
 				if (__shfl(ps, c2 + st - 1) < s_hi)
@@ -1626,27 +1636,46 @@ __device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX
 			const int32_t xcut2 = int32_t((sb >> 21) & 31u), xn2 = int32_t((sb >> 26) & 31u);
 			const int32_t xa2 = xa1 + 16 - (int32_t(sb) < 0 ? xoff : 0);
 			const int32_t xpd2 = two ? xpd + int32_t(sa >> 28) + 1 : xpd;
+			// Reads first.  Unit 1's read, unit 2's and the pattern selectors'
+			// (their address needs only xoff) are issued here, before the
+			// step's first store, and consumed below, so they are in flight
+			// together and each use waits for its own (a counted lgkmcnt)
+			// instead of paying a round trip of its own behind the store
+			// before it.  The rule that makes it valid: no read of a ready
+			// lane meets a store of this step.  Not its own piece's --
+			// neither unit reads its own match's output (ring_match's rule)
+			// -- and not another ready lane's: dep covers the sources of both
+			// units, so two lanes ready in one step never read each other's
+			// stores of that step.  The compiler cannot prove that two oring
+			// addresses differ and would keep unit 2's read behind unit 1's
+			// store; hence the order here.  (The wrap-merge reads of an
+			// overlap stay where they are used: issued up here under their
+			// predicates they measured slower, and so did unit 2's early
+			// read in the branching form below, which keeps the plain
+			// order)
 			if constexpr (lds_fast<LD>::value) {
 				// every lane loads and stores (a lane not ready stores
 				// nothing: its stores go to the junk bytes)
 				u32x4 v = oload16(D, xa1);
+				u32x4 w = oload16(D, xa2);
+				const u32x4 sel = pattern_sel(opat ? xoff : 0, plut_of(D));
 				if (ready && xcut1 < 16)
 					v = merge_at(v, oload16(D, xa1 - xoff), xcut1);
 				if (ready && opat)
-					v = pattern_perm(v, xoff, plut_of(D));
+					v = pattern_perm(v, xoff, sel);
+				// unit 2's bytes are assembled before unit 1's store is issued:
+				// placed after it, their wait would count the store as well
+				asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w)::"memory");
 				// the first unit of two: 16 whole bytes in one store (one wrapping
 				// the ring's end takes ostore's byte loop)
 				if (__builtin_expect(!__any(ready && two && uint32_t(xpd) + 16u > omask_of(D) + 1), 1))
 					__builtin_memcpy((ready && two) ? &oring_of(D)[xpd] : junk_of(D), &v, 16);
 				else
 					ostore(D, xpd, v, (ready && two) ? 16 : 0);
-				if (__any(ready && ld2)) {
-					u32x4 w = oload16(D, xa2);
-					if (ready && ld2 && xcut2 < 16)
-						w = merge_at(w, oload16(D, xa2 - xoff), xcut2);
-					if (ld2)
-						v = w;
-				}
+				if (ready && ld2 && xcut2 < 16)
+					w = merge_at(w, oload16(D, xa2 - xoff), xcut2);
+				if (ld2)
+					v = w;
 				ostore(D, xpd2, v, ready ? xn2 : 0);
 			} else if (ready) {
 				u32x4 v = oload16(D, xa1);
@@ -1705,9 +1734,12 @@ __device__ __forceinline__ int32_t ring_lanes(LD& D, int32_t mdst, int32_t off, 
 	// a step of their own
 	bool near = ml > 0;
 	const int32_t mend = mdst + ml;
-	int32_t j1 = 0, c2 = 0;
+	// the first probe by readlane (lane 31 in every lane).  wave_get's
+	// conditions hold: every lane holds its mdst and mend -- the caller
+	// computes them for all 64 lanes, in wave-uniform control flow
+	int32_t j1 = wave_get(mend, 31) <= src ? 32 : 0, c2 = wave_get(mdst, 31) < dep_end ? 32 : 0;
 #pragma unroll
-	for (int st = 32; st >= 1; st >>= 1) {
+	for (int st = 16; st >= 1; st >>= 1) {
 		if (__shfl(mend, j1 + st - 1) <= src)
 			j1 += st;
 		if (__shfl(mdst, c2 + st - 1) < dep_end)
