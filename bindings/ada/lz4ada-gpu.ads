@@ -124,6 +124,48 @@ package LZ4Ada.GPU is
 				Linked:        in     Boolean := False;
 				Exact:         in     Boolean := False);
 
+	-- lz4ada_frames_device_bound_dict / lz4ada_decode_frames_device_dict:
+	-- the two device calls with one dictionary in device memory that every
+	-- frame of the call shares (lz4ada_device_dict of include/lz4ada_hip.h;
+	-- the LZ4 specification's semantics, no reference twin).  The thin
+	-- imports: Jobs is the address of a Device_Frame_Jobs' first element,
+	-- Flags are Frames_Linked / Frames_Exact (1, 2), Dict may be null (the
+	-- call is then the one without a dictionary), the result is the status
+	-- of the call (0, or 5: Too_Little_Memory with Out_Len the bound, or 6:
+	-- misuse).  A job with Status 9 and Reason 8 (LZ4ADA_DEVFRAME_DICT)
+	-- names another dictionary id than Dict_Id (compared only with
+	-- Dict_Check_Id in Flags).  For a frame answered with Status 9,
+	-- Decode_Frame_Dict_Host decodes its host bytes against the dictionary's
+	-- host bytes: plain host code, statuses 1, 2, 3 and 5 as the exceptions
+	-- of LZ4Ada.
+	Dict_Check_Id: constant Interfaces.Unsigned_32 := 1;
+	type Device_Dict is record
+		D_Dict:   System.Address;
+		Dict_Len: Interfaces.Integer_64;
+		Dict_Id:  Interfaces.Unsigned_32;
+		Flags:    Interfaces.Unsigned_32;
+	end record;
+	pragma Convention(C, Device_Dict);
+	function Frames_Device_Bound_Dict(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Flags: Interfaces.Unsigned_32; Dict: access constant Device_Dict;
+			Bound: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, Frames_Device_Bound_Dict, "lz4ada_frames_device_bound_dict");
+	function Decode_Frames_Device_Dict(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Flags: Interfaces.Unsigned_32; Dict: access constant Device_Dict;
+			D_Out: System.Address; Out_Cap: Interfaces.Integer_64;
+			Out_Len: access Interfaces.Integer_64; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, Decode_Frames_Device_Dict, "lz4ada_decode_frames_device_dict");
+	function Decode_Frame_Dict_Host(Frame: System.Address; Len: Interfaces.Integer_64;
+			Dict: System.Address; Dict_Len: Interfaces.Integer_64;
+			Out_Buf: System.Address; Out_Cap: Interfaces.Integer_64;
+			Out_Len, Consumed: access Interfaces.Integer_64)
+			return Interfaces.Integer_32;
+	pragma Import(C, Decode_Frame_Dict_Host, "lz4ada_decode_frame_dict_host");
+
 	-- lz4ada_rccl_version: the RCCL this process bound (22606 = 2.26.6).
 	function RCCL_Version return Interfaces.Integer_32;
 	pragma Import(C, RCCL_Version, "lz4ada_rccl_version");

@@ -16,7 +16,9 @@
 // LZ4ADA_FRAMES_EXACT, and in lz4ada_frames_device_sizes, a sizes stage finds
 // what every accepted frame decodes to without decoding it (lz4ada_sizes.hip,
 // one more D2H of per-frame records per call), and the passes are laid out by
-// those sizes instead of the slot capacities.
+// those sizes instead of the slot capacities.  The _dict calls
+// are the same passes with a gap in front of the slots that need one, filled
+// with the dictionary's tail, and the dictionary decoders.
 #include "lz4ada_block_size.h"
 #include "lz4ada_frame_walk.h"
 #include "lz4ada_host_common.h"
@@ -214,6 +216,95 @@ int64_t report_sizes(const FramesIndex& ix, lz4ada_device_frame_job* jobs)
 
 namespace {
 
+// The dictionary of a _dict call as the passes see it (null: none, the _opt call).
+struct DictCtx {
+	const uint8_t* d_dict;
+	uint64_t len;
+	uint32_t used;  // min(len, DICT_MAX)
+	uint64_t gap;   // dict_gap(used)
+};
+
+// The blocks of sorted job k that get a gap: every block of an independent
+// modern frame, the first of a linked one.
+uint64_t gapped_blocks(const FramesIndex& ix, size_t k)
+{
+	if (!ix.taken(k) || ix.walk[k].format != LZ4ADA_FORMAT_MODERN || ix.walk[k].nblocks == 0)
+		return 0;
+	return ix.linked(k) ? 1 : ix.walk[k].nblocks;
+}
+
+// LZ4ADA_DICT_CHECK_ID: a taken modern frame that names another dictionary id
+// is no longer taken(), with LZ4ADA_DEVFRAME_DICT as its verdict, on the host
+// and on the device.  One host synchronisation: a word per frame.
+void check_dict_ids(FramesIndex& ix, const uint8_t* d_in, uint32_t dict_id, hipStream_t stream)
+{
+	const size_t n = ix.order.size();
+	if (n == 0)
+		return;
+	uint32_t* const d_bad = reinterpret_cast<uint32_t*>(scratch(SC_DICT, n * 4));
+	if (!d_bad)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the dictionary ids");
+	HIP_OK(launch_frames_dictid(d_in, ix.d_span, ix.d_walk, uint32_t(n), dict_id, d_bad, stream));
+	PinBuf& h = scratch_cache().pin;
+	h.reserve(n * 4);
+	HIP_OK(hipMemcpyAsync(h.p, d_bad, n * 4, hipMemcpyDeviceToHost, stream));
+	HIP_OK(hipStreamSynchronize(stream));
+	const uint32_t* bad = reinterpret_cast<const uint32_t*>(h.p);
+	for (size_t k = 0; k < n; ++k)
+		if (bad[k] && ix.taken(k))
+			ix.walk[k].verdict = LZ4ADA_DEVFRAME_DICT;
+}
+
+// A dictionary pass over the sorted jobs [lo, hi), once its descriptors are
+// filled: the gaps (k_frames_dictgap from a word per frame), their bytes
+// (k_dict_fill), and the runs cut again so that legacy frames, which read no
+// dictionary, keep launch_decode_checked while modern ones take the dictionary
+// decoders.  `total`: the pass's slots and gaps, what SC_OUT holds.
+void lay_dict_pass(PassArrays& m, const FramesIndex& ix, size_t lo, size_t hi, uint64_t total, uint64_t in_len,
+                   const DictCtx& dc, PinBuf& h, hipStream_t stream)
+{
+	const size_t kind_b = size_t(m.nf) * 8;
+	uint64_t* const d_kind = reinterpret_cast<uint64_t*>(scratch(SC_DICT, kind_b));
+	if (!d_kind)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's gaps");
+	uint64_t* const kind = reinterpret_cast<uint64_t*>(h.p);
+	uint64_t before = 0;
+	for (size_t k = lo; k < hi; ++k) {
+		const uint64_t g = gapped_blocks(ix, k);
+		kind[k - lo] = (before << 2) | (g == 0 ? DICT_KIND_NONE : ix.linked(k) ? DICT_KIND_LINKED : DICT_KIND_INDEP);
+		before += g;
+	}
+	HIP_OK(hipMemcpyAsync(d_kind, kind, kind_b, hipMemcpyHostToDevice, stream));
+	HIP_OK(launch_frames_dictgap(m.d_rec, m.nf, d_kind, dc.gap, total, m.d_desc, m.nb, stream));
+	HIP_OK(launch_dict_fill(m.d_desc, m.nb, dc.d_dict, dc.len, dc.used, m.d_slots, stream));
+	// the runs: a linked run takes the dictionary as it is; an independent one
+	// is cut where legacy and modern frames meet
+	std::vector<PassRun> runs;
+	for (const PassRun& r : m.runs) {
+		if (r.linked) {
+			runs.push_back(r);
+			runs.back().dict = true;
+			continue;
+		}
+		std::vector<PassFrame> fr;
+		for (uint32_t f = r.f0; f < r.f1; ++f) {
+			const size_t k = lo + f;
+			fr.push_back(PassFrame{ ix.taken(k) ? uint32_t(ix.walk[k].nblocks) : 0u,
+			                        ix.walk[k].format == LZ4ADA_FORMAT_MODERN });
+		}
+		for (PassRun q : pass_runs(fr)) {  // (`linked` there: modern)
+			q.dict = q.linked;
+			q.linked = false;
+			q.b0 += r.b0, q.b1 += r.b0, q.f0 += r.f0, q.f1 += r.f0;
+			runs.push_back(q);
+		}
+	}
+	m.runs = runs;
+	m.dict_used = dc.used;
+	if (!m.d_tab && m.nb && !(m.d_tab = scratch(SC_TAB, index_table_bytes(in_len, m.nb))))
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's sequence index");
+}
+
 // Room on the device for a pass over the sorted jobs [lo, hi), their blocks as
 // k_frames_scan counts them: a frame the index did not take rides without any.
 void reserve_pass(PassArrays& a, const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots,
@@ -257,19 +348,22 @@ void job_skipped(lz4ada_device_frame_job& j, const FrameWalkRec& w, uint64_t at)
 	add_last_path(LZ4ADA_PATH_BATCH);
 }
 
-// One pass over the sorted jobs [lo, hi) (`slots` slot bytes): their bytes go
-// to d_out from *base on, which then moves past them.  The jobs are sorted and
-// their frames disjoint, and in_len covers every block, as decode_pass asks.
+// One pass over the sorted jobs [lo, hi) (`slots` slot bytes, a dictionary
+// pass's gaps included): their bytes go to d_out from *base on, which then
+// moves past them.  The jobs are sorted and their frames disjoint, and in_len
+// covers every block, as decode_pass asks.
 void run_device_pass(const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots, const uint8_t* d_in,
                      uint64_t in_len, lz4ada_device_frame_job* jobs, uint8_t* d_out, uint64_t* base,
-                     uint64_t hash_max, hipStream_t stream)
+                     uint64_t hash_max, hipStream_t stream, const DictCtx* dc = nullptr)
 {
 	PassArrays m;
 	reserve_pass(m, ix, lo, hi, slots, in_len);
 	uint8_t* const dst = d_out + *base;
 	fill_pass(ix, lo, hi, d_in, m, stream);
 	PinBuf& h = scratch_cache().pin;  // this thread's small pinned transfers
-	h.reserve(m.rec_b);
+	h.reserve(std::max(m.rec_b, dc ? size_t(m.nf) * 8 : size_t(0)));
+	if (dc)
+		lay_dict_pass(m, ix, lo, hi, slots, in_len, *dc, h, stream);
 	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p);
 	decode_pass(m, d_in, in_len, dst, hash_max, rec, stream);
 	lz4ada_batch_stats& stats = batch_stats();
@@ -309,6 +403,89 @@ void run_device_pass(const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots
 		add_last_path(LZ4ADA_PATH_BATCH | (ix.linked(k) ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT));
 	}
 	*base += rec[m.nf - 1].out_off + rec[m.nf - 1].out_len;
+}
+
+// API misuse of a _dict call's dictionary, before any launch.
+void check_dict(const char* entry, const lz4ada_device_dict* dict)
+{
+	if (!dict)
+		return;
+	if (dict->dict_len < 0 || (dict->dict_len > 0 && !dict->d_dict))
+		misuse(entry, "dict_len is negative, or d_dict is NULL");
+	if (dict->flags & ~LZ4ADA_DICT_CHECK_ID)
+		misuse(entry, "unknown bits in dict->flags");
+}
+
+// lz4ada_decode_frames_device_opt, and with a dictionary of dict_len > 0 the
+// _dict call: the same index, sizes and passes, the gaps charged against the
+// budget, and every pass laid out and decoded with the dictionary.
+int decode_frames_device(const char* entry, const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs,
+                         int64_t njobs, uint32_t flags, const lz4ada_device_dict* dict, void* d_out,
+                         int64_t out_cap, int64_t* out_len, void* stream)
+{
+	*out_len = 0;
+	batch_stats() = lz4ada_batch_stats{};
+	set_last_path(0);
+	return guarded(nullptr, [&] {
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		check_dict(entry, dict);
+		DictCtx dctx{}, *dc = nullptr;
+		if (dict && dict->dict_len > 0) {
+			dctx.d_dict = static_cast<const uint8_t*>(dict->d_dict);
+			dctx.len = uint64_t(dict->dict_len);
+			dctx.used = uint32_t(std::min<uint64_t>(dctx.len, DICT_MAX));
+			dctx.gap = dict_gap(dctx.used);
+			dc = &dctx;
+		}
+		FramesIndex ix;
+		index_jobs(entry, d_in, in_len, jobs, njobs, flags, s, ix);
+		if (dc && (dict->flags & LZ4ADA_DICT_CHECK_ID))
+			check_dict_ids(ix, static_cast<const uint8_t*>(d_in), dict->dict_id, s);
+		// LZ4ADA_FRAMES_EXACT: the sizes stage, then the frames it passed laid
+		// out by their sizes; what suffices is their sum, not the bound
+		if (flags & LZ4ADA_FRAMES_EXACT)
+			size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
+		const int64_t sizes_total = ix.sized ? report_sizes(ix, jobs) : 0;
+		const int64_t index_bound = report_index(ix, jobs);
+		const int64_t bound = ix.sized ? sizes_total : index_bound;
+		if (out_cap < bound || (bound > 0 && !d_out)) {
+			*out_len = bound;
+			raise(LZ4ADA_TOO_LITTLE_MEMORY, std::string(entry) + ": the output holds" + img(out_cap) +
+			                                        " bytes, the frames may decode to" + img(bound));
+		}
+		const uint64_t budget = uint64_t(batch_budget()), hash_max = uint64_t(batch_hash_max());
+		uint64_t base = 0;
+		const size_t n = ix.order.size();
+		size_t lo = 0;
+		while (lo < n) {
+			// the sorted jobs [lo, hi): as many frames as the budget takes
+			size_t hi = lo;
+			uint64_t acc = 0, nb = 0, real = 0;
+			for (; hi < n; ++hi) {
+				if (!ix.taken(hi))
+					continue;
+				// (a dictionary pass's gaps are scratch like its slots)
+				const uint64_t cost = ix.slots(hi) + (dc ? dc->gap * gapped_blocks(ix, hi) : 0);
+				if ((acc && acc + cost > budget) || nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
+					break;
+				acc += cost;
+				nb += ix.walk[hi].nblocks;
+				real += ix.skippable(hi) ? 0 : 1;
+			}
+			if (hi == lo)  // one frame of 2^31 blocks or more
+				raise(LZ4ADA_CONSTRAINT_ERROR, "a frame holds more blocks than a pass takes");
+			if (real) {
+				run_device_pass(ix, lo, hi, acc, static_cast<const uint8_t*>(d_in), uint64_t(in_len), jobs,
+				                static_cast<uint8_t*>(d_out), &base, hash_max, s, dc);
+			} else {  // nothing but skippable frames, if any: no launch
+				for (size_t k = lo; k < hi; ++k)
+					if (ix.taken(k))
+						job_skipped(jobs[ix.order[k]], ix.walk[k], base);
+			}
+			lo = hi;
+		}
+		*out_len = int64_t(base);
+	});
 }
 
 }  // namespace
@@ -386,57 +563,34 @@ int lz4ada_decode_frames_device_opt(const void* d_in, int64_t in_len, lz4ada_dev
                                     int64_t njobs, uint32_t flags, void* d_out, int64_t out_cap,
                                     int64_t* out_len, void* stream)
 {
-	*out_len = 0;
+	return decode_frames_device("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, flags, nullptr, d_out,
+	                            out_cap, out_len, stream);
+}
+
+int lz4ada_frames_device_bound_dict(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs,
+                                    int64_t njobs, uint32_t flags, const lz4ada_device_dict* dict,
+                                    int64_t* bound, void* stream)
+{
+	*bound = 0;
 	batch_stats() = lz4ada_batch_stats{};
-	set_last_path(0);
 	return guarded(nullptr, [&] {
+		check_dict("lz4ada_frames_device_bound_dict", dict);
 		hipStream_t s = static_cast<hipStream_t>(stream);
 		FramesIndex ix;
-		index_jobs("lz4ada_decode_frames_device", d_in, in_len, jobs, njobs, flags, s, ix);
-		// LZ4ADA_FRAMES_EXACT: the sizes stage, then the frames it passed laid
-		// out by their sizes; what suffices is their sum, not the bound
-		if (flags & LZ4ADA_FRAMES_EXACT)
-			size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
-		const int64_t sizes_total = ix.sized ? report_sizes(ix, jobs) : 0;
-		const int64_t index_bound = report_index(ix, jobs);
-		const int64_t bound = ix.sized ? sizes_total : index_bound;
-		if (out_cap < bound || (bound > 0 && !d_out)) {
-			*out_len = bound;
-			raise(LZ4ADA_TOO_LITTLE_MEMORY, "lz4ada_decode_frames_device: the output holds" + img(out_cap) +
-			                                        " bytes, the frames may decode to" + img(bound));
-		}
-		const uint64_t budget = uint64_t(batch_budget()), hash_max = uint64_t(batch_hash_max());
-		uint64_t base = 0;
-		const size_t n = ix.order.size();
-		size_t lo = 0;
-		while (lo < n) {
-			// the sorted jobs [lo, hi): as many frames as the budget takes
-			size_t hi = lo;
-			uint64_t acc = 0, nb = 0, real = 0;
-			for (; hi < n; ++hi) {
-				if (!ix.taken(hi))
-					continue;
-				if ((acc && acc + ix.slots(hi) > budget) ||
-				    nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
-					break;
-				acc += ix.slots(hi);
-				nb += ix.walk[hi].nblocks;
-				real += ix.skippable(hi) ? 0 : 1;
-			}
-			if (hi == lo)  // one frame of 2^31 blocks or more
-				raise(LZ4ADA_CONSTRAINT_ERROR, "a frame holds more blocks than a pass takes");
-			if (real) {
-				run_device_pass(ix, lo, hi, acc, static_cast<const uint8_t*>(d_in), uint64_t(in_len), jobs,
-				                static_cast<uint8_t*>(d_out), &base, hash_max, s);
-			} else {  // nothing but skippable frames, if any: no launch
-				for (size_t k = lo; k < hi; ++k)
-					if (ix.taken(k))
-						job_skipped(jobs[ix.order[k]], ix.walk[k], base);
-			}
-			lo = hi;
-		}
-		*out_len = int64_t(base);
+		index_jobs("lz4ada_frames_device_bound_dict", d_in, in_len, jobs, njobs, flags, s, ix);
+		if (dict && dict->dict_len > 0 && (dict->flags & LZ4ADA_DICT_CHECK_ID))
+			check_dict_ids(ix, static_cast<const uint8_t*>(d_in), dict->dict_id, s);
+		*bound = report_index(ix, jobs);
 	});
+}
+
+int lz4ada_decode_frames_device_dict(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs,
+                                     int64_t njobs, uint32_t flags, const lz4ada_device_dict* dict, void* d_out,
+                                     int64_t out_cap, int64_t* out_len, void* stream)
+{
+	const bool none = !dict || dict->dict_len == 0;
+	return decode_frames_device(none ? "lz4ada_decode_frames_device" : "lz4ada_decode_frames_device_dict", d_in,
+	                            in_len, jobs, njobs, flags, dict, d_out, out_cap, out_len, stream);
 }
 
 int lz4ada_frames_index_device_debug(const void* d_in, int64_t in_len, const lz4ada_device_frame_job* jobs,

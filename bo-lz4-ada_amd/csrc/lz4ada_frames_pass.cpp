@@ -24,22 +24,32 @@ thread_local lz4ada_batch_stats g_stats{};
 
 // One run's decode launches.  Independent: launch_decode_checked over its
 // blocks.  Linked: the block checksums beside pass 1 over its blocks, one wave
-// per frame (k_decode_idx_frames), then the join.
+// per frame (k_decode_idx_frames), then the join.  A dictionary run (DESIGN.md
+// §15) is the linked arm with the dictionary decoders: one wave per frame
+// (linked) or per block (independent: no launch_decode_checked, whose fallback
+// decoders know no history, so a block pass 1 declines keeps its code).
 void decode_pass_run(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, const PassRun& run,
                      hipStream_t stream)
 {
 	const uint32_t n = run.b1 - run.b0;
 	if (n == 0)
 		return;
-	if (!run.linked) {
+	if (!run.linked && !run.dict) {
 		HIP_OK(launch_decode_checked(d_in, in_len, a.d_desc + run.b0, n, a.d_slots, a.d_st + run.b0, stream));
 		return;
 	}
 	HIP_OK(launch_block_checksums_beside(d_in, a.d_desc + run.b0, n, a.d_st + run.b0, stream));
 	HIP_OK(launch_index(d_in, in_len, a.d_desc + run.b0, n, a.d_tab + size_t(run.b0) * 64, a.d_st + run.b0,
 	                    stream));
-	HIP_OK(launch_decode_idx_frames(d_in, in_len, a.d_desc, a.nb, a.d_tab, a.d_slots, a.d_st, a.d_rec + run.f0,
-	                                run.f1 - run.f0, stream));
+	if (run.dict && run.linked)
+		HIP_OK(launch_decode_idx_frames_dict(d_in, in_len, a.d_desc, a.nb, a.d_tab, a.d_slots, a.d_st,
+		                                     a.d_rec + run.f0, run.f1 - run.f0, a.dict_used, stream));
+	else if (run.dict)
+		HIP_OK(launch_decode_idx_dict(d_in, in_len, a.d_desc + run.b0, n, a.d_tab + size_t(run.b0) * 64, a.d_slots,
+		                              a.d_st + run.b0, a.dict_used, stream));
+	else
+		HIP_OK(launch_decode_idx_frames(d_in, in_len, a.d_desc, a.nb, a.d_tab, a.d_slots, a.d_st,
+		                                a.d_rec + run.f0, run.f1 - run.f0, stream));
 	HIP_OK(join_block_checksums(stream));
 }
 

@@ -392,8 +392,9 @@ inline bool try_reserve(DevBuf<T>& b, size_t count)
 // single-frame decodes of the frames the pass did not find good.
 // SC_SIZES: what the sizes stage of a device call leaves for its passes
 // (lz4ada_bulk_frames_device.cpp).
+// SC_DICT: a dictionary call's small per-frame words.
 enum ScratchRole { SC_FRAME, SC_OUT, SC_COMPACT, SC_X, SC_Y, SC_H, SC_Z, SC_TAB, SC_P, SC_F, SC_LONE, SC_U,
-	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_SIZES, SC_N };
+	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_SIZES, SC_DICT, SC_N };
 struct ScratchCache {
 	DevBuf<uint8_t> b[SC_N];
 	PinBuf pin;  // the linked path's small host transfers (pinned: no staging copy)
@@ -476,6 +477,7 @@ struct PassArrays {
 	uint64_t *d_off = nullptr, *d_loc = nullptr, *d_part = nullptr;
 	uint8_t *d_slots = nullptr, *d_tab = nullptr;
 	std::vector<PassRun> runs;  // pass_runs(frames)
+	uint32_t dict_used = 0;     // a dictionary pass: the history of a BLOCK_DICT block (runs with .dict)
 	const char* reserve(const std::vector<PassFrame>& frames, uint64_t slots, uint64_t in_len);
 };
 // The device half of a pass, once a.d_desc and a.d_rec are queued on stream:

@@ -2710,6 +2710,76 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 		status[r].code = DS_RETRY;
 }
 
+// Dictionary frames.  A block whose descriptor carries
+// BLOCK_DICT has `G` bytes in front of its slot whose last dict_used are the
+// dictionary's last (k_dict_fill, lz4ada_dict.hip): to decode_block they are
+// history like a linked frame's earlier output.  The semantics are the LZ4
+// specification's: no quirk-D1 round state, AUX_D1_RISK is ignored.  One
+// caution of decode_block's remains, because the function is shared with the
+// other decoders as it is (a parameter for it changed their code): an
+// oversized batch (batch_global) declines a match that starts before the block
+// with an offset of D1_OFF or more, so such a block fails its frame and the
+// caller's host decode takes it.
+
+// Independent blocks against the dictionary: one wave per block, pass 2 over a
+// table from launch_index over the same descriptors.  A block without
+// BLOCK_DICT (a legacy frame's) reads no history.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_dict(
+        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
+        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
+        lz4ada_block_status* __restrict__ status, uint32_t dict_used)
+{
+	__shared__ DecLds D;
+	if (blockIdx.x >= nblocks)
+		return;
+	const uint32_t fl = wave_uniform(desc[blockIdx.x].flags);
+	int32_t len;
+	decode_block(D, frame, frame_len, desc, blockIdx.x, tab_all, out, status,
+	                   (fl & BLOCK_DICT) ? int64_t(dict_used) : 0, len);
+}
+
+// k_decode_idx_frames with the dictionary before each linked frame's first
+// block: hist starts at dict_used when that block carries BLOCK_DICT and grows
+// block by block as there.  Same clamps: no status and no slot outside the
+// frame's blocks is written whatever the record says.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_frames_dict(
+        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
+        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
+        lz4ada_block_status* __restrict__ status, const FrameRec* __restrict__ frames, uint32_t nframes,
+        uint32_t dict_used)
+{
+	__shared__ DecLds D;
+	if (blockIdx.x >= nframes)
+		return;
+	const uint32_t flags = frames[blockIdx.x].flags;
+	if (!(flags & FRAME_LINKED))
+		return;
+	const uint32_t first = min(frames[blockIdx.x].first, nblocks);
+	const uint32_t bend = first + min(frames[blockIdx.x].nblocks, nblocks - first);
+	if (first >= bend)
+		return;
+	int64_t hist = (wave_uniform(desc[first].flags) & BLOCK_DICT) ? int64_t(dict_used) : 0;
+	uint32_t stop = bend;  // the first block left DS_RETRY
+	for (uint32_t b = first; b < bend; ++b) {
+		int32_t len;
+		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status, hist, len);
+		vm_wait();  // the next block reads this output as history
+		__syncthreads();
+		if (code != DS_OK) {
+			stop = b + 1;  // (its own status is non-zero already)
+			break;
+		}
+		if (b + 1 < bend && (uint32_t(len) != desc[b].out_cap ||
+		                     desc[b + 1].out_off != desc[b].out_off + uint64_t(len))) {
+			stop = b + 1;  // the next block's history would not be contiguous
+			break;
+		}
+		hist += len;
+	}
+	for (uint32_t r = stop + lane_id(); r < bend; r += 64)
+		status[r].code = DS_RETRY;
+}
+
 // ============================================================ pipelined pair
 // k_decode_pp2 (round 5): two waves per block that pipeline consecutive
 // batches instead of splitting each one (k_decode_idx2), for launches of at
@@ -3407,6 +3477,29 @@ hipError_t launch_decode_idx_frames(const uint8_t* d_frame, uint64_t frame_len,
 		return hipSuccess;
 	hipLaunchKernelGGL(idx::k_decode_idx_frames, dim3(nframes), dim3(64), 0, stream, d_frame, frame_len, d_desc,
 	                   nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, d_frames, nframes);
+	return hipGetLastError();
+}
+
+hipError_t launch_decode_idx_dict(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
+                                  uint32_t nblocks, const uint8_t* d_tab, uint8_t* d_out,
+                                  lz4ada_block_status* d_status, uint32_t dict_used, hipStream_t stream)
+{
+	if (nblocks == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(idx::k_decode_idx_dict, dim3(nblocks), dim3(64), 0, stream, d_frame, frame_len, d_desc,
+	                   nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, dict_used);
+	return hipGetLastError();
+}
+
+hipError_t launch_decode_idx_frames_dict(const uint8_t* d_frame, uint64_t frame_len,
+                                         const lz4ada_block_desc* d_desc, uint32_t nblocks, const uint8_t* d_tab,
+                                         uint8_t* d_out, lz4ada_block_status* d_status, const FrameRec* d_frames,
+                                         uint32_t nframes, uint32_t dict_used, hipStream_t stream)
+{
+	if (nframes == 0 || nblocks == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(idx::k_decode_idx_frames_dict, dim3(nframes), dim3(64), 0, stream, d_frame, frame_len,
+	                   d_desc, nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, d_frames, nframes, dict_used);
 	return hipGetLastError();
 }
 

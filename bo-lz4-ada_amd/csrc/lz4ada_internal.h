@@ -431,6 +431,57 @@ hipError_t launch_frames_refit(const FrameWalkRec* d_tight, const uint64_t* d_fi
                                const uint64_t* d_size_first, const uint32_t* d_size, uint32_t nframes,
                                lz4ada_block_desc* d_desc, hipStream_t stream);
 
+// ---- dictionary frames (lz4ada_dict.hip, lz4ada_idx.hip) ----
+// A descriptor flag of a dictionary pass (bit 2: free beside the public flags
+// and the linked path's BLOCK_D1_* bits, which such a pass never sets): the
+// block is *gapped* -- DICT_GAP(dict_used) bytes lie in front of its slot and
+// their last dict_used are the dictionary's last.
+constexpr uint32_t BLOCK_DICT = 4u;
+constexpr uint32_t DICT_MAX = 65536;  // dictionary bytes a block can reach (HISTORY_SIZE)
+// The gap: the dictionary's used bytes, the 32 that decode_block's ring fill
+// may read further back than its history, rounded up to 256 like every slot.
+__host__ __device__ inline uint64_t dict_gap(uint32_t dict_used)
+{
+	return (uint64_t(dict_used) + 32 + 255) & ~uint64_t(255);
+}
+// How the frames of a dictionary pass take gaps, one word per frame, from the
+// host's walk records: kind in the low 2 bits, the gapped blocks before the
+// frame above them.
+constexpr uint32_t DICT_KIND_NONE = 0;    // not modern, or without blocks: its blocks move, none is gapped
+constexpr uint32_t DICT_KIND_LINKED = 1;  // one gap before the frame's first block
+constexpr uint32_t DICT_KIND_INDEP = 2;   // a gap before every block
+// One lane per block, after launch_frames_fill (and _refit): block k of frame f
+// moves up by gap times the gapped blocks before it and including it, and a
+// gapped block gets BLOCK_DICT.  A block that would end past `limit` (the
+// slots and gaps the host reserved) becomes an empty one at 0 instead.
+hipError_t launch_frames_dictgap(const FrameRec* d_rec, uint32_t nframes, const uint64_t* d_kind, uint64_t gap,
+                                 uint64_t limit, lz4ada_block_desc* d_desc, uint32_t nblocks, hipStream_t stream);
+// One workgroup per block: in front of every BLOCK_DICT block's slot, gap bytes
+// whose last dict_used are d_dict[dict_len - dict_used, dict_len) and whose
+// others are zeros.  16-byte stores (out_off is a multiple of 256), loads at
+// any alignment.  Writes inside [out_off - gap, out_off) only, and nothing for
+// a block whose out_off is below gap.
+hipError_t launch_dict_fill(const lz4ada_block_desc* d_desc, uint32_t nblocks, const uint8_t* d_dict,
+                            uint64_t dict_len, uint32_t dict_used, uint8_t* d_slots, hipStream_t stream);
+// One lane per frame (LZ4ADA_DICT_CHECK_ID): a taken modern frame whose FLG bit
+// 0 is set and whose dictionary id is not dict_id gets LZ4ADA_DEVFRAME_DICT as
+// its walk verdict, so that later scans give it no block, and d_bad[i] = 1
+// (else 0).  Reads the 4 id bytes of headers the walk has validated.
+hipError_t launch_frames_dictid(const uint8_t* d_in, const FrameSpan* d_span, FrameWalkRec* d_walk,
+                                uint32_t nframes, uint32_t dict_id, uint32_t* d_bad, hipStream_t stream);
+// k_decode_idx_dict: pass 2 of independent blocks, one wave per block, hist =
+// dict_used for a BLOCK_DICT block; d_tab from a launch_index over the same
+// descriptors.  A block pass 1 declined keeps its DS_RETRY / DS_SPARSE.
+hipError_t launch_decode_idx_dict(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
+                                  uint32_t nblocks, const uint8_t* d_tab, uint8_t* d_out,
+                                  lz4ada_block_status* d_status, uint32_t dict_used, hipStream_t stream);
+// k_decode_idx_frames_dict: launch_decode_idx_frames with hist starting at
+// dict_used and without the quirk-D1 round state.
+hipError_t launch_decode_idx_frames_dict(const uint8_t* d_frame, uint64_t frame_len,
+                                         const lz4ada_block_desc* d_desc, uint32_t nblocks, const uint8_t* d_tab,
+                                         uint8_t* d_out, lz4ada_block_status* d_status, const FrameRec* d_frames,
+                                         uint32_t nframes, uint32_t dict_used, hipStream_t stream);
+
 // ---- seek index and ranged decode (lz4ada_ranges.hip) ----
 // The device arrays of a seek index over nframes frames in rising in_off, as
 // the kernels see them.  first: n + 1 entries, frame k's blocks are

@@ -17,6 +17,7 @@ struct PassFrame {
 struct PassRun {
 	uint32_t b0, b1, f0, f1;
 	bool linked;
+	bool dict = false;  // a dictionary pass's run of modern frames; pass_runs leaves it clear
 };
 
 // The runs in order, tiling the frames and their blocks.  A run ends just

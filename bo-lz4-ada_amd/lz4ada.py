@@ -193,6 +193,14 @@ class DeviceFrameJob(ctypes.Structure):
                 ("status", ctypes.c_int32), ("reason", ctypes.c_int32)]
 
 
+class DeviceDict(ctypes.Structure):
+    """The dictionary of the _dict device calls: the last 65,536 bytes of
+    dict_len bytes of device memory at d_dict; dict_id is compared with a
+    frame's only under DICT_CHECK_ID in flags."""
+    _fields_ = [("d_dict", ctypes.c_void_p), ("dict_len", ctypes.c_int64), ("dict_id", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
 class FrameRange(ctypes.Structure):
     """One range of decode_ranges_device: decoded bytes [off, off + len) of job."""
     _fields_ = [("job", ctypes.c_int64), ("off", ctypes.c_int64), ("len", ctypes.c_int64),
@@ -202,6 +210,8 @@ class FrameRange(ctypes.Structure):
 
 # DeviceFrameJob.reason: 1..4 are the BATCH_* reasons
 DEVFRAME_OK, DEVFRAME_BLOCK, DEVFRAME_SIZE, DEVFRAME_CHECKSUM = 0, 5, 6, 7
+DEVFRAME_DICT = 8  # the frame names another dictionary id (DeviceDict with DICT_CHECK_ID)
+DICT_CHECK_ID = 1
 EXACT_PATH = 9  # DeviceFrameJob.status of a frame the device pass did not decode
 
 BLOCK_STORED = 1
@@ -239,6 +249,10 @@ _sig = {
                                         ctypes.c_int),
     "lz4ada_frame_walk_host_opt": ([_vp, _i64, ctypes.c_uint32, ctypes.POINTER(FrameInfo), _vp, _i64],
                                    ctypes.c_int),
+    "lz4ada_frames_device_bound_dict": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _vp, _pi64, _vp], ctypes.c_int),
+    "lz4ada_decode_frames_device_dict": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _vp, _vp, _i64, _pi64, _vp],
+                                         ctypes.c_int),
+    "lz4ada_decode_frame_dict_host": ([_vp, _i64, _vp, _i64, _vp, _i64, _pi64, _pi64], ctypes.c_int),
     "lz4ada_frames_device_sizes": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _pi64, _vp], ctypes.c_int),
     "lz4ada_block_size_host": ([_vp, _i64, ctypes.c_int], _i64),
     "lz4ada_seek_index_build": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, ctypes.POINTER(_vp), _vp], ctypes.c_int),
@@ -648,12 +662,28 @@ def _device_entry(linked, plain, opt, exact=False):
     return lambda *a: opt(*a[:4], flags, *a[4:])
 
 
-def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0, linked=False):
+def _dict_flags(linked, exact):
+    """The flags a _dict call gets: what _device_entry gives the _opt call."""
+    flags = (FRAMES_LINKED if linked else 0) | (FRAMES_EXACT if exact else 0)
+    if not linked:  # as the plain entry reads it
+        e = os.environ.get("LZ4ADA_BATCH_LINKED", "")
+        flags |= FRAMES_LINKED if e and e[0] != "0" else 0
+    return flags
+
+
+def frames_device_bound(d_in: int, in_len: int, spans, stream: int = 0, linked=False, dict=None):
     """Index the frames at spans [(in_off, in_len)] of the device buffer d_in
     (raw pointer) on the device -> (an out_cap that always suffices, the
-    DeviceFrameJob array with the index's verdict per frame)."""
+    DeviceFrameJob array with the index's verdict per frame).  dict: a
+    DeviceDict (lz4ada_frames_device_bound_dict: with DICT_CHECK_ID a frame
+    naming another id is EXACT_PATH / DEVFRAME_DICT)."""
     jobs = _device_jobs(spans)
     bound = _i64()
+    if dict is not None:
+        _check(_lib.lz4ada_frames_device_bound_dict(d_in, in_len, jobs, len(spans), _dict_flags(linked, False),
+                                                    ctypes.byref(dict), ctypes.byref(bound), stream),
+               _thread_error())
+        return bound.value, jobs
     call = _device_entry(linked, _lib.lz4ada_frames_device_bound, _lib.lz4ada_frames_device_bound_opt)
     _check(call(d_in, in_len, jobs, len(spans), ctypes.byref(bound), stream), _thread_error())
     return bound.value, jobs
@@ -681,19 +711,26 @@ def block_size_host(block, stored=False) -> int:
 
 
 def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0,
-                         linked=False, exact=False):
+                         linked=False, exact=False, dict=None):
     """Decode the frames at spans [(in_off, in_len)] of the device buffer d_in
     into the device buffer d_out (raw pointers) -> (bytes written, the
     DeviceFrameJob array: out_off, out_len, consumed, status, reason).  A
     frame with status EXACT_PATH was not decoded: explain_frame gives the
     reference's verdict.  TooLittleMemory carries the needed size as .bound.
     exact: the frames are sized first (frames_device_sizes) and laid out by
-    their sizes, so out_cap need only be that call's total."""
+    their sizes, so out_cap need only be that call's total.  dict: a
+    DeviceDict shared by every frame (lz4ada_decode_frames_device_dict, the LZ4
+    specification's semantics; decode_frame_dict_host is the way for a frame it
+    answers with EXACT_PATH)."""
     jobs = _device_jobs(spans)
     n = _i64()
-    call = _device_entry(linked, _lib.lz4ada_decode_frames_device, _lib.lz4ada_decode_frames_device_opt,
-                         exact)
-    st = call(d_in, in_len, jobs, len(spans), d_out, out_cap, ctypes.byref(n), stream)
+    if dict is not None:
+        st = _lib.lz4ada_decode_frames_device_dict(d_in, in_len, jobs, len(spans), _dict_flags(linked, exact),
+                                                   ctypes.byref(dict), d_out, out_cap, ctypes.byref(n), stream)
+    else:
+        call = _device_entry(linked, _lib.lz4ada_decode_frames_device, _lib.lz4ada_decode_frames_device_opt,
+                             exact)
+        st = call(d_in, in_len, jobs, len(spans), d_out, out_cap, ctypes.byref(n), stream)
     if st:
         exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
         exc.bound = n.value
@@ -701,19 +738,50 @@ def decode_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int
     return n.value, jobs
 
 
-def decode_frames_tensor(t, spans, out=None, linked=False, exact=False):
+def decode_frame_dict_host(frame, dict=b"", out_cap=None):
+    """One modern frame decoded against a dictionary (bytes) on the host, no
+    GPU involved: lz4ada_decode_frame_dict_host, the LZ4 specification's
+    semantics -> (decoded bytes, bytes of the frame consumed).  out_cap: the
+    output buffer's size (default: the declared content size, else every block
+    at the frame's block maximum)."""
+    frame, dict = bytes(frame), bytes(dict)
+    if out_cap is None:
+        info = FrameInfo()
+        _lib.lz4ada_frame_walk_host_opt(_addr(frame) if frame else None, len(frame), FRAMES_LINKED,
+                                        ctypes.byref(info), None, 0)
+        out_cap = int(info.content_size) if info.has_content_size else int(info.nblocks) * int(info.block_max)
+    buf = ctypes.create_string_buffer(max(out_cap, 1))
+    n, used = _i64(), _i64()
+    _check(_lib.lz4ada_decode_frame_dict_host(_addr(frame) if frame else None, len(frame),
+                                              _addr(dict) if dict else None, len(dict), buf, out_cap,
+                                              ctypes.byref(n), ctypes.byref(used)), _thread_error())
+    return buf.raw[:n.value], used.value
+
+
+def decode_frames_tensor(t, spans, out=None, linked=False, exact=False, dict=None, dict_id=None):
     """decode_frames_device for a CUDA torch.uint8 tensor holding the frames,
     on torch's current stream -> (the decoded bytes as a uint8 tensor on the
     same device, the DeviceFrameJob array).  out: a uint8 tensor there to
     decode into; by default one is allocated from frames_device_bound, or,
-    exact, from frames_device_sizes."""
+    exact, from frames_device_sizes.  dict: a CUDA uint8 tensor on the same
+    device holding the dictionary every frame shares; dict_id: when given,
+    a frame naming another dictionary id is rejected (DEVFRAME_DICT)."""
     if torch is None:
         raise RuntimeError("decode_frames_tensor needs torch")
     if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
         raise ValueError("the frames must be a contiguous CUDA uint8 tensor")
+    dd = None
+    if dict is not None:
+        if not (dict.is_cuda and dict.device == t.device and dict.dtype == torch.uint8 and dict.is_contiguous()):
+            raise ValueError("the dictionary must be a contiguous CUDA uint8 tensor on the frames' device")
+        dd = DeviceDict(dict.data_ptr() if dict.numel() else None, dict.numel(),
+                        0 if dict_id is None else dict_id, 0 if dict_id is None else DICT_CHECK_ID)
     with torch.cuda.device(t.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if out is None:
+        if out is None and dd is not None and not exact:
+            bound, _ = frames_device_bound(t.data_ptr(), t.numel(), spans, stream, linked, dd)
+            out = torch.empty(max(bound, 1), dtype=torch.uint8, device=t.device)
+        elif out is None:
             size_of = frames_device_sizes if exact else frames_device_bound
             bound, _ = size_of(t.data_ptr(), t.numel(), spans, stream, linked)
             out = torch.empty(max(bound, 1), dtype=torch.uint8, device=t.device)
@@ -721,7 +789,7 @@ def decode_frames_tensor(t, spans, out=None, linked=False, exact=False):
                   and out.is_contiguous()):
             raise ValueError("out must be a contiguous CUDA uint8 tensor on the frames' device")
         n, jobs = decode_frames_device(t.data_ptr(), t.numel(), spans, out.data_ptr(), out.numel(),
-                                       stream, linked, exact)
+                                       stream, linked, exact, dd)
     return out[:n], jobs
 
 
@@ -1131,15 +1199,17 @@ def gen_block(kind: int, seed: int, raw_len: int):
 
 
 def gen_linked_blocks(kind: int, seed: int, block_len: int, nblocks: int, last_len=None,
-                      lens=None):
+                      lens=None, hist=b""):
     """Blocks of one linked frame whose matches reach back into the earlier
     blocks' output (up to 64 KiB) -> list of (payload, decoded).  lens: the
-    decoded length of every block (overrides block_len / nblocks / last_len)."""
+    decoded length of every block (overrides block_len / nblocks / last_len).
+    hist: bytes that precede the first block (a dictionary), which its matches
+    may read too."""
     if lens is None:
         lens = [block_len] * nblocks
         if last_len is not None and nblocks:
             lens[-1] = last_len
-    out, hist = [], b""
+    out, hist = [], bytes(hist)
     for i, raw_len in enumerate(lens):
         h = hist[-65536:]
         buf = ctypes.create_string_buffer(h + bytes(max(raw_len, 1)), len(h) + max(raw_len, 1))

@@ -14,13 +14,16 @@ BD_CODE = {64 << 10: 4, 256 << 10: 5, 1 << 20: 6, 4 << 20: 7}
 
 
 def header(block_max: int, indep=True, block_cksum=False, content_cksum=False,
-           content_size=None) -> bytes:
+           content_size=None, dict_id=None) -> bytes:
     flg = 0x40 | (0x20 if indep else 0) | (0x10 if block_cksum else 0) \
-        | (0x08 if content_size is not None else 0) | (0x04 if content_cksum else 0)
+        | (0x08 if content_size is not None else 0) | (0x04 if content_cksum else 0) \
+        | (0x01 if dict_id is not None else 0)
     bd = BD_CODE[block_max] << 4
     desc = bytes([flg, bd])
     if content_size is not None:
         desc += struct.pack("<Q", content_size)
+    if dict_id is not None:
+        desc += struct.pack("<I", dict_id)
     hc = (xxhash.xxh32(desc).intdigest() >> 8) & 0xFF
     return struct.pack("<I", MAGIC) + desc + bytes([hc])
 
@@ -42,11 +45,12 @@ def trailer(content: bytes = None, content_cksum=False, content_hash=None) -> by
 
 
 def build_frame(blocks, block_max: int, indep=True, block_cksum=False, content_cksum=False,
-                with_content_size=False):
-    """blocks: list of (payload, decoded, stored) -> (frame bytes, decoded bytes)."""
+                with_content_size=False, dict_id=None):
+    """blocks: list of (payload, decoded, stored) -> (frame bytes, decoded bytes).
+    dict_id: FLG bit 0 and the dictionary id in the header."""
     decoded = b"".join(b[1] for b in blocks)
     out = [header(block_max, indep, block_cksum, content_cksum,
-                  len(decoded) if with_content_size else None)]
+                  len(decoded) if with_content_size else None, dict_id)]
     for payload, _, stored in blocks:
         out.append(block_record(payload, stored, block_cksum))
     out.append(trailer(decoded, content_cksum))

@@ -616,6 +616,81 @@ int lz4ada_frames_index_device_debug(const void *d_in, int64_t in_len,
                                      int32_t *verdict, int64_t *nblocks,
                                      lz4ada_block_desc *descs, int64_t desc_cap, void *stream);
 
+/* ------------------------------- device-resident frames with a dictionary */
+/*
+ * Small frames are what LZ4F dictionaries exist for: a 2 KiB record that
+ * compresses badly alone compresses well against a shared 64 KiB dictionary
+ * (LZ4F_compressFrame_usingCDict).  The two calls below are
+ * lz4ada_frames_device_bound_opt / lz4ada_decode_frames_device_opt with one
+ * dictionary, in device memory, shared by every frame of the call (DESIGN.md
+ * section 15).  Semantics are the LZ4 frame specification's
+ * (LZ4F_decompress_usingDict), not the reference's: the reference knows no
+ * dictionary and raises "Backreference location out of range" on such a
+ * frame, so these calls have no reference twin and replay none of its quirks
+ * (quirk D1 has no meaning where the reference cannot decode the frame at
+ * all: a match it would concern reads plain history).
+ *
+ * The last min(dict_len, 65536) bytes of the dictionary precede the first
+ * block of a linked modern frame and every block of an independent one;
+ * legacy blocks read no dictionary.  flags (LZ4ADA_FRAMES_LINKED,
+ * LZ4ADA_FRAMES_EXACT), job semantics, ordering, bounds, the
+ * LZ4ADA_TOO_LITTLE_MEMORY rule, lz4ada_last_batch_stats(), lz4ada_last_path()
+ * and the host synchronisations are those of the _opt calls (one more per call
+ * with LZ4ADA_DICT_CHECK_ID); the bound and out_cap count decoded bytes only,
+ * the room for the dictionary in front of the slots is the library's scratch
+ * and is charged against LZ4ADA_BATCH_BYTES when the passes are split.  A
+ * frame that never reads the dictionary decodes to the bytes the _opt call
+ * gives.  dict == NULL or dict_len == 0 is the _opt call itself, launch by
+ * launch.  API misuse, LZ4ADA_ASSERTION_ERROR before any launch: dict_len < 0,
+ * d_dict == NULL with dict_len > 0, unknown bits in dict->flags.
+ *
+ * With LZ4ADA_DICT_CHECK_ID a modern frame whose header carries a dictionary
+ * id (FLG bit 0) other than dict_id gets LZ4ADA_EXACT_PATH /
+ * LZ4ADA_DEVFRAME_DICT from the index stage, in both calls, and takes no slot;
+ * a frame without an id is accepted, as LZ4F allows.  Without the flag no id
+ * is looked at.
+ *
+ * A frame the pass does not find good gets LZ4ADA_EXACT_PATH and a reason, as
+ * in the _opt call.  The blocks of a dictionary call go through the index
+ * decoder alone (its fallback decoders know no history), so a block its first
+ * pass declines -- a block maximum over 256 KiB, or a literal-heavy payload --
+ * fails its frame with LZ4ADA_DEVFRAME_BLOCK, as does a match that reaches
+ * further back than the dictionary's first used byte.  One caution of the
+ * shared block decoder remains: where 2 KiB of a block's payload decode to
+ * more than 4,080 bytes, a match that starts before the block with an offset
+ * of 65,529 or more fails the frame the same way (elsewhere such a match is
+ * decoded).  The caller's way for such a frame is
+ * lz4ada_decode_frame_dict_host on its host bytes.
+ */
+#define LZ4ADA_DEVFRAME_DICT 8 /* the frame names another dictionary id */
+#define LZ4ADA_DICT_CHECK_ID 1u
+typedef struct {
+	const void *d_dict; /* device memory */
+	int64_t dict_len;   /* any length >= 0; the last 65,536 bytes are used */
+	uint32_t dict_id;   /* compared only with LZ4ADA_DICT_CHECK_ID */
+	uint32_t flags;     /* LZ4ADA_DICT_* */
+} lz4ada_device_dict;
+int lz4ada_frames_device_bound_dict(const void *d_in, int64_t in_len,
+                                    lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
+                                    const lz4ada_device_dict *dict, int64_t *bound, void *stream);
+int lz4ada_decode_frames_device_dict(const void *d_in, int64_t in_len,
+                                     lz4ada_device_frame_job *jobs, int64_t njobs, uint32_t flags,
+                                     const lz4ada_device_dict *dict, void *d_out, int64_t out_cap,
+                                     int64_t *out_len, void *stream);
+/* One modern frame (linked or independent, stored blocks included) decoded
+ * against a dictionary on the host: plain serial code, no HIP call, the LZ4
+ * specification's semantics as above.  It verifies block checksums, the
+ * content size and the content checksum, and compares no dictionary id.
+ * LZ4ADA_DATA_CORRUPTION (a malformed or truncated frame, a match reaching
+ * before the dictionary's first used byte, a wrong content size),
+ * LZ4ADA_CHECKSUM_ERROR, LZ4ADA_TOO_LITTLE_MEMORY (out_cap is too small),
+ * LZ4ADA_NOT_SUPPORTED (a legacy or skippable frame, unknown header bits); the
+ * message, this library's own, is in lz4ada_thread_last_error().  dict may be
+ * NULL with dict_len 0.  *out_len and *frame_consumed are 0 unless LZ4ADA_OK. */
+int lz4ada_decode_frame_dict_host(const uint8_t *frame, int64_t len, const uint8_t *dict,
+                                  int64_t dict_len, uint8_t *out, int64_t out_cap, int64_t *out_len,
+                                  int64_t *frame_consumed);
+
 /* --------------------- seek index and ranged decode of device-resident frames */
 /*
  * The exact sizes above are one prefix sum away from a seek table.  A seek
