@@ -14,10 +14,20 @@
 // The index is immutable after the build; a ranged call works in the calling
 // thread's scratch roles (SC_FRAME: the range records, SC_BATCH_META: the
 // pass's arrays, SC_OUT: the slots), so any number of threads may share one.
+//
+// With LZ4ADA_SEEK_LINKED (lz4ada_seek_index_build_opt) the
+// index takes linked frames: the build decodes each once with the linked run
+// of §12 (decode_linked_frames) and keeps the 64 KiB in front of every K-th
+// block in a store of its own (k_ckpt_save).  A range of a linked frame marks
+// its chain (lz4ada_range_chains.h): the pass lays a gap in front of every
+// head, fills it with the head's checkpoint (k_ckpt_fill) and decodes the
+// chains with the dictionary decoder of §15, one wave per chain, beside the
+// independent frames' launch_decode_checked; SC_TAB holds the sequence index.
 #include <climits>
 
 #include "lz4ada_host_common.h"
 #include "lz4ada_range_blocks.h"
+#include "lz4ada_range_chains.h"
 
 using namespace lz4ada;
 
@@ -25,6 +35,12 @@ struct lz4ada_seek_index {
 	int64_t in_len = 0;  // the input it was built over
 	void* d_mem = nullptr;
 	size_t bytes = 0;  // desc | first | start | slotp
+	// LZ4ADA_SEEK_LINKED: store | ckfirst | kgrp, and by sorted position what the
+	// last two hold (kgrp: n entries, K or 0; ckfirst: n + 1)
+	void* d_ck = nullptr;
+	size_t ck_bytes = 0;
+	std::vector<uint64_t> kgrp, ckfirst;
+	bool linked = false;  // it holds a linked frame
 	SeekView view{};
 	uint64_t* d_start = nullptr;
 	// by job
@@ -43,6 +59,11 @@ namespace {
 {
 	raise(LZ4ADA_ASSERTION_ERROR, std::string(entry) + ": " + what);
 }
+
+// LZ4ADA_SEEK_LINKED with checkpoint_bytes == 0: a checkpoint per MiB decoded.
+// A choice, not a measurement taken beforehand (DESIGN.md §16 has the table): the
+// store is then at most 1/16 of the decoded size for any block maximum up to 1 MiB.
+constexpr uint64_t SEEK_CHECKPOINT_BYTES = uint64_t(1) << 20;
 
 struct IndexDeleter {
 	void operator()(lz4ada_seek_index* x) const { lz4ada_seek_index_free(x); }
@@ -135,37 +156,55 @@ void select_ranges(const lz4ada_seek_index& x, Selection& s, hipStream_t stream)
 }
 
 // The blocks that the sorted ranges [lo, hi) mark, from their records: how
-// many once shared ones count once, their slot bytes, and the span of blocks
-// (among all the index's) they lie in.  The ranges of a frame come in rising
-// first block, so their union is a sweep.
+// many once shared ones count once, their slot bytes with the heads' gaps, the
+// span of blocks (among all the index's) they lie in, and the compacted blocks
+// cut into runs of one kind.  The ranges of a frame come in rising first block,
+// and so do their chains' starts, so their union is a sweep (ChainSweep).
 struct PassPlan {
 	uint32_t nsel = 0, span_n = 0;
 	uint64_t slots = 0, span_lo = 0;
+	bool linked = false;                            // a run is
+	std::vector<std::pair<bool, uint32_t>> runs;  // (linked, compacted blocks), in order
 };
+uint64_t frame_k(const lz4ada_seek_index& x, uint32_t f) { return x.kgrp.empty() ? 0 : x.kgrp[f]; }
+// what a range's own chain takes of the budget: its blocks' slots and its heads' gaps
+uint64_t range_need(const lz4ada_seek_index& x, const Selection& s, size_t k)
+{
+	const RangeSel& r = s.sel[k];
+	const uint64_t K = frame_k(x, s.rec[k].frame);
+	return r.slot_hi - r.slot_lo + CKPT_GAP * chain_heads(K, chain_start(K, r.first), uint64_t(r.first) + r.count);
+}
 PassPlan plan_pass(const lz4ada_seek_index& x, const Selection& s, size_t lo, size_t hi)
 {
 	PassPlan p;
-	uint64_t run_end = 0, run_slot = 0, nsel = 0, span_hi = 0;  // the open run: past its last block, its slots' end
+	uint64_t run_slot = 0, nsel = 0, span_hi = 0;  // the open frame's sweep, its slots' end
 	uint32_t run_frame = UINT32_MAX;
+	ChainSweep sweep(0);
 	for (size_t k = lo; k < hi; ++k) {
 		const RangeSel& r = s.sel[k];
 		const uint32_t f = s.rec[k].frame;
-		const uint64_t g0 = x.first[f] + r.first, g1 = g0 + r.count;
+		const uint64_t K = frame_k(x, f), c0 = chain_start(K, r.first);
 		if (k == lo)
-			p.span_lo = g0;
-		if (f != run_frame || g0 >= run_end) {  // a new run
-			nsel += r.count;
-			p.slots += r.slot_hi - r.slot_lo;
+			p.span_lo = x.first[f] + c0;
+		if (f != run_frame) {
+			sweep = ChainSweep(K);
 			run_frame = f;
-			run_end = g1;
-			run_slot = r.slot_hi;
-		} else if (g1 > run_end) {  // reaches past the open run
-			nsel += g1 - run_end;
-			p.slots += r.slot_hi - run_slot;
-			run_end = g1;
-			run_slot = r.slot_hi;
 		}
-		span_hi = std::max(span_hi, g1);
+		const ChainSweep::Added a = sweep.add(r.first, uint64_t(r.first) + r.count - 1);
+		span_hi = std::max(span_hi, x.first[f] + r.first + r.count);
+		if (a.hi <= a.lo)
+			continue;
+		// a new run of blocks takes its own slots, one that continues the open run
+		// what lies past that (slot_lo is slotp at c0, slot_hi past the last block)
+		p.slots += a.lo == c0 ? r.slot_hi - r.slot_lo : r.slot_hi - run_slot;
+		p.slots += CKPT_GAP * chain_heads(K, a.lo, a.hi);
+		run_slot = r.slot_hi;
+		nsel += a.hi - a.lo;
+		if (!p.runs.empty() && p.runs.back().first == (K != 0))
+			p.runs.back().second += uint32_t(a.hi - a.lo);
+		else
+			p.runs.emplace_back(K != 0, uint32_t(a.hi - a.lo));
+		p.linked |= K != 0;
 	}
 	// the index holds fewer than 2^31 blocks
 	p.nsel = uint32_t(nsel);
@@ -174,27 +213,33 @@ PassPlan plan_pass(const lz4ada_seek_index& x, const Selection& s, size_t lo, si
 }
 
 // A pass's device arrays in this thread's scratch.  SC_BATCH_META: descriptors
-// | statuses | slot | mark | cnt.  SC_OUT: the slots.
+// | statuses | chain records | slot | mark | cnt.  SC_OUT: the slots.  SC_TAB:
+// the sequence index.  The chain records and the sequence index only when the
+// pass decodes linked frames (in_len > 0 says so to reserve()).
 struct RangePass {
 	lz4ada_block_desc* d_desc = nullptr;
 	lz4ada_block_status* d_st = nullptr;
+	FrameRec* d_chain = nullptr;
 	uint64_t* d_slot = nullptr;
 	uint32_t *d_mark = nullptr, *d_cnt = nullptr;
-	uint8_t* d_slots = nullptr;
-	size_t st_b = 0, mark_b = 0;
-	void reserve(const PassPlan& p)
+	uint8_t *d_slots = nullptr, *d_tab = nullptr;
+	size_t st_b = 0, mark_b = 0, chain_b = 0;
+	void reserve(const PassPlan& p, bool chains = false, uint64_t in_len = 0)
 	{
 		const size_t desc_b = size_t(p.nsel) * sizeof(lz4ada_block_desc), slot_b = (size_t(p.span_n) + 1) * 8;
+		chain_b = chains ? size_t(chain_slots(p.nsel)) * sizeof(FrameRec) : 0;
 		st_b = size_t(p.nsel) * sizeof(lz4ada_block_status);
 		mark_b = size_t(p.span_n) * 4;
-		uint8_t* const d = scratch(SC_BATCH_META, desc_b + st_b + slot_b + mark_b + mark_b + 4);
+		uint8_t* const d = scratch(SC_BATCH_META, desc_b + st_b + chain_b + slot_b + mark_b + mark_b + 4);
 		d_slots = scratch(SC_OUT, size_t(std::max<uint64_t>(p.slots, 1)));
-		if (!d || !d_slots)
+		d_tab = chains ? scratch(SC_TAB, index_table_bytes(in_len, p.nsel)) : nullptr;
+		if (!d || !d_slots || (chains && !d_tab))
 			raise(LZ4ADA_DEVICE_ERROR, "no device memory for a pass over the ranges");
 		d_desc = reinterpret_cast<lz4ada_block_desc*>(d);
 		d_st = reinterpret_cast<lz4ada_block_status*>(d + desc_b);
-		d_slot = reinterpret_cast<uint64_t*>(d + desc_b + st_b);
-		d_mark = reinterpret_cast<uint32_t*>(d + desc_b + st_b + slot_b);
+		d_chain = chains ? reinterpret_cast<FrameRec*>(d + desc_b + st_b) : nullptr;
+		d_slot = reinterpret_cast<uint64_t*>(d + desc_b + st_b + chain_b);
+		d_mark = reinterpret_cast<uint32_t*>(d + desc_b + st_b + chain_b + slot_b);
 		d_cnt = d_mark + p.span_n;
 	}
 	// marks, scan: what select_debug needs of a pass, and its first half
@@ -204,7 +249,7 @@ struct RangePass {
 		HIP_OK(hipMemsetAsync(d_mark, 0, std::max<size_t>(mark_b, 4), stream));
 		HIP_OK(launch_ranges_select(x.view, s.d_rec + lo, uint32_t(hi - lo), nullptr, d_mark, p.span_lo, p.span_n,
 		                            stream));
-		HIP_OK(launch_ranges_scan(d_mark, p.span_n, d_cnt, d_slot, stream));
+		HIP_OK(launch_ranges_scan(d_mark, p.span_n, x.linked ? CKPT_GAP : 0, d_cnt, d_slot, stream));
 	}
 };
 
@@ -222,13 +267,37 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 {
 	const PassPlan p = plan_pass(x, s, lo, hi);
 	RangePass m;
-	m.reserve(p);
+	const uint64_t in_len = uint64_t(x.in_len);
+	m.reserve(p, p.linked, in_len);
 	const uint32_t nr = uint32_t(hi - lo);
 	m.mark(x, s, lo, hi, p, stream);
+	if (p.linked)  // a record no block fills has flags 0: its workgroup returns at once
+		HIP_OK(hipMemsetAsync(m.d_chain, 0, m.chain_b, stream));
 	HIP_OK(launch_ranges_fill(x.view, m.d_mark, m.d_cnt, m.d_slot, p.span_lo, p.span_n, p.nsel, p.slots, m.d_desc,
-	                          stream));
+	                          m.d_chain, stream));
 	HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
-	HIP_OK(launch_decode_checked(d_in, uint64_t(x.in_len), m.d_desc, p.nsel, m.d_slots, m.d_st, stream));
+	if (p.linked)
+		HIP_OK(launch_ckpt_fill(x.view, m.d_desc, m.d_chain, p.nsel, m.d_slots, p.slots, stream));
+	// the compacted blocks run by run, as the host's sweep cut them: independent
+	// frames' with the passes' decoders, linked frames' with pass 1 and the block
+	// checksums as a linked run of a many-frame pass has them; then every chain
+	// of the pass in one launch, one wave each, its checkpoint as its dictionary
+	uint32_t b0 = 0;
+	for (const auto& run : p.runs) {
+		const uint32_t n = run.second;
+		if (!run.first) {
+			HIP_OK(launch_decode_checked(d_in, in_len, m.d_desc + b0, n, m.d_slots, m.d_st + b0, stream));
+		} else {
+			HIP_OK(launch_block_checksums_beside(d_in, m.d_desc + b0, n, m.d_st + b0, stream));
+			HIP_OK(launch_index(d_in, in_len, m.d_desc + b0, n, m.d_tab + size_t(b0) * 64, m.d_st + b0, stream));
+		}
+		b0 += n;
+	}
+	if (p.linked) {
+		HIP_OK(launch_decode_idx_frames_dict(d_in, in_len, m.d_desc, p.nsel, m.d_tab, m.d_slots, m.d_st, m.d_chain,
+		                                     uint32_t(chain_slots(p.nsel)), uint32_t(CKPT_BYTES), stream));
+		HIP_OK(join_block_checksums(stream));
+	}
 	HIP_OK(launch_ranges_verdict(x.view, s.d_rec + lo, nr, s.d_sel + lo, m.d_cnt, p.span_lo, p.span_n, m.d_desc,
 	                             m.d_st, p.nsel, stream));
 	const uint64_t tile_lo = s.rec[lo].tile0, tile_hi = hi < s.rec.size() ? s.rec[hi].tile0 : s.tiles;
@@ -248,8 +317,206 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 		if (got[k - lo].fail >= 0)
 			range_failed(ranges[s.of[k]], LZ4ADA_DEVFRAME_BLOCK);
 		else
-			add_last_path(LZ4ADA_PATH_BATCH | LZ4ADA_PATH_INDEPENDENT);
+			add_last_path(LZ4ADA_PATH_BATCH |
+			              (frame_k(x, s.rec[k].frame) ? LZ4ADA_PATH_LINKED : LZ4ADA_PATH_INDEPENDENT));
 	}
+}
+
+// LZ4ADA_SEEK_LINKED: every linked frame the sizes stage accepted, decoded once
+// with the linked run of a many-frame pass (pass 1, one wave per
+// frame with quirk D1's round state, the block checksums beside them), in
+// passes under the byte budget, and the checkpoints of each pass saved from its
+// slots.  The passes see walk records in which only those frames are accepted
+// (SC_DICT: nominal | tight), so an independent frame takes no block and no
+// slot.  A frame whose chain fails is no longer taken(), on the host and on the
+// device, with LZ4ADA_DEVFRAME_BLOCK (_SIZE) as its verdict.  One host
+// synchronisation per pass: the frame records.
+void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* d_store, uint64_t* d_ckfirst,
+                          uint64_t* d_kgrp, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
+{
+	const size_t n = ix.order.size(), walk_b = n * sizeof(FrameWalkRec);
+	const size_t ckf_b = (n + 1) * 8, kg_b = n * 8;
+	auto mine = [&](size_t k) { return ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0; };
+	FrameWalkRec* const d_nom = reinterpret_cast<FrameWalkRec*>(scratch(SC_DICT, 2 * walk_b));
+	if (!d_nom)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the linked frames' records");
+	FrameWalkRec* const d_tight = d_nom + n;
+	// pinned: the index's per-frame words and the records going up, and behind
+	// them room for a pass's frame records coming down, so that nothing is
+	// written while a copy may read it
+	PinBuf& h = scratch_cache().pin;
+	h.reserve(ckf_b + kg_b + 2 * walk_b + n * sizeof(FrameRec));
+	memcpy(h.p, x.ckfirst.data(), ckf_b);
+	memcpy(h.p + ckf_b, x.kgrp.data(), kg_b);
+	HIP_OK(hipMemcpyAsync(d_ckfirst, h.p, ckf_b + kg_b, hipMemcpyHostToDevice, stream));  // (kgrp follows ckfirst)
+	FrameWalkRec* const w = reinterpret_cast<FrameWalkRec*>(h.p + ckf_b + kg_b);
+	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p + ckf_b + kg_b + 2 * walk_b);
+	bool any = false;
+	for (size_t k = 0; k < n; ++k) {
+		w[k] = ix.walk[k];
+		if (!mine(k))
+			w[k].verdict = w[k].verdict == LZ4ADA_BATCH_OK ? LZ4ADA_BATCH_LINKED : w[k].verdict;  // rides along
+		w[n + k] = w[k];
+		w[n + k].slots = ix.size[k].tight;
+		any |= mine(k);
+	}
+	if (!any)
+		return;
+	HIP_OK(hipMemcpyAsync(d_nom, w, 2 * walk_b, hipMemcpyHostToDevice, stream));
+	const uint64_t budget = uint64_t(batch_budget());
+	bool failed = false;
+	for (size_t lo = 0; lo < n;) {
+		size_t hi = lo;
+		uint64_t acc = 0, nb = 0;
+		for (; hi < n; ++hi) {
+			if (!mine(hi))
+				continue;
+			const uint64_t cost = ix.size[hi].tight;
+			if ((acc && acc + cost > budget) || nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
+				break;
+			acc += cost;
+			nb += ix.walk[hi].nblocks;
+		}
+		if (nb == 0) {
+			lo = std::max(hi, lo + 1);
+			continue;
+		}
+		std::vector<PassFrame> frames;
+		for (size_t k = lo; k < hi; ++k)
+			frames.push_back(PassFrame{ mine(k) ? uint32_t(ix.walk[k].nblocks) : 0u, true });
+		PassArrays m;
+		if (const char* what = m.reserve(frames, acc, in_len))
+			raise(LZ4ADA_DEVICE_ERROR, std::string("no device memory for the build pass's ") + what);
+		const uint32_t nf = m.nf;
+		HIP_OK(launch_frames_scan(d_tight + lo, nf, ix.d_first, ix.d_slot, stream));
+		HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, d_nom + lo, ix.d_first, ix.d_slot, nf, lone_blocks_disabled(),
+		                          true, ix.linked_max, m.d_desc, m.d_rec, stream));
+		HIP_OK(launch_frames_refit(d_tight + lo, ix.d_first, ix.d_slot, ix.d_size_first + lo, ix.d_size, nf, m.d_desc,
+		                           stream));
+		HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
+		HIP_OK(launch_block_checksums_beside(d_in, m.d_desc, m.nb, m.d_st, stream));
+		HIP_OK(launch_index(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_st, stream));
+		HIP_OK(launch_decode_idx_frames(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_slots, m.d_st, m.d_rec, nf, stream));
+		HIP_OK(join_block_checksums(stream));
+		HIP_OK(launch_frames_plan(m.d_desc, m.d_st, m.nb, m.d_rec, nf, m.d_off, m.d_loc, m.d_part, stream));
+		HIP_OK(launch_ckpt_save(d_kgrp, d_ckfirst, uint32_t(lo), nf, x.ckfirst[lo], uint32_t(x.ckfirst[hi] - x.ckfirst[lo]),
+		                        x.ckfirst[n], m.d_desc, m.nb, m.d_rec, m.d_slots, acc, d_store, stream));
+		// the pass's host synchronisation: the frame records
+		HIP_OK(hipMemcpyAsync(rec, m.d_rec, m.rec_b, hipMemcpyDeviceToHost, stream));
+		HIP_OK(hipStreamSynchronize(stream));
+		++batch_stats().passes;
+		for (size_t k = lo; k < hi; ++k) {
+			if (!mine(k))
+				continue;
+			const FrameRec& r = rec[k - lo];
+			if (r.fail >= 0 || (r.verdict & FRAME_SIZE_BAD)) {
+				ix.walk[k].verdict = r.fail >= 0 ? LZ4ADA_DEVFRAME_BLOCK : LZ4ADA_DEVFRAME_SIZE;
+				failed = true;
+			}
+		}
+		lo = hi;
+	}
+	if (failed) {  // the device's records follow the host's, for the scan that fixes the index
+		memcpy(w, ix.walk.data(), walk_b);
+		HIP_OK(hipMemcpyAsync(ix.d_walk, w, walk_b, hipMemcpyHostToDevice, stream));
+	}
+}
+
+// The one body of both builds.  linked: LZ4ADA_SEEK_LINKED, with a checkpoint
+// every `every` decoded bytes.
+void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                 bool linked, uint64_t every, lz4ada_seek_index** idx, hipStream_t s)
+{
+	FramesIndex ix;
+	index_jobs(entry, d_in, in_len, jobs, njobs, linked ? LZ4ADA_FRAMES_LINKED : 0, s, ix);
+	size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
+	std::unique_ptr<lz4ada_seek_index, IndexDeleter> x(new lz4ada_seek_index);
+	const size_t n = ix.order.size();
+	x->in_len = in_len;
+	if (linked && n) {
+		// the checkpoints of every linked frame the sizes stage accepted, and the
+		// linked frames decoded once into them
+		x->kgrp.assign(n, 0);
+		x->ckfirst.assign(n + 1, 0);
+		for (size_t k = 0; k < n; ++k) {
+			const bool lk = ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0;
+			if (lk)
+				x->kgrp[k] = chain_group(every, chain_block_max(ix.walk[k].nblocks, ix.size[k].exact));
+			x->ckfirst[k + 1] = x->ckfirst[k] + (lk ? chain_checkpoints(x->kgrp[k], ix.walk[k].nblocks) : 0);
+		}
+		const uint64_t nck = x->ckfirst[n];
+		const size_t store_b = size_t(nck) * CKPT_BYTES, ckf_b = (n + 1) * 8, kg_b = n * 8;
+		x->ck_bytes = store_b + ckf_b + kg_b;
+		if (hipMalloc(&x->d_ck, x->ck_bytes) != hipSuccess) {
+			(void)hipGetLastError();
+			x->d_ck = nullptr;
+			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index's checkpoints");
+		}
+		uint8_t* const c = static_cast<uint8_t*>(x->d_ck);
+		uint64_t* const d_ckfirst = reinterpret_cast<uint64_t*>(c + store_b);
+		uint64_t* const d_kgrp = d_ckfirst + n + 1;
+		// (which also sends the two arrays up, from pinned memory with its records)
+		decode_linked_frames(ix, *x, c, d_ckfirst, d_kgrp, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
+		x->view.kgrp = d_kgrp;
+		x->view.ckfirst = d_ckfirst;
+		x->view.store = c;
+		x->view.nckpt = nck;
+	}
+	report_sizes(ix, jobs);
+	x->pos.resize(n);
+	x->reason.resize(n);
+	x->size.assign(n, 0);
+	x->first.assign(n + 1, 0);
+	for (size_t k = 0; k < n; ++k) {
+		const size_t job = ix.order[k];
+		x->pos[job] = uint32_t(k);
+		x->reason[job] = ix.walk[k].verdict;
+		x->size[job] = ix.taken(k) ? ix.size[k].exact : 0;
+		x->first[k + 1] = x->first[k] + (ix.taken(k) ? ix.walk[k].nblocks : 0);
+		if (linked && n && !ix.taken(k))
+			x->kgrp[k] = 0;
+		x->linked |= linked && ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0;
+	}
+	const uint64_t nb = x->first[n];
+	if (nb >= (uint64_t(1) << 31))
+		raise(LZ4ADA_CONSTRAINT_ERROR, "the frames hold more blocks than a seek index takes");
+	if (n == 0) {
+		*idx = x.release();
+		return;
+	}
+	// what the index keeps: 32 bytes per block, 16 for its two prefixes,
+	// 24 per frame (first, and the prefixes' end entries)
+	const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), first_b = (n + 1) * 8,
+	             pre_b = (size_t(nb) + n) * 8;
+	x->bytes = desc_b + first_b + 2 * pre_b;
+	if (hipMalloc(&x->d_mem, x->bytes) != hipSuccess) {
+		(void)hipGetLastError();
+		x->d_mem = nullptr;
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index");
+	}
+	uint8_t* const m = static_cast<uint8_t*>(x->d_mem);
+	lz4ada_block_desc* const d_desc = reinterpret_cast<lz4ada_block_desc*>(m);
+	uint64_t* const d_first = reinterpret_cast<uint64_t*>(m + desc_b);
+	x->d_start = reinterpret_cast<uint64_t*>(m + desc_b + first_b);
+	uint64_t* const d_slotp = reinterpret_cast<uint64_t*>(m + desc_b + first_b + pre_b);
+	x->view.desc = d_desc;
+	x->view.first = d_first;
+	x->view.start = x->d_start;
+	x->view.slotp = d_slotp;
+	x->view.nframes = uint32_t(n);
+	FrameRec* const d_rec = reinterpret_cast<FrameRec*>(scratch(SC_BATCH_META, n * sizeof(FrameRec)));
+	if (!d_rec)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index");
+	// the descriptors of every frame the sizes stage passed, for good: its
+	// verdicts are in d_walk, so the scan counts what x->first counts
+	HIP_OK(launch_frames_scan(ix.d_walk, uint32_t(n), ix.d_first, ix.d_slot, s));
+	HIP_OK(launch_frames_fill(static_cast<const uint8_t*>(d_in), ix.d_span, ix.d_walk, ix.d_first, ix.d_slot,
+	                          uint32_t(n), lone_blocks_disabled(), linked, ix.linked_max, d_desc, d_rec, s));
+	HIP_OK(hipMemcpyAsync(d_first, ix.d_first, first_b, hipMemcpyDeviceToDevice, s));
+	HIP_OK(launch_block_starts(ix.d_first, ix.d_size_first, ix.d_size, uint32_t(n), x->d_start, d_slotp, s));
+	// the index is complete when the call returns, for any stream and thread
+	HIP_OK(hipStreamSynchronize(s));
+	*idx = x.release();
 }
 
 }  // namespace
@@ -269,61 +536,29 @@ int lz4ada_seek_index_build(const void* d_in, int64_t in_len, lz4ada_device_fram
 			misuse(entry, "idx is NULL");
 		if (flags != 0)
 			misuse(entry, "flags must be 0");
-		hipStream_t s = static_cast<hipStream_t>(stream);
-		FramesIndex ix;
-		index_jobs(entry, d_in, in_len, jobs, njobs, 0, s, ix);
-		size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
-		report_sizes(ix, jobs);
-		std::unique_ptr<lz4ada_seek_index, IndexDeleter> x(new lz4ada_seek_index);
-		const size_t n = ix.order.size();
-		x->in_len = in_len;
-		x->pos.resize(n);
-		x->reason.resize(n);
-		x->size.assign(n, 0);
-		x->first.assign(n + 1, 0);
-		for (size_t k = 0; k < n; ++k) {
-			const size_t job = ix.order[k];
-			x->pos[job] = uint32_t(k);
-			x->reason[job] = ix.walk[k].verdict;
-			x->size[job] = ix.taken(k) ? ix.size[k].exact : 0;
-			x->first[k + 1] = x->first[k] + (ix.taken(k) ? ix.walk[k].nblocks : 0);
-		}
-		const uint64_t nb = x->first[n];
-		if (nb >= (uint64_t(1) << 31))
-			raise(LZ4ADA_CONSTRAINT_ERROR, "the frames hold more blocks than a seek index takes");
-		if (n == 0) {
-			*idx = x.release();
-			return;
-		}
-		// what the index keeps: 32 bytes per block, 16 for its two prefixes,
-		// 24 per frame (first, and the prefixes' end entries)
-		const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), first_b = (n + 1) * 8,
-		             pre_b = (size_t(nb) + n) * 8;
-		x->bytes = desc_b + first_b + 2 * pre_b;
-		if (hipMalloc(&x->d_mem, x->bytes) != hipSuccess) {
-			(void)hipGetLastError();
-			x->d_mem = nullptr;
-			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index");
-		}
-		uint8_t* const m = static_cast<uint8_t*>(x->d_mem);
-		lz4ada_block_desc* const d_desc = reinterpret_cast<lz4ada_block_desc*>(m);
-		uint64_t* const d_first = reinterpret_cast<uint64_t*>(m + desc_b);
-		x->d_start = reinterpret_cast<uint64_t*>(m + desc_b + first_b);
-		uint64_t* const d_slotp = reinterpret_cast<uint64_t*>(m + desc_b + first_b + pre_b);
-		x->view = SeekView{ d_desc, d_first, x->d_start, d_slotp, uint32_t(n) };
-		FrameRec* const d_rec = reinterpret_cast<FrameRec*>(scratch(SC_BATCH_META, n * sizeof(FrameRec)));
-		if (!d_rec)
-			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index");
-		// the descriptors of every frame the sizes stage passed, for good: its
-		// verdicts are in d_walk, so the scan counts what x->first counts
-		HIP_OK(launch_frames_scan(ix.d_walk, uint32_t(n), ix.d_first, ix.d_slot, s));
-		HIP_OK(launch_frames_fill(static_cast<const uint8_t*>(d_in), ix.d_span, ix.d_walk, ix.d_first, ix.d_slot,
-		                          uint32_t(n), lone_blocks_disabled(), false, ix.linked_max, d_desc, d_rec, s));
-		HIP_OK(hipMemcpyAsync(d_first, ix.d_first, first_b, hipMemcpyDeviceToDevice, s));
-		HIP_OK(launch_block_starts(ix.d_first, ix.d_size_first, ix.d_size, uint32_t(n), x->d_start, d_slotp, s));
-		// the index is complete when the call returns, for any stream and thread
-		HIP_OK(hipStreamSynchronize(s));
-		*idx = x.release();
+		build_index(entry, d_in, in_len, jobs, njobs, false, 0, idx, static_cast<hipStream_t>(stream));
+	});
+}
+
+int lz4ada_seek_index_build_opt(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                                const lz4ada_seek_options* opt, lz4ada_seek_index** idx, void* stream)
+{
+	if (idx)
+		*idx = nullptr;
+	batch_stats() = lz4ada_batch_stats{};
+	return guarded(nullptr, [&] {
+		const char* const entry = "lz4ada_seek_index_build_opt";
+		if (!idx)
+			misuse(entry, "idx is NULL");
+		if (opt && (opt->flags & ~LZ4ADA_SEEK_LINKED))
+			misuse(entry, "unknown bits in opt->flags");
+		if (opt && opt->reserved != 0)
+			misuse(entry, "opt->reserved must be 0");
+		if (opt && opt->checkpoint_bytes < 0)
+			misuse(entry, "opt->checkpoint_bytes is negative");
+		const bool linked = opt && (opt->flags & LZ4ADA_SEEK_LINKED);
+		const uint64_t every = opt && opt->checkpoint_bytes ? uint64_t(opt->checkpoint_bytes) : SEEK_CHECKPOINT_BYTES;
+		build_index(entry, d_in, in_len, jobs, njobs, linked, every, idx, static_cast<hipStream_t>(stream));
 	});
 }
 
@@ -333,10 +568,12 @@ void lz4ada_seek_index_free(lz4ada_seek_index* idx)
 		return;
 	if (idx->d_mem)
 		(void)hipFree(idx->d_mem);
+	if (idx->d_ck)
+		(void)hipFree(idx->d_ck);
 	delete idx;
 }
 
-int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index* idx) { return idx ? int64_t(idx->bytes) : 0; }
+int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index* idx) { return idx ? int64_t(idx->bytes + idx->ck_bytes) : 0; }
 
 int lz4ada_decode_ranges_device(const lz4ada_seek_index* idx, const void* d_in, int64_t in_len,
                                 lz4ada_frame_range* ranges, int64_t nranges, void* d_out, int64_t out_cap,
@@ -366,14 +603,14 @@ int lz4ada_decode_ranges_device(const lz4ada_seek_index* idx, const void* d_in, 
 		hipStream_t s = static_cast<hipStream_t>(stream);
 		select_ranges(*idx, sel, s);
 		// the sorted ranges [lo, hi): as many as the budget takes, by the sum of
-		// their own slot bytes (a block two of them share counts twice)
+		// their own chains' slot bytes and gaps (a block two of them share counts twice)
 		const uint64_t budget = uint64_t(batch_budget());
 		const size_t n = sel.of.size();
 		for (size_t lo = 0; lo < n;) {
 			size_t hi = lo;
 			uint64_t acc = 0;
 			for (; hi < n; ++hi) {
-				const uint64_t need = sel.sel[hi].slot_hi - sel.sel[hi].slot_lo;
+				const uint64_t need = range_need(*idx, sel, hi);
 				if (need > budget || (acc && acc + need > budget))
 					break;
 				acc += need;
@@ -403,6 +640,22 @@ int lz4ada_range_blocks_host(const uint64_t* start, int64_t nblocks, const int64
 		count[i] = int64_t(r.count);
 		want[i] = int64_t(range_clip(start[nblocks], uint64_t(off[i]), uint64_t(len[i])));
 	}
+	return LZ4ADA_OK;
+}
+
+int lz4ada_range_chains_host(int64_t nblocks, int64_t group, const int64_t* first, const int64_t* count, int64_t n,
+                             uint8_t* marked, uint8_t* head, int64_t* chain_first, int64_t* chain_count,
+                             int64_t* nchains)
+{
+	if (nchains)
+		*nchains = 0;
+	if (nblocks < 0 || group < 0 || n < 0 || !nchains || (n > 0 && (!first || !count)) ||
+	    (nblocks > 0 && (!marked || !head || !chain_first || !chain_count)))
+		return LZ4ADA_ASSERTION_ERROR;
+	for (int64_t i = 0; i < n; ++i)
+		if (first[i] < 0 || count[i] < 0 || first[i] > nblocks || count[i] > nblocks - first[i])
+			return LZ4ADA_ASSERTION_ERROR;
+	*nchains = range_chains(uint64_t(nblocks), uint64_t(group), first, count, n, marked, head, chain_first, chain_count);
 	return LZ4ADA_OK;
 }
 

@@ -489,12 +489,21 @@ hipError_t launch_decode_idx_frames_dict(const uint8_t* d_frame, uint64_t frame_
 // none).  start / slotp: frame k's nb + 1 entries begin at first[k] + k: the
 // decoded offset at which each block starts and the frame's size, and the same
 // prefix over round256(size), the blocks' tight slots.
+// An index that took linked frames also has kgrp: frame k's K,
+// the blocks per checkpoint group, 0 for a frame of independent blocks, and
+// ckfirst: n + 1 entries, frame k's checkpoints are [ckfirst[k], ckfirst[k + 1])
+// among the nckpt entries of CKPT_BYTES bytes each at store.  All three are
+// null / 0 in an index built without LZ4ADA_SEEK_LINKED.
 struct SeekView {
 	const lz4ada_block_desc* desc;
 	const uint64_t* first;
 	const uint64_t* start;
 	const uint64_t* slotp;
 	uint32_t nframes;
+	const uint64_t* kgrp;
+	const uint64_t* ckfirst;
+	const uint8_t* store;
+	uint64_t nckpt;
 };
 // One range with bytes to deliver, as the host hands it to the kernels.
 struct RangeRec {
@@ -506,7 +515,7 @@ struct RangeRec {
 // What k_ranges_select found for it, and k_ranges_verdict after the decode.
 struct RangeSel {
 	uint32_t first, count;      // the blocks it touches, frame-relative
-	uint64_t slot_lo, slot_hi;  // slotp at first and at first + count
+	uint64_t slot_lo, slot_hi;  // slotp at its chain's start (chain_start: `first` unless linked), at first + count
 	int32_t fail;               // first failing block among them (frame-relative), -1: none
 	int32_t pad;
 };
@@ -519,22 +528,53 @@ hipError_t launch_block_starts(const uint64_t* d_first, const uint64_t* d_size_f
                                uint32_t nframes, uint64_t* d_start, uint64_t* d_slotp, hipStream_t stream);
 // One wave per range.  d_sel not null: every range's RangeSel (fail -1).
 // d_mark not null: mark[b - span_lo] = 1 + round256(size) / 256 for every block
-// b the range touches inside [span_lo, span_lo + span_n) (the same value from
-// every writer).  Reads the index alone.
+// b of the range's chain (lz4ada_range_chains.h: the blocks it touches, and in
+// a linked frame those from its group's start on) inside [span_lo, span_lo +
+// span_n), with RANGE_MARK_GAP added for a head (the same value from every
+// writer).  Reads the index alone.
+constexpr uint32_t RANGE_MARK_GAP = 0x80000000u;
+// The gap in front of a head's slot: its checkpoint as a dictionary of DICT_MAX bytes.
+constexpr uint64_t CKPT_GAP = (uint64_t(DICT_MAX) + 32 + 255) & ~uint64_t(255);
 hipError_t launch_ranges_select(const SeekView& v, const RangeRec* d_ranges, uint32_t nranges, RangeSel* d_sel,
                                 uint32_t* d_mark, uint64_t span_lo, uint32_t span_n, hipStream_t stream);
-// One workgroup: d_cnt[i] / d_slot[i] get the marked blocks / their slot bytes
-// before span block i, entry span_n the totals.
-hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint32_t* d_cnt, uint64_t* d_slot,
-                              hipStream_t stream);
+// One workgroup: d_cnt[i] / d_slot[i] get the marked blocks before span block i
+// and where block i's bytes begin: past the slot bytes of the marked blocks
+// before it and past the gaps (`gap` bytes per RANGE_MARK_GAP) up to its own;
+// entry span_n the totals.
+hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t gap, uint32_t* d_cnt,
+                              uint64_t* d_slot, hipStream_t stream);
 // One lane per span block: a marked block's descriptor goes to d_desc[d_cnt[i]]
 // with out_off = d_slot[i] and out_cap = its exact size.  Writes no descriptor
 // at or past nsel and places no block past slots (an empty one instead).
+// d_chain not null (a pass with linked frames): d_chain[chain_slot(d_cnt[i],
+// nsel)] (lz4ada_range_chains.h; chain_slots(nsel) records, zeroed by the
+// caller) gets the block's chain record -- a head (BLOCK_DICT in its descriptor, its checkpoint's
+// number among the store's in content_size) or a marked block 0 of a linked
+// frame carries FRAME_LINKED, first = its own place and nblocks = the marked
+// blocks of its group from it on (a walk over at most K marks); every other
+// record has flags 0.
 hipError_t launch_ranges_fill(const SeekView& v, const uint32_t* d_mark, const uint32_t* d_cnt,
                               const uint64_t* d_slot, uint64_t span_lo, uint32_t span_n, uint32_t nsel,
-                              uint64_t slots, lz4ada_block_desc* d_desc, hipStream_t stream);
-// One wave per range, after the decode: d_sel[i].fail = the first block the
-// range touches whose status is non-zero, whose length is not its size or
+                              uint64_t slots, lz4ada_block_desc* d_desc, FrameRec* d_chain, hipStream_t stream);
+// One workgroup per compacted block: in front of the slot of every BLOCK_DICT
+// block whose chain record names a checkpoint, CKPT_GAP bytes: zeros, then the
+// checkpoint.  Writes inside [out_off - CKPT_GAP, out_off) only, and nothing
+// where out_off < CKPT_GAP or out_off > slots.
+hipError_t launch_ckpt_fill(const SeekView& v, const lz4ada_block_desc* d_desc, const FrameRec* d_chain,
+                            uint32_t nsel, uint8_t* d_slots, uint64_t slots, hipStream_t stream);
+// The build: the checkpoints [ck_lo, ck_lo + nck) of the index, which are those
+// of the sorted frames [f_lo, f_lo + nf) of one decode pass (d_rec: the pass's
+// frame records after launch_frames_plan, d_desc its descriptors), from the
+// pass's slots to the store, CKPT_SAVE_SPLIT workgroups per checkpoint.  A
+// checkpoint whose frame does not have CKPT_BYTES contiguous decoded bytes in
+// front of that block inside [0, slots) sets the frame's fail to 0 instead.
+constexpr uint32_t CKPT_SAVE_SPLIT = 4;
+hipError_t launch_ckpt_save(const uint64_t* d_kgrp, const uint64_t* d_ckfirst, uint32_t f_lo, uint32_t nf,
+                            uint64_t ck_lo, uint32_t nck, uint64_t nckpt, const lz4ada_block_desc* d_desc,
+                            uint32_t nblocks, FrameRec* d_rec, const uint8_t* d_slots, uint64_t slots,
+                            uint8_t* d_store, hipStream_t stream);
+// One wave per range, after the decode: d_sel[i].fail = the first block of the
+// range's chain whose status is non-zero, whose length is not its size or
 // whose block checksum differs.
 hipError_t launch_ranges_verdict(const SeekView& v, const RangeRec* d_ranges, uint32_t nranges, RangeSel* d_sel,
                                  const uint32_t* d_cnt, uint64_t span_lo, uint32_t span_n,

@@ -15,6 +15,15 @@
 //  * k_ranges_verdict -- one wave per range: its first failing block;
 //  * k_ranges_gather -- one workgroup per 16 KiB of a range: from the blocks'
 //    slots to the caller's buffer, 16 bytes per lane between bytewise edges.
+// Linked frames through history checkpoints add
+//  * k_ckpt_save -- at the build: the 64 KiB in front of every group start,
+//    from a decode pass's slots to the index's store, 16 bytes per lane;
+//  * k_ckpt_fill -- one workgroup per compacted block: a head's checkpoint into
+//    the gap in front of its slot, behind 256 zeros;
+// and the chain rule (lz4ada_range_chains.h) in select, fill and verdict: the
+// marks reach back to the group's start, a head's mark carries RANGE_MARK_GAP,
+// the scan turns that bit into the gap's bytes, and the fill writes one chain
+// record per compacted block for k_decode_idx_frames_dict.
 // Every bound is taken from the index's arrays and the host's counts; no
 // kernel here reads a frame byte, and none lets a block status steer an
 // address.  Plain vector stores only.
@@ -25,6 +34,7 @@
 #include "lz4ada_dev.h"
 #include "lz4ada_block_size.h"
 #include "lz4ada_range_blocks.h"
+#include "lz4ada_range_chains.h"
 
 namespace lz4ada {
 
@@ -34,6 +44,10 @@ constexpr uint32_t WAVE = 64;
 constexpr uint32_t RSCAN_WG = 1024;  // span blocks per round of the scan
 constexpr uint32_t FILL_WG = 256;
 constexpr uint32_t GATHER_WG = 256;
+constexpr uint32_t CKPT_WG = 256;
+static_assert(CKPT_GAP >= CKPT_BYTES + 32 && CKPT_GAP % 256 == 0 && CKPT_BYTES == DICT_MAX,
+              "a checkpoint is a dictionary of DICT_MAX bytes in a gap of dict_gap(DICT_MAX)");
+static_assert(CKPT_BYTES % (CKPT_SAVE_SPLIT * CKPT_WG * 16) == 0, "k_ckpt_save's pieces tile a checkpoint");
 
 // 16 bytes at any byte address: one global_load_dwordx4 (gfx950 takes an
 // unaligned address; the bytes read are the 16 asked for)
@@ -120,40 +134,48 @@ __global__ __launch_bounds__(WAVE) void k_ranges_select(SeekView v, const RangeR
 	// every lane runs the same search over the same addresses
 	const RangeBlocks rb = range_blocks(st, nb, off, want);
 	const uint64_t b0 = wave_uniform(rb.first), n = wave_uniform(rb.count);
+	// the chain: in a linked frame the marks begin at the group's start
+	const uint64_t K = v.kgrp ? wave_uniform(v.kgrp[k]) : 0;
+	const uint64_t c0 = n ? chain_start(K, b0) : b0;
 	if (sel && lane_id() == 0) {
 		RangeSel r;
 		r.first = uint32_t(b0);
 		r.count = uint32_t(n);
-		r.slot_lo = sp[b0];
+		r.slot_lo = sp[c0];
 		r.slot_hi = sp[b0 + n];
 		r.fail = -1;
 		r.pad = 0;
 		sel[i] = r;
 	}
 	if (mark) {
-		for (uint64_t j = lane_id(); j < n; j += WAVE) {
-			const uint64_t b = f + b0 + j;
+		for (uint64_t j = c0 + lane_id(); j < b0 + n; j += WAVE) {
+			const uint64_t b = f + j;
 			if (b >= span_lo && b - span_lo < span_n)
-				mark[b - span_lo] = 1u + uint32_t((sp[b0 + j + 1] - sp[b0 + j]) >> 8);
+				mark[b - span_lo] = (1u + (uint32_t((sp[j + 1] - sp[j]) >> 8) & ~RANGE_MARK_GAP)) |
+				                    (chain_head(K, j) ? RANGE_MARK_GAP : 0u);
 		}
 	}
 }
 
 __global__ __launch_bounds__(RSCAN_WG) void k_ranges_scan(const uint32_t* __restrict__ mark, uint32_t span_n,
-                                                          uint32_t* __restrict__ cnt, uint64_t* __restrict__ slot)
+                                                          uint64_t gap, uint32_t* __restrict__ cnt,
+                                                          uint64_t* __restrict__ slot)
 {
 	__shared__ uint64_t wsum[RSCAN_WG / 64];
 	uint64_t carry_c = 0, carry_s = 0;
 	for (uint32_t i0 = 0; i0 < span_n; i0 += RSCAN_WG) {
 		const uint32_t i = i0 + threadIdx.x;
-		const uint32_t m = i < span_n ? mark[i] : 0u;
-		const uint64_t c = m ? 1u : 0u, s = m ? uint64_t(m - 1) << 8 : 0u;
+		const uint32_t mg = i < span_n ? mark[i] : 0u, m = mg & ~RANGE_MARK_GAP;
+		// a head's gap lies in front of its slot: part of what it takes, and of
+		// where its own bytes begin
+		const uint64_t g = (mg & RANGE_MARK_GAP) && m ? gap : 0u;
+		const uint64_t c = m ? 1u : 0u, s = m ? (uint64_t(m - 1) << 8) + g : 0u;
 		uint64_t total_c, total_s;
 		const uint64_t off_c = wg_excl_scan<RSCAN_WG>(c, wsum, &total_c);
 		const uint64_t off_s = wg_excl_scan<RSCAN_WG>(s, wsum, &total_s);
 		if (i < span_n) {
 			cnt[i] = uint32_t(carry_c + off_c);
-			slot[i] = carry_s + off_s;
+			slot[i] = carry_s + off_s + g;
 		}
 		carry_c += total_c;
 		carry_s += total_s;
@@ -168,10 +190,11 @@ __global__ __launch_bounds__(FILL_WG) void k_ranges_fill(SeekView v, const uint3
                                                          const uint32_t* __restrict__ cnt,
                                                          const uint64_t* __restrict__ slot, uint64_t span_lo,
                                                          uint32_t span_n, uint32_t nsel, uint64_t slots,
-                                                         lz4ada_block_desc* __restrict__ out)
+                                                         lz4ada_block_desc* __restrict__ out,
+                                                         FrameRec* __restrict__ chain)
 {
 	const uint32_t i = blockIdx.x * FILL_WG + threadIdx.x;
-	if (i >= span_n || mark[i] == 0)
+	if (i >= span_n || (mark[i] & ~RANGE_MARK_GAP) == 0)
 		return;
 	const uint32_t at = cnt[i];
 	if (at >= nsel)  // the host counted the same marks: does not happen
@@ -189,7 +212,113 @@ __global__ __launch_bounds__(FILL_WG) void k_ranges_fill(SeekView v, const uint3
 	} else {
 		d.out_cap = uint32_t(size);
 	}
+	if (chain) {
+		// the block's chain record: a head and a linked frame's marked block 0
+		// start a chain of the marked blocks of their group, the others ride
+		FrameRec r;
+		r.first = at;
+		r.nblocks = 0;
+		r.flags = 0;
+		r.hash = 0;
+		r.content_size = 0;
+		r.out_off = r.out_len = 0;
+		r.fail = -1;
+		r.verdict = 0;
+		const uint64_t K = v.kgrp ? v.kgrp[k] : 0;
+		const uint64_t j = b - v.first[k], nb = v.first[k + 1] - v.first[k];
+		const bool head = (mark[i] & RANGE_MARK_GAP) != 0;
+		if (K && d.out_cap == size && (head || j == 0)) {
+			const uint64_t ck = head ? v.ckfirst[k] + chain_checkpoint_of(K, j) : 0;
+			// a head without its gap or its checkpoint is an empty block
+			if (head && (!chain_head(K, j) || ck >= v.ckfirst[k + 1] || ck >= v.nckpt || d.out_off < CKPT_GAP)) {
+				d.in_len = 0;
+				d.flags = LZ4ADA_BLOCK_STORED;
+				d.out_cap = 0;
+				d.out_off = 0;
+			} else {
+				const uint64_t e = chain_group_end(K, nb, j);
+				uint32_t run = 1;
+				while (j + run < e && i + run < span_n && (mark[i + run] & ~RANGE_MARK_GAP) != 0)
+					++run;
+				r.flags = FRAME_LINKED;
+				r.nblocks = run;
+				r.content_size = ck;
+				if (head)
+					d.flags |= BLOCK_DICT;
+			}
+		}
+		chain[chain_slot(at, nsel)] = r;
+	}
 	out[at] = d;
+}
+
+__global__ __launch_bounds__(CKPT_WG) void k_ckpt_fill(SeekView v, const lz4ada_block_desc* __restrict__ desc,
+                                                       const FrameRec* __restrict__ chain, uint32_t nsel,
+                                                       uint8_t* __restrict__ slots_p, uint64_t slots)
+{
+	if (blockIdx.x >= nsel)
+		return;
+	const lz4ada_block_desc d = desc[blockIdx.x];
+	const FrameRec r = chain[chain_slot(blockIdx.x, nsel)];
+	if (!(d.flags & BLOCK_DICT) || !(r.flags & FRAME_LINKED) || r.content_size >= v.nckpt || d.out_off < CKPT_GAP ||
+	    d.out_off > slots)
+		return;
+	// 256-aligned on both sides: out_off and CKPT_GAP are, and the store's entries
+	g8* const dst = gptr(slots_p) + (d.out_off - CKPT_GAP);
+	cg8* const src = gptr(v.store) + r.content_size * CKPT_BYTES;
+	constexpr uint32_t ZEROS = uint32_t(CKPT_GAP - CKPT_BYTES);
+	const uint32_t t = threadIdx.x;
+	if (t < ZEROS / 16) {
+		const u32x4 z = { 0u, 0u, 0u, 0u };
+		*reinterpret_cast<GLOBAL u32x4*>(dst + 16 * t) = z;
+	}
+	for (uint32_t x = 16 * t; x < uint32_t(CKPT_BYTES); x += 16 * CKPT_WG) {
+		const u32x4 w = *reinterpret_cast<const GLOBAL u32x4*>(src + x);
+		*reinterpret_cast<GLOBAL u32x4*>(dst + ZEROS + x) = w;
+	}
+}
+
+__global__ __launch_bounds__(CKPT_WG) void k_ckpt_save(const uint64_t* __restrict__ kgrp,
+                                                       const uint64_t* __restrict__ ckfirst, uint32_t f_lo,
+                                                       uint32_t nf, uint64_t ck_lo, uint32_t nck, uint64_t nckpt,
+                                                       const lz4ada_block_desc* __restrict__ desc,
+                                                       uint32_t nblocks, FrameRec* __restrict__ rec,
+                                                       const uint8_t* __restrict__ slots_p, uint64_t slots,
+                                                       uint8_t* __restrict__ store)
+{
+	const uint32_t c_local = blockIdx.x / CKPT_SAVE_SPLIT, piece = blockIdx.x % CKPT_SAVE_SPLIT;
+	if (c_local >= nck || nf == 0)
+		return;
+	const uint64_t c = ck_lo + c_local;
+	// its frame among the pass's: the last one whose first checkpoint is not past c
+	const uint64_t* const cf = ckfirst + f_lo;
+	if (c >= nckpt || c < cf[0] || c >= cf[nf])
+		return;
+	const uint32_t f = uint32_t(rising_find(cf, nf, c));
+	const uint64_t K = kgrp[f_lo + f];
+	const FrameRec r = rec[f];
+	const uint64_t b = K ? (c - cf[f] + 1) * K : 0;
+	bool ok = K && (r.flags & FRAME_LINKED) && b < r.nblocks && uint64_t(r.first) + r.nblocks <= nblocks;
+	uint64_t at = 0;
+	if (ok) {
+		// the frame's chain is contiguous when it decoded (k_decode_idx_frames ends
+		// it otherwise), so the bytes in front of block b are the frame's own
+		// once there are enough of them
+		at = desc[r.first + b].out_off;
+		ok = at >= desc[r.first].out_off + CKPT_BYTES && at <= slots;
+	}
+	if (!ok) {
+		if (threadIdx.x == 0 && piece == 0)
+			rec[f].fail = 0;
+		return;
+	}
+	constexpr uint32_t PIECE = uint32_t(CKPT_BYTES / CKPT_SAVE_SPLIT);
+	cg8* const src = gptr(slots_p) + (at - CKPT_BYTES) + piece * PIECE;
+	g8* const dst = gptr(store) + c * CKPT_BYTES + piece * PIECE;
+	for (uint32_t x = 16 * threadIdx.x; x < PIECE; x += 16 * CKPT_WG) {
+		const u32x4 w = *reinterpret_cast<const GLOBAL u32x4*>(src + x);
+		*reinterpret_cast<GLOBAL u32x4*>(dst + x) = w;
+	}
 }
 
 __global__ __launch_bounds__(WAVE) void k_ranges_verdict(SeekView v, const RangeRec* __restrict__ ranges,
@@ -207,7 +336,10 @@ __global__ __launch_bounds__(WAVE) void k_ranges_verdict(SeekView v, const Range
 	if (k >= v.nframes)
 		return;
 	const uint64_t f = wave_uniform(v.first[k]);
-	const uint32_t b0 = wave_uniform(sel[i].first), n = wave_uniform(sel[i].count);
+	const uint32_t t0 = wave_uniform(sel[i].first), tn = wave_uniform(sel[i].count);
+	// the range's chain: a block in front of the touched ones fails it too
+	const uint64_t K = v.kgrp ? wave_uniform(v.kgrp[k]) : 0;
+	const uint32_t b0 = tn ? uint32_t(chain_start(K, t0)) : t0, n = t0 - b0 + tn;
 	int32_t fail = -1;
 	for (uint32_t j0 = 0; j0 < n; j0 += WAVE) {
 		const uint32_t j = j0 + lane_id();
@@ -272,7 +404,7 @@ __global__ __launch_bounds__(GATHER_WG) void k_ranges_gather(SeekView v, const R
 		const uint64_t in_block = x - st[j], avail = st[j + 1] - x;
 		const uint64_t take = avail < rem ? avail : rem;
 		const uint64_t b = f + j;
-		if (take && b >= span_lo && b - span_lo < span_n && mark[b - span_lo]) {
+		if (take && b >= span_lo && b - span_lo < span_n && (mark[b - span_lo] & ~RANGE_MARK_GAP)) {
 			const uint64_t at = slot[b - span_lo] + in_block;
 			if (at + take <= slots)
 				wg_copy(dst, src + at, take);
@@ -303,21 +435,42 @@ hipError_t launch_ranges_select(const SeekView& v, const RangeRec* d_ranges, uin
 	return hipGetLastError();
 }
 
-hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint32_t* d_cnt, uint64_t* d_slot,
-                              hipStream_t stream)
+hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t gap, uint32_t* d_cnt,
+                              uint64_t* d_slot, hipStream_t stream)
 {
-	hipLaunchKernelGGL(k_ranges_scan, dim3(1), dim3(RSCAN_WG), 0, stream, d_mark, span_n, d_cnt, d_slot);
+	hipLaunchKernelGGL(k_ranges_scan, dim3(1), dim3(RSCAN_WG), 0, stream, d_mark, span_n, gap, d_cnt, d_slot);
 	return hipGetLastError();
 }
 
 hipError_t launch_ranges_fill(const SeekView& v, const uint32_t* d_mark, const uint32_t* d_cnt,
                               const uint64_t* d_slot, uint64_t span_lo, uint32_t span_n, uint32_t nsel,
-                              uint64_t slots, lz4ada_block_desc* d_desc, hipStream_t stream)
+                              uint64_t slots, lz4ada_block_desc* d_desc, FrameRec* d_chain, hipStream_t stream)
 {
 	if (span_n == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_ranges_fill, dim3((span_n + FILL_WG - 1) / FILL_WG), dim3(FILL_WG), 0, stream, v, d_mark,
-	                   d_cnt, d_slot, span_lo, span_n, nsel, slots, d_desc);
+	                   d_cnt, d_slot, span_lo, span_n, nsel, slots, d_desc, d_chain);
+	return hipGetLastError();
+}
+
+hipError_t launch_ckpt_fill(const SeekView& v, const lz4ada_block_desc* d_desc, const FrameRec* d_chain,
+                            uint32_t nsel, uint8_t* d_slots, uint64_t slots, hipStream_t stream)
+{
+	if (nsel == 0 || v.nckpt == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_ckpt_fill, dim3(nsel), dim3(CKPT_WG), 0, stream, v, d_desc, d_chain, nsel, d_slots, slots);
+	return hipGetLastError();
+}
+
+hipError_t launch_ckpt_save(const uint64_t* d_kgrp, const uint64_t* d_ckfirst, uint32_t f_lo, uint32_t nf,
+                            uint64_t ck_lo, uint32_t nck, uint64_t nckpt, const lz4ada_block_desc* d_desc,
+                            uint32_t nblocks, FrameRec* d_rec, const uint8_t* d_slots, uint64_t slots,
+                            uint8_t* d_store, hipStream_t stream)
+{
+	if (nck == 0 || nf == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_ckpt_save, dim3(nck * CKPT_SAVE_SPLIT), dim3(CKPT_WG), 0, stream, d_kgrp, d_ckfirst, f_lo, nf,
+	                   ck_lo, nck, nckpt, d_desc, nblocks, d_rec, d_slots, slots, d_store);
 	return hipGetLastError();
 }
 

@@ -208,6 +208,14 @@ class FrameRange(ctypes.Structure):
                 ("status", ctypes.c_int32), ("reason", ctypes.c_int32)]
 
 
+class SeekOptions(ctypes.Structure):
+    """lz4ada_seek_options: flags (SEEK_LINKED), reserved (0), checkpoint_bytes
+    (decoded bytes between history checkpoints; 0: the default, 1 MiB)."""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("checkpoint_bytes", ctypes.c_int64)]
+
+
+SEEK_LINKED = 1  # SeekOptions.flags: the index takes linked frames, with checkpoints
+
 # DeviceFrameJob.reason: 1..4 are the BATCH_* reasons
 DEVFRAME_OK, DEVFRAME_BLOCK, DEVFRAME_SIZE, DEVFRAME_CHECKSUM = 0, 5, 6, 7
 DEVFRAME_DICT = 8  # the frame names another dictionary id (DeviceDict with DICT_CHECK_ID)
@@ -256,6 +264,8 @@ _sig = {
     "lz4ada_frames_device_sizes": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, _pi64, _vp], ctypes.c_int),
     "lz4ada_block_size_host": ([_vp, _i64, ctypes.c_int], _i64),
     "lz4ada_seek_index_build": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_seek_index_build_opt": ([_vp, _i64, _vp, _i64, _vp, ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_range_chains_host": ([_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _pi64], ctypes.c_int),
     "lz4ada_seek_index_free": ([_vp], None),
     "lz4ada_seek_index_bytes": ([_vp], _i64),
     "lz4ada_decode_ranges_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, _pi64, _vp], ctypes.c_int),
@@ -808,21 +818,32 @@ class SeekIndex:
         self._ptr, self.jobs, self.njobs, self.in_len = ptr, jobs, njobs, in_len
 
     @classmethod
-    def build(cls, d_in: int, in_len: int, spans, stream: int = 0, flags: int = 0):
+    def build(cls, d_in: int, in_len: int, spans, stream: int = 0, flags: int = 0, linked: bool = False,
+              checkpoint_bytes: int = 0):
         """Index the frames at spans [(in_off, in_len)] of the device buffer
-        d_in (raw pointer).  Linked frames are refused (BATCH_LINKED)."""
+        d_in (raw pointer).  Linked frames are refused (BATCH_LINKED) unless
+        linked is set: then the build decodes each once and keeps a history
+        checkpoint every checkpoint_bytes decoded bytes (0: 1 MiB), through
+        lz4ada_seek_index_build_opt.  flags goes to
+        lz4ada_seek_index_build as it is."""
         jobs = _device_jobs(spans)
         ptr = _vp()
-        _check(_lib.lz4ada_seek_index_build(d_in, in_len, jobs, len(spans), flags, ctypes.byref(ptr), stream),
-               _thread_error())
+        if linked or checkpoint_bytes:
+            opt = SeekOptions(SEEK_LINKED if linked else 0, 0, checkpoint_bytes)
+            st = _lib.lz4ada_seek_index_build_opt(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
+                                                  ctypes.byref(ptr), stream)
+        else:
+            st = _lib.lz4ada_seek_index_build(d_in, in_len, jobs, len(spans), flags, ctypes.byref(ptr), stream)
+        _check(st, _thread_error())
         return cls(ptr.value, jobs, len(spans), in_len)
 
     @classmethod
-    def build_tensor(cls, t, spans):
+    def build_tensor(cls, t, spans, linked: bool = False, checkpoint_bytes: int = 0):
         """build for a CUDA torch.uint8 tensor, on torch's current stream."""
         _frames_tensor(t)
         with torch.cuda.device(t.device):
-            return cls.build(t.data_ptr(), t.numel(), spans, torch.cuda.current_stream().cuda_stream)
+            return cls.build(t.data_ptr(), t.numel(), spans, torch.cuda.current_stream().cuda_stream,
+                             linked=linked, checkpoint_bytes=checkpoint_bytes)
 
     @property
     def device_bytes(self) -> int:
@@ -927,6 +948,22 @@ def range_blocks_host(starts, off: int, len: int):
     block, count, clipped length)."""
     first, count, want = range_blocks_host_many(starts, [off], [len])
     return first[0], count[0], want[0]
+
+
+def range_chains_host(nblocks: int, group: int, touched):
+    """Test-only: the chain rule on the host (lz4ada_range_chains.h) for one
+    linked frame of nblocks blocks in groups of `group` and the touched
+    intervals [(first, count)] of its ranges -> (marked blocks, heads, chains
+    as [(first, count)]), the first two as sorted lists of block numbers."""
+    n = _len(touched)
+    first = (_i64 * max(n, 1))(*[t[0] for t in touched])
+    count = (_i64 * max(n, 1))(*[t[1] for t in touched])
+    marked, head = (ctypes.c_uint8 * max(nblocks, 1))(), (ctypes.c_uint8 * max(nblocks, 1))()
+    cf, cc, nc = (_i64 * max(nblocks, 1))(), (_i64 * max(nblocks, 1))(), _i64()
+    _check(_lib.lz4ada_range_chains_host(nblocks, group, first, count, n, marked, head, cf, cc, ctypes.byref(nc)),
+           "range_chains_host: a NULL or out-of-range argument")
+    return ([b for b in range(nblocks) if marked[b]], [b for b in range(nblocks) if head[b]],
+            [(cf[i], cc[i]) for i in range(nc.value)])
 
 
 def seek_index_debug(idx: SeekIndex, stream: int = 0):

@@ -708,7 +708,8 @@ int lz4ada_decode_frame_dict_host(const uint8_t *frame, int64_t len, const uint8
  * lz4ada_frames_device_sizes runs them -- every job gets the same status,
  * reason and out_len = exact decoded size -- and then the table is kept.
  * flags must be 0: a linked frame is refused with LZ4ADA_BATCH_LINKED, since a
- * block of a linked frame needs every block before it.  njobs == 0 builds an
+ * block of a linked frame needs the output before it (lz4ada_seek_index_build_opt
+ * below takes them, with history checkpoints).  njobs == 0 builds an
  * empty index without a device call.  On failure *idx is NULL.  Synchronous
  * on stream; host synchronisations: the two of lz4ada_frames_device_sizes and
  * one that ends the build, after which the index never changes.  Any number of
@@ -771,6 +772,65 @@ int lz4ada_seek_index_build(const void *d_in, int64_t in_len,
 void lz4ada_seek_index_free(lz4ada_seek_index *idx);
 int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index *idx);
 
+/*
+ * Linked frames in the seek index, through history checkpoints (DESIGN.md
+ * section 16).  lz4ada_seek_index_build_opt with opt == NULL or opt->flags == 0
+ * is lz4ada_seek_index_build(..., 0, ...) launch by launch.  With
+ * LZ4ADA_SEEK_LINKED the index stage runs as the many-frame pass does with
+ * LZ4ADA_FRAMES_LINKED: a linked modern frame of at most
+ * lz4ada_batch_linked_max() slot bytes is taken (above it: LZ4ADA_BATCH_LINKED,
+ * as before), and the build decodes every such frame once, in passes under
+ * LZ4ADA_BATCH_BYTES into the calling thread's scratch (one more host
+ * synchronisation per pass; lz4ada_last_batch_stats().passes counts them).  A
+ * frame whose chain fails there -- a declined block, a bad block checksum,
+ * quirk D1's round state -- gets LZ4ADA_EXACT_PATH / LZ4ADA_DEVFRAME_BLOCK and
+ * out_len 0 in the job report and for every later range.  The content checksum
+ * is not asserted.
+ *
+ * Checkpoints: per linked frame K = max(1, ceil(checkpoint_bytes / block_max))
+ * blocks form a group (checkpoint_bytes == 0: 1 MiB), and for every group start
+ * b = K, 2K, ... < nblocks the index keeps the 65,536 decoded bytes in front of
+ * block b.  lz4ada_seek_index_bytes, exactly, with nb the blocks of the accepted
+ * frames and n the jobs:
+ *     32 * nb + 8 * (n + 1) + 16 * (nb + n)                  any index with n > 0
+ *   + 65536 * C + 8 * (n + 1) + 8 * n                        LZ4ADA_SEEK_LINKED, n > 0
+ * where C is the sum of (nblocks - 1) / K (integer division) over the linked
+ * frames with blocks that the sizes stage accepted (a frame whose chain then
+ * fails at the build keeps its share of the store).
+ *
+ * A range of a linked frame decodes its chain: the blocks from the start of
+ * the group of its first touched block to its last touched block, every group
+ * in a wave of its own from its checkpoint, so the cost of a range no longer
+ * grows with its distance from the frame's start.  Everything
+ * lz4ada_decode_ranges_device says above holds, with these additions:
+ *  - the range fails with LZ4ADA_DEVFRAME_BLOCK when any block of its chain
+ *    fails, touched or not;
+ *  - a range whose chain's slots and gaps (65,792 bytes in front of every
+ *    group start but block 0) exceed LZ4ADA_BATCH_BYTES is
+ *    LZ4ADA_BATCH_OVER_BUDGET in place;
+ *  - a delivered range asserts its chain's blocks (decoded, block checksums)
+ *    and, at the build, the whole frame's; the bytes are the reference's,
+ *    since the build refused quirk D1's round state;
+ *  - if the input changed since the build, a group whose own blocks are
+ *    unchanged still delivers what the build saw: its history is the
+ *    checkpoint;
+ *  - lz4ada_last_path() carries LZ4ADA_PATH_LINKED when a linked range was
+ *    delivered.
+ * Misuse, LZ4ADA_ASSERTION_ERROR before any device call with *idx = NULL:
+ * unknown bits in opt->flags, opt->reserved != 0, opt->checkpoint_bytes < 0,
+ * and everything lz4ada_seek_index_build calls misuse.
+ */
+#define LZ4ADA_SEEK_LINKED 1u /* opt->flags: take linked frames, with checkpoints */
+typedef struct {
+	uint32_t flags;           /* LZ4ADA_SEEK_* */
+	uint32_t reserved;        /* must be 0 */
+	int64_t checkpoint_bytes; /* decoded bytes between checkpoints; 0: the default */
+} lz4ada_seek_options;
+int lz4ada_seek_index_build_opt(const void *d_in, int64_t in_len,
+                                lz4ada_device_frame_job *jobs, int64_t njobs,
+                                const lz4ada_seek_options *opt,
+                                lz4ada_seek_index **idx, void *stream);
+
 typedef struct {
 	int64_t job;              /* in: which of the njobs frames the index was built over */
 	int64_t off, len;         /* in: decoded bytes [off, off + len) of that frame */
@@ -793,6 +853,17 @@ int lz4ada_decode_ranges_device(const lz4ada_seek_index *idx, const void *d_in, 
 int lz4ada_range_blocks_host(const uint64_t *start, int64_t nblocks, const int64_t *off,
                              const int64_t *len, int64_t n, int64_t *first, int64_t *count,
                              int64_t *want);
+/* The chain rule on the host (lz4ada_range_chains.h, the statement the ranged
+ * decode's kernels and its host sweep run), for one linked frame of nblocks
+ * blocks in groups of `group` (0: independent blocks) and the touched
+ * intervals [first[i], first[i] + count[i]) of n ranges (count 0: none):
+ * marked[b] / head[b] (nblocks bytes each, 0 or 1) and the chains in rising
+ * order as chain_first / chain_count (room for nblocks), *nchains of them.
+ * LZ4ADA_ASSERTION_ERROR on a NULL or out-of-range argument.  Host only, no
+ * HIP call. */
+int lz4ada_range_chains_host(int64_t nblocks, int64_t group, const int64_t *first,
+                             const int64_t *count, int64_t n, uint8_t *marked, uint8_t *head,
+                             int64_t *chain_first, int64_t *chain_count, int64_t *nchains);
 /* One job of an index: its reason (0: accepted), its block count, and, when
  * start is not NULL, its start[0 .. nblocks] copied to the host (start_cap
  * entries of room). */
@@ -800,8 +871,8 @@ int lz4ada_seek_index_debug(const lz4ada_seek_index *idx, int64_t job, int32_t *
                             int64_t *nblocks, uint64_t *start, int64_t start_cap, void *stream);
 /* k_ranges_select and the marks of one pass over all the ranges, nothing
  * decoded: per range its first touched block and their count (frame-relative;
- * 0, 0 for an empty range), and *marked: the blocks marked once shared ones
- * count once.  ranges gets out_off, out_len, status and reason as the index
+ * 0, 0 for an empty range), and *marked: the blocks a pass would decode once
+ * shared ones count once (in a linked frame the chains' blocks, section 16).  ranges gets out_off, out_len, status and reason as the index
  * alone gives them. */
 int lz4ada_ranges_select_debug(const lz4ada_seek_index *idx, lz4ada_frame_range *ranges,
                                int64_t nranges, int64_t *first, int64_t *count, int64_t *marked,
