@@ -21,34 +21,6 @@ void set_thread_error(const std::string& msg);  // lz4ada_host_common.cpp
 
 namespace {
 
-constexpr uint32_t XP1 = 2654435761u, XP2 = 2246822519u, XP3 = 3266489917u, XP4 = 668265263u, XP5 = 374761393u;
-
-uint32_t xxh32_host(const uint8_t* p, int64_t n)
-{
-	const uint8_t* const end = p + n;
-	uint32_t h;
-	if (n >= 16) {
-		uint32_t v1 = XP1 + XP2, v2 = XP2, v3 = 0, v4 = 0u - XP1;
-		for (; end - p >= 16; p += 16) {
-			v1 = walk_rotl(v1 + walk_load32(p) * XP2, 13) * XP1;
-			v2 = walk_rotl(v2 + walk_load32(p + 4) * XP2, 13) * XP1;
-			v3 = walk_rotl(v3 + walk_load32(p + 8) * XP2, 13) * XP1;
-			v4 = walk_rotl(v4 + walk_load32(p + 12) * XP2, 13) * XP1;
-		}
-		h = walk_rotl(v1, 1) + walk_rotl(v2, 7) + walk_rotl(v3, 12) + walk_rotl(v4, 18);
-	} else {
-		h = XP5;
-	}
-	h += uint32_t(n);
-	for (; end - p >= 4; p += 4)
-		h = walk_rotl(h + walk_load32(p) * XP3, 17) * XP4;
-	for (; p < end; ++p)
-		h = walk_rotl(h + uint32_t(*p) * XP5, 11) * XP1;
-	h = (h ^ (h >> 15)) * XP2;
-	h = (h ^ (h >> 13)) * XP3;
-	return h ^ (h >> 16);
-}
-
 struct Fail {
 	int code;
 	std::string msg;
@@ -196,7 +168,7 @@ int decode(const uint8_t* p, int64_t len, const uint8_t* dict, int64_t dict_len,
 			return fail(LZ4ADA_DATA_CORRUPTION, "dictionary decode: a block is larger than the block maximum");
 		if (pos + int64_t(word) + (bck ? 4 : 0) > len)
 			return fail(LZ4ADA_DATA_CORRUPTION, "dictionary decode: the frame is truncated");
-		if (bck && xxh32_host(p + pos, word) != walk_load32(p + pos + word))
+		if (bck && walk_xxh32(p + pos, word) != walk_load32(p + pos + word))
 			return fail(LZ4ADA_CHECKSUM_ERROR, "dictionary decode: block checksum");
 		if (stored) {
 			if (int64_t(word) > out_cap - opos)
@@ -219,7 +191,7 @@ int decode(const uint8_t* p, int64_t len, const uint8_t* dict, int64_t dict_len,
 	if (cck) {
 		if (pos + 4 > len)
 			return fail(LZ4ADA_DATA_CORRUPTION, "dictionary decode: the frame is truncated");
-		if (xxh32_host(out, opos) != walk_load32(p + pos))
+		if (walk_xxh32(out, opos) != walk_load32(p + pos))
 			return fail(LZ4ADA_CHECKSUM_ERROR, "dictionary decode: content checksum");
 		pos += 4;
 	}

@@ -79,6 +79,35 @@ LZ4ADA_HD inline uint32_t walk_descriptor_xxh32(const uint8_t* p, int64_t n)
 	return h ^ (h >> 16);
 }
 
+// XXH32, seed 0, of n bytes, serially: the block and content checksums of the
+// host statements (lz4ada_dict_host.cpp, lz4ada_compress_host.cpp).
+inline uint32_t walk_xxh32(const uint8_t* p, int64_t n)
+{
+	constexpr uint32_t P1 = 2654435761u, P2 = 2246822519u, P3 = 3266489917u, P4 = 668265263u, P5 = 374761393u;
+	const uint8_t* const end = p + n;
+	uint32_t h;
+	if (n >= 16) {
+		uint32_t v1 = P1 + P2, v2 = P2, v3 = 0, v4 = 0u - P1;
+		for (; end - p >= 16; p += 16) {
+			v1 = walk_rotl(v1 + walk_load32(p) * P2, 13) * P1;
+			v2 = walk_rotl(v2 + walk_load32(p + 4) * P2, 13) * P1;
+			v3 = walk_rotl(v3 + walk_load32(p + 8) * P2, 13) * P1;
+			v4 = walk_rotl(v4 + walk_load32(p + 12) * P2, 13) * P1;
+		}
+		h = walk_rotl(v1, 1) + walk_rotl(v2, 7) + walk_rotl(v3, 12) + walk_rotl(v4, 18);
+	} else {
+		h = P5;
+	}
+	h += uint32_t(n);
+	for (; end - p >= 4; p += 4)
+		h = walk_rotl(h + walk_load32(p) * P3, 17) * P4;
+	for (; p < end; ++p)
+		h = walk_rotl(h + uint32_t(*p) * P5, 11) * P1;
+	h = (h ^ (h >> 15)) * P2;
+	h = (h ^ (h >> 13)) * P3;
+	return h ^ (h >> 16);
+}
+
 LZ4ADA_HD inline bool walk_is_any_magic(uint32_t v)
 {
 	return v == 0x184d2204u || v == 0x184c2102u || (v >= 0x184d2a50u && v <= 0x184d2a5fu);

@@ -589,4 +589,50 @@ hipError_t launch_ranges_gather(const SeekView& v, const RangeRec* d_ranges, uin
                                 const uint64_t* d_slot, uint64_t span_lo, uint32_t span_n, const uint8_t* d_slots,
                                 uint64_t slots, uint8_t* d_out, hipStream_t stream);
 
+// ---- records compressed into frames (lz4ada_compress.hip) ----
+// One block of a pass: its bytes inside d_in, its scratch slot (of at least
+// len bytes), the job it belongs to.  The host fills them: it knows every length.
+struct CompBlock {
+	uint64_t in_off, slot_off;
+	uint32_t len, job;
+};
+// One job of a pass: its record, its blocks among the pass's, and the header
+// and trailer bytes of the pass's earlier jobs.
+struct CompJob {
+	uint64_t in_off, in_len;
+	uint64_t fixed_before;
+	uint32_t first, nblocks;
+};
+// What a pass reports per job: its frame inside d_out and its stored blocks
+// (counted by atomic adds: zeroed by the caller).
+struct CompJobRec {
+	uint64_t out_off, out_len;
+	uint32_t stored, pad;
+};
+// One wave per block: block b compressed into its slot, d_csize[b] its length
+// there, or 0 for a block to be stored (the compressed form would not be
+// shorter).  Writes inside [slot_off, slot_off + len - 1) only.
+hipError_t launch_compress_blocks(const uint8_t* d_in, const CompBlock* d_blk, uint32_t nblocks, uint8_t* d_slots,
+                                  uint32_t* d_csize, hipStream_t stream);
+// The exclusive prefix sum of the blocks' bytes in the output (size word,
+// payload, checksum under `flags`): block b's is d_part[b / PLAN_TILE] +
+// d_loc[b], the total d_part[plan_tiles(nblocks)].  nblocks may be 0.
+hipError_t launch_compress_scan(const CompBlock* d_blk, const uint32_t* d_csize, uint32_t nblocks, uint32_t flags,
+                                uint64_t* d_loc, uint64_t* d_part, hipStream_t stream);
+// One workgroup per block: size word and payload into d_out (the pass begins
+// at d_out + base), d_desc[b] the payload inside d_out, d_rec[job].stored.
+hipError_t launch_compress_emit(const uint8_t* d_in, const uint8_t* d_slots, const CompBlock* d_blk,
+                                const uint32_t* d_csize, const uint64_t* d_loc, const uint64_t* d_part,
+                                const CompJob* d_jobs, uint32_t nblocks, uint32_t flags, uint64_t base, uint8_t* d_out,
+                                lz4ada_block_desc* d_desc, CompJobRec* d_rec, hipStream_t stream);
+// d_st[b].cksum (launch_block_checksums over d_out and d_desc) behind every payload.
+hipError_t launch_compress_block_cksums(const lz4ada_block_desc* d_desc, const lz4ada_block_status* d_st,
+                                        uint32_t nblocks, uint8_t* d_out, hipStream_t stream);
+// One thread per job: header, end mark, the content checksum when d_frec[j]
+// carries one (launch_xxh32_spans over d_in; d_frec may be null without
+// LZ4ADA_COMP_CONTENT_CHECKSUM), and d_rec[j].out_off / out_len.
+hipError_t launch_compress_frames(const CompJob* d_jobs, uint32_t njobs, const uint64_t* d_loc, const uint64_t* d_part,
+                                  uint32_t nblocks, uint32_t block_id, uint32_t flags, uint64_t base,
+                                  const FrameRec* d_frec, uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream);
+
 }  // namespace lz4ada

@@ -216,6 +216,21 @@ class SeekOptions(ctypes.Structure):
 
 SEEK_LINKED = 1  # SeekOptions.flags: the index takes linked frames, with checkpoints
 
+
+class CompressOptions(ctypes.Structure):
+    """lz4ada_compress_options: block_id (4..7 = 64 KiB..4 MiB; 0 means 4), flags (COMP_*)."""
+    _fields_ = [("block_id", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
+class CompressJob(ctypes.Structure):
+    """One record of compress_frames_device and, after the call, its frame."""
+    _fields_ = [("in_off", ctypes.c_int64), ("in_len", ctypes.c_int64), ("out_off", ctypes.c_int64),
+                ("out_len", ctypes.c_int64), ("status", ctypes.c_int32), ("stored_blocks", ctypes.c_int32)]
+
+
+COMP_BLOCK_CHECKSUM, COMP_CONTENT_CHECKSUM, COMP_CONTENT_SIZE = 1, 2, 4
+_COMP_BLOCK_ID = {65536: 4, 262144: 5, 1 << 20: 6, 4 << 20: 7}
+
 # DeviceFrameJob.reason: 1..4 are the BATCH_* reasons
 DEVFRAME_OK, DEVFRAME_BLOCK, DEVFRAME_SIZE, DEVFRAME_CHECKSUM = 0, 5, 6, 7
 DEVFRAME_DICT = 8  # the frame names another dictionary id (DeviceDict with DICT_CHECK_ID)
@@ -278,6 +293,10 @@ _sig = {
                                        ctypes.c_int),
     "lz4ada_frames_index_device_debug": ([_vp, _i64, _vp, _i64, ctypes.POINTER(ctypes.c_int32), _pi64,
                                           _vp, _i64, _vp], ctypes.c_int),
+    "lz4ada_compress_frames_bound": ([_vp, _i64, _vp], _i64),
+    "lz4ada_compress_frames_device": ([_vp, _i64, _vp, _i64, _vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_compress_block_host": ([_vp, _i64, _vp, _i64], _i64),
+    "lz4ada_compress_frame_host": ([_vp, _i64, _vp, _vp, _i64], _i64),
     "lz4ada_abi_version": ([], ctypes.c_int),
     "lz4ada_device_check": ([], ctypes.c_int),
     "lz4ada_error_name": ([ctypes.c_int], ctypes.c_char_p),
@@ -801,6 +820,110 @@ def decode_frames_tensor(t, spans, out=None, linked=False, exact=False, dict=Non
         n, jobs = decode_frames_device(t.data_ptr(), t.numel(), spans, out.data_ptr(), out.numel(),
                                        stream, linked, exact, dd)
     return out[:n], jobs
+
+
+# ------------------- records compressed into frames, device memory to device
+# 
+
+def _compress_options(block, block_checksum, content_checksum, content_size):
+    """block: the block maximum in bytes (65536, 262144, 1 MiB, 4 MiB) or a
+    block id as it is (0, 4..7, and whatever a misuse test passes)."""
+    return CompressOptions(_COMP_BLOCK_ID.get(block, block),
+                           (COMP_BLOCK_CHECKSUM if block_checksum else 0)
+                           | (COMP_CONTENT_CHECKSUM if content_checksum else 0)
+                           | (COMP_CONTENT_SIZE if content_size else 0))
+
+
+def _compress_jobs(spans):
+    jobs = (CompressJob * max(len(spans), 1))()
+    for j, (off, n) in zip(jobs, spans):
+        j.in_off, j.in_len = off, n
+    return jobs
+
+
+def compress_frames_bound(lens, block=65536, block_checksum=False, content_checksum=False, content_size=False):
+    """An out_cap that always suffices for records of these lengths, one frame
+    each: the header's exact worst-case arithmetic (every block stored).  No
+    GPU involved."""
+    opt = _compress_options(block, block_checksum, content_checksum, content_size)
+    jobs = _compress_jobs([(0, n) for n in lens])
+    bound = int(_lib.lz4ada_compress_frames_bound(jobs, len(lens), ctypes.byref(opt)))
+    if bound < 0:
+        raise AssertionFailure("lz4ada_compress_frames_bound: a negative length, or options out of range")
+    return bound
+
+
+def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0, block=65536,
+                           block_checksum=False, content_checksum=False, content_size=False):
+    """Compress the records at spans [(in_off, in_len)] of the device buffer
+    d_in into LZ4 frames laid back to back into the device buffer d_out (raw
+    pointers) -> (bytes written, the CompressJob array: out_off, out_len,
+    status, stored_blocks).  TooLittleMemory carries the needed size as .bound
+    and leaves d_out untouched."""
+    opt = _compress_options(block, block_checksum, content_checksum, content_size)
+    jobs = _compress_jobs(spans)
+    n = _i64()
+    st = _lib.lz4ada_compress_frames_device(d_in, in_len, jobs, len(spans), ctypes.byref(opt), d_out, out_cap,
+                                            ctypes.byref(n), stream)
+    if st:
+        exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
+        exc.bound = n.value
+        raise exc
+    return n.value, jobs
+
+
+def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False, content_checksum=False,
+                           content_size=False):
+    """compress_frames_device for a CUDA torch.uint8 tensor holding the
+    records, on torch's current stream -> (the frames as a uint8 tensor on the
+    same device, [(off, len)] of every record's frame inside it).  out: a uint8
+    tensor there to write into; by default one of compress_frames_bound bytes
+    is allocated."""
+    if torch is None:
+        raise RuntimeError("compress_frames_tensor needs torch")
+    if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+        raise ValueError("the records must be a contiguous CUDA uint8 tensor")
+    kw = dict(block=block, block_checksum=block_checksum, content_checksum=content_checksum,
+              content_size=content_size)
+    with torch.cuda.device(t.device):
+        if out is None:
+            out = torch.empty(max(compress_frames_bound([n for _, n in spans], **kw), 1), dtype=torch.uint8,
+                              device=t.device)
+        elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8 and out.is_contiguous()):
+            raise ValueError("out must be a contiguous CUDA uint8 tensor on the records' device")
+        n, jobs = compress_frames_device(t.data_ptr() if t.numel() else None, t.numel(), spans, out.data_ptr(),
+                                         out.numel(), torch.cuda.current_stream().cuda_stream, **kw)
+    return out[:n], [(jobs[i].out_off, jobs[i].out_len) for i in range(len(spans))]
+
+
+def compress_block_host(data, cap=None) -> bytes:
+    """The serial statement of the block compressor (no GPU involved): data as
+    one LZ4 block of at most cap bytes (default: whatever it takes) -> the
+    block, or b"" when it does not fit into cap bytes."""
+    data = bytes(data)
+    if cap is None:
+        cap = len(data) + len(data) // 255 + 16
+    buf = ctypes.create_string_buffer(max(cap, 1))
+    n = int(_lib.lz4ada_compress_block_host(_addr(data) if data else None, len(data), buf, cap))
+    if n < 0:
+        raise AssertionFailure("lz4ada_compress_block_host: a NULL pointer or a length out of range")
+    return buf.raw[:n]
+
+
+def compress_frame_host(data, block=65536, block_checksum=False, content_checksum=False, content_size=False,
+                        cap=None) -> bytes:
+    """The serial statement of one frame (no GPU involved): the bytes
+    compress_frames_device writes for this record.  cap: the destination's
+    size (default: the bound); below the bound: TooLittleMemory."""
+    data = bytes(data)
+    opt = _compress_options(block, block_checksum, content_checksum, content_size)
+    if cap is None:
+        cap = compress_frames_bound([len(data)], block, block_checksum, content_checksum, content_size)
+    buf = ctypes.create_string_buffer(max(cap, 1))
+    n = int(_lib.lz4ada_compress_frame_host(_addr(data) if data else None, len(data), ctypes.byref(opt), buf, cap))
+    if n < 0:
+        raise _ERRORS.get(-n, LZ4AdaError)(f"lz4ada_compress_frame_host: {error_name(-n)}")
+    return buf.raw[:n]
 
 
 # ----------------------------- seek index and ranged decode (DESIGN.md §14)

@@ -878,6 +878,77 @@ int lz4ada_ranges_select_debug(const lz4ada_seek_index *idx, lz4ada_frame_range 
                                int64_t nranges, int64_t *first, int64_t *count, int64_t *marked,
                                void *stream);
 
+/* ------------------------ records compressed into frames, device to device */
+/*
+ * The write side of the device calls above: every job's
+ * record, in_len bytes at d_in + in_off, becomes one LZ4 frame (format 1.6.x,
+ * version 01, independent blocks, no dictionary id) and the frames are laid
+ * back to back into d_out in job order, the first at d_out: a job's out_off /
+ * out_len say where its frame lies, *out_len is their sum, and nothing at or
+ * beyond d_out + *out_len is written.  Jobs may overlap in d_in and come in any
+ * order of in_off; in_len may be 0 (header, end mark and, if asked for, the
+ * checksum).  opt == NULL is {0, 0}.  opt->block_id: the frame's block maximum,
+ * 4..7 = 64 KiB, 256 KiB, 1 MiB, 4 MiB; 0 means 4.  One wave compresses one
+ * block, so a 4 MiB block is one wave's serial work and 64 KiB is the default.
+ * opt->flags: LZ4ADA_COMP_BLOCK_CHECKSUM (XXH32 of every block's payload as
+ * written), LZ4ADA_COMP_CONTENT_CHECKSUM (XXH32 of the record after the end
+ * mark), LZ4ADA_COMP_CONTENT_SIZE (the 8-byte content size in the header).  A
+ * block is stored (size word bit 31) whenever its compressed form is not
+ * shorter than the block; stored_blocks counts a job's.
+ *
+ * The bound, exact worst-case arithmetic (every block stored): per frame
+ *   7 + (CONTENT_SIZE ? 8 : 0)
+ *   + nblocks * (4 + (BLOCK_CHECKSUM ? 4 : 0)) + in_len
+ *   + 4 + (CONTENT_CHECKSUM ? 4 : 0),      nblocks = ceil(in_len / block_len),
+ * and lz4ada_compress_frames_bound is its sum over the jobs (host only, no HIP
+ * call; -1 on the misuse below).  out_cap below the bound:
+ * LZ4ADA_TOO_LITTLE_MEMORY with *out_len set to the bound and d_out untouched.
+ * API misuse, LZ4ADA_ASSERTION_ERROR before any launch: a NULL jobs / d_in /
+ * d_out / out_len where one is needed, a range outside [0, in_len), a block_id
+ * outside {0, 4..7}, unknown flag bits.  No GPU: LZ4ADA_DEVICE_ERROR.
+ *
+ * The host synchronises `stream` once per call for the per-job results (once
+ * per pass when the blocks' scratch slots exceed LZ4ADA_BATCH_BYTES and the
+ * jobs are cut into passes).  No payload byte crosses to the host, except that
+ * a content checksum over more than lz4ada_batch_hash_max() bytes is hashed by
+ * the host chain (lz4ada_content_xxh32_d2h with no host destination), which
+ * costs a synchronisation more.
+ *
+ * Every LZ4F decoder reads the frames: this library's calls without any flag,
+ * liblz4.  The compressor is its own (no reference twin, as with dictionaries):
+ * lz4ada_compress_block_host states the matching rule serially and the kernel
+ * produces the same bytes, so lz4ada_compress_frame_host(record) is bytewise
+ * what the device call writes for that job.
+ */
+#define LZ4ADA_COMP_BLOCK_CHECKSUM   1u
+#define LZ4ADA_COMP_CONTENT_CHECKSUM 2u
+#define LZ4ADA_COMP_CONTENT_SIZE     4u
+typedef struct {
+	uint32_t block_id; /* 4..7 = 64 KiB..4 MiB; 0 means 4 */
+	uint32_t flags;    /* LZ4ADA_COMP_* */
+} lz4ada_compress_options;
+typedef struct {
+	int64_t in_off, in_len;   /* in: the record inside d_in (in_len may be 0) */
+	int64_t out_off, out_len; /* out: its frame inside d_out */
+	int32_t status;           /* out */
+	int32_t stored_blocks;    /* out: blocks written uncompressed */
+} lz4ada_compress_job;
+int64_t lz4ada_compress_frames_bound(const lz4ada_compress_job *jobs, int64_t njobs,
+                                     const lz4ada_compress_options *opt);
+int lz4ada_compress_frames_device(const void *d_in, int64_t in_len, lz4ada_compress_job *jobs,
+                                  int64_t njobs, const lz4ada_compress_options *opt, void *d_out,
+                                  int64_t out_cap, int64_t *out_len, void *stream);
+/* The serial statement of the block compressor: src[0 .. n) as one LZ4 block
+ * into dst[0 .. cap) -> its length, 0 when it does not fit into cap bytes
+ * (nothing beyond dst + cap is written), -1 on a NULL pointer, a negative
+ * length or n over 0x7E000000.  Host only, no HIP call. */
+int64_t lz4ada_compress_block_host(const uint8_t *src, int64_t n, uint8_t *dst, int64_t cap);
+/* One record as one frame, as the device call writes it -> the frame's length;
+ * -LZ4ADA_TOO_LITTLE_MEMORY when cap is below the bound above (dst untouched),
+ * -LZ4ADA_ASSERTION_ERROR on the misuse above.  Host only, no HIP call. */
+int64_t lz4ada_compress_frame_host(const uint8_t *src, int64_t n, const lz4ada_compress_options *opt,
+                                   uint8_t *dst, int64_t cap);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
