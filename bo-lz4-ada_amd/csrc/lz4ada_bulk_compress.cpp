@@ -18,15 +18,22 @@ using namespace lz4ada;
 namespace lz4ada {
 namespace {
 
-constexpr const char* ENTRY = "lz4ada_compress_frames_device";
+// A call's dictionary: its used tail (dl bytes, 0: none, the plain kernel) and
+// the seeded table on the device; the header's flags and id.
+struct PassDict {
+	const uint8_t* d_tail = nullptr;
+	uint32_t dl = 0;
+	const uint32_t* d_seed = nullptr;
+	uint32_t dflags = 0, dict_id = 0;
+};
 
 inline size_t up16(size_t v) { return (v + 15) & ~size_t(15); }
 
 // One pass over the jobs [lo, hi), nb blocks and slot_b slot bytes in all:
 // their frames go to d_out from *base on, which then moves past them.
-void compress_pass(const uint8_t* d_in, lz4ada_compress_job* jobs, size_t lo, size_t hi, uint64_t nb64,
-                   uint64_t slot_b, uint32_t id, uint32_t flags, uint8_t* d_out, uint64_t* base, uint64_t hash_max,
-                   hipStream_t stream)
+void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* jobs, size_t lo, size_t hi,
+                   uint64_t nb64, uint64_t slot_b, uint32_t id, uint32_t flags, const PassDict& dict, uint8_t* d_out,
+                   uint64_t* base, uint64_t hash_max, hipStream_t stream)
 {
 	const bool bck = (flags & LZ4ADA_COMP_BLOCK_CHECKSUM) != 0, cck = (flags & LZ4ADA_COMP_CONTENT_CHECKSUM) != 0;
 	const uint32_t nb = uint32_t(nb64), nj = uint32_t(hi - lo);
@@ -71,7 +78,7 @@ void compress_pass(const uint8_t* d_in, lz4ada_compress_job* jobs, size_t lo, si
 		const lz4ada_compress_job& j = jobs[k];
 		const uint32_t n = uint32_t(comp_nblocks(j.in_len, blen));
 		cj[k - lo] = CompJob{ uint64_t(j.in_off), uint64_t(j.in_len), fixed, b, n };
-		fixed += uint64_t(comp_header_len(flags) + comp_trailer_len(flags));
+		fixed += uint64_t(comp_header_len(flags, dict.dflags) + comp_trailer_len(flags));
 		for (uint32_t i = 0; i < n; ++i, ++b) {
 			const int64_t at = int64_t(i) * blen, len = std::min(blen, j.in_len - at);
 			blk[b] = CompBlock{ uint64_t(j.in_off + at), slot, uint32_t(len), uint32_t(k - lo) };
@@ -90,15 +97,20 @@ void compress_pass(const uint8_t* d_in, lz4ada_compress_job* jobs, size_t lo, si
 	HIP_OK(hipMemsetAsync(d_rec, 0, rec_b, stream));
 	if (cck)  // over the records where they lie; the longer ones are the host chain's
 		HIP_OK(launch_xxh32_spans(d_in, d_frec, nj, hash_max, stream));
-	HIP_OK(launch_compress_blocks(d_in, d_blk, nb, d_slots, d_csize, stream));
+	if (dict.dl)
+		HIP_OK(launch_compress_blocks_dict(d_in, d_blk, nb, dict.d_tail, dict.dl, dict.d_seed, d_slots, d_csize,
+		                                   stream));
+	else
+		HIP_OK(launch_compress_blocks(d_in, d_blk, nb, d_slots, d_csize, stream));
 	HIP_OK(launch_compress_scan(d_blk, d_csize, nb, flags, d_loc, d_part, stream));
-	HIP_OK(launch_compress_emit(d_in, d_slots, d_blk, d_csize, d_loc, d_part, d_jobs, nb, flags, *base, d_out, d_desc,
-	                            d_rec, stream));
+	HIP_OK(launch_compress_emit(d_in, d_slots, d_blk, d_csize, d_loc, d_part, d_jobs, nb, flags, dict.dflags, *base,
+	                            d_out, d_desc, d_rec, stream));
 	if (bck) {  // over the payloads as written
 		HIP_OK(launch_block_checksums(d_out, d_desc, nb, d_st, stream));
 		HIP_OK(launch_compress_block_cksums(d_desc, d_st, nb, d_out, stream));
 	}
-	HIP_OK(launch_compress_frames(d_jobs, nj, d_loc, d_part, nb, id, flags, *base, d_frec, d_out, d_rec, stream));
+	HIP_OK(launch_compress_frames(d_jobs, nj, d_loc, d_part, nb, id, flags, dict.dflags, dict.dict_id, *base, d_frec,
+	                              d_out, d_rec, stream));
 	// the pass's host synchronisation: places, lengths and counts, no payload byte
 	HIP_OK(hipMemcpyAsync(h.p + up_b, d_rec, rec_b, hipMemcpyDeviceToHost, stream));
 	HIP_OK(hipStreamSynchronize(stream));
@@ -127,28 +139,29 @@ void compress_pass(const uint8_t* d_in, lz4ada_compress_job* jobs, size_t lo, si
 		HIP_OK(hipStreamSynchronize(stream));
 }
 
-}  // namespace
-}  // namespace lz4ada
-
-extern "C" int lz4ada_compress_frames_device(const void* d_in, int64_t in_len, lz4ada_compress_job* jobs,
-                                             int64_t njobs, const lz4ada_compress_options* opt, void* d_out,
-                                             int64_t out_cap, int64_t* out_len, void* stream)
+// Both entries: cdict null is the plain call.
+int compress_frames(const char* ENTRY, const void* d_in, int64_t in_len, lz4ada_compress_job* jobs, int64_t njobs,
+                    const lz4ada_compress_options* opt, const lz4ada_compress_dict* cdict, void* d_out, int64_t out_cap,
+                    int64_t* out_len, void* stream)
 {
 	if (out_len)
 		*out_len = 0;
 	return guarded(nullptr, [&] {
-		auto misuse = [](const std::string& what) { raise(LZ4ADA_ASSERTION_ERROR, std::string(ENTRY) + ": " + what); };
+		auto misuse = [&](const std::string& what) { raise(LZ4ADA_ASSERTION_ERROR, std::string(ENTRY) + ": " + what); };
 		const uint32_t id = opt ? opt->block_id : 0, flags = opt ? opt->flags : 0;
 		if (!out_len || njobs < 0 || (njobs > 0 && !jobs) || in_len < 0 || (in_len > 0 && !d_in) || out_cap < 0 ||
 		    njobs >= (int64_t(1) << 31))
 			misuse("jobs, d_in or out_len is NULL, or a count is out of range");
 		if (!comp_options_ok(id, flags))
 			misuse("block_id is not 0 or 4..7, or unknown bits in flags");
+		if (cdict && (cdict->dict_len < 0 || (cdict->dict_len > 0 && !cdict->d_dict) ||
+		              (cdict->flags & ~COMP_DICT_FLAGS_ALL)))
+			misuse("dict_len is negative, d_dict is NULL, or unknown bits in dict->flags");
 		for (int64_t i = 0; i < njobs; ++i)
 			if (jobs[i].in_off < 0 || jobs[i].in_len < 0 || jobs[i].in_off > in_len ||
 			    jobs[i].in_len > in_len - jobs[i].in_off)
 				misuse("job" + img(i) + " lies outside the input");
-		const int64_t bound = lz4ada_compress_frames_bound(jobs, njobs, opt);
+		const int64_t bound = lz4ada_compress_frames_bound_dict(jobs, njobs, opt, cdict);
 		if (bound < 0)
 			misuse("the jobs' bound is out of range");
 		if (bound > 0 && !d_out && out_cap >= bound)
@@ -167,6 +180,21 @@ extern "C" int lz4ada_compress_frames_device(const void* d_in, int64_t in_len, l
 			return;
 		device_check_or_raise();
 		hipStream_t s = static_cast<hipStream_t>(stream);
+		PassDict dict;
+		if (cdict) {
+			dict.dflags = cdict->flags;
+			dict.dict_id = cdict->dict_id;
+			const int64_t dl = std::min(cdict->dict_len, COMP_DICT_MAX);
+			if (dl >= 4) {  // below 4 bytes nothing is seeded: the plain kernel's bytes
+				uint32_t* const d_seed = reinterpret_cast<uint32_t*>(scratch(SC_DICT, COMP_TABLE * sizeof(uint32_t)));
+				if (!d_seed)
+					raise(LZ4ADA_DEVICE_ERROR, std::string(ENTRY) + ": no device memory for the dictionary's table");
+				dict.d_tail = static_cast<const uint8_t*>(cdict->d_dict) + (cdict->dict_len - dl);
+				dict.dl = uint32_t(dl);
+				dict.d_seed = d_seed;
+				HIP_OK(launch_compress_dict_table(dict.d_tail, dict.dl, d_seed, s));  // once per call
+			}
+		}
 		const uint64_t budget = uint64_t(batch_budget()), hash_max = uint64_t(batch_hash_max());
 		const int64_t blen = comp_block_len(id);
 		uint64_t base = 0;
@@ -188,10 +216,30 @@ extern "C" int lz4ada_compress_frames_device(const void* d_in, int64_t in_len, l
 			}
 			if (nb >= (uint64_t(1) << 31))
 				raise(LZ4ADA_CONSTRAINT_ERROR, std::string(ENTRY) + ": a record holds more blocks than a pass takes");
-			compress_pass(static_cast<const uint8_t*>(d_in), jobs, lo, hi, nb, acc, id, flags,
+			compress_pass(ENTRY, static_cast<const uint8_t*>(d_in), jobs, lo, hi, nb, acc, id, flags, dict,
 			              static_cast<uint8_t*>(d_out), &base, hash_max, s);
 			lo = hi;
 		}
 		*out_len = int64_t(base);
 	});
+}
+
+}  // namespace
+}  // namespace lz4ada
+
+extern "C" int lz4ada_compress_frames_device(const void* d_in, int64_t in_len, lz4ada_compress_job* jobs,
+                                             int64_t njobs, const lz4ada_compress_options* opt, void* d_out,
+                                             int64_t out_cap, int64_t* out_len, void* stream)
+{
+	return compress_frames("lz4ada_compress_frames_device", d_in, in_len, jobs, njobs, opt, nullptr, d_out, out_cap,
+	                       out_len, stream);
+}
+
+extern "C" int lz4ada_compress_frames_device_dict(const void* d_in, int64_t in_len, lz4ada_compress_job* jobs,
+                                                  int64_t njobs, const lz4ada_compress_options* opt,
+                                                  const lz4ada_compress_dict* dict, void* d_out, int64_t out_cap,
+                                                  int64_t* out_len, void* stream)
+{
+	return compress_frames("lz4ada_compress_frames_device_dict", d_in, in_len, jobs, njobs, opt, dict, d_out, out_cap,
+	                       out_len, stream);
 }

@@ -28,6 +28,10 @@ constexpr int64_t COMP_MAX_OFF = 65535;
 // n - COMP_LAST_LITERALS.
 constexpr int64_t COMP_MIN_BLOCK = 13, COMP_MFLIMIT = 12, COMP_LAST_LITERALS = 5;
 constexpr int64_t COMP_MAX_INPUT = 0x7E000000;  // LZ4_MAX_INPUT_SIZE
+// With a dictionary positions are virtual: its last
+// min(dict_len, COMP_DICT_MAX) bytes D lie at [-dl, 0) in front of every block,
+// and the table holds virtual position + dl + 1.
+constexpr int64_t COMP_DICT_MAX = 65536;
 
 LZ4ADA_HD inline uint32_t comp_hash(uint32_t four_bytes)
 {
@@ -58,7 +62,12 @@ LZ4ADA_HD inline int64_t comp_block_len(uint32_t block_id)
 	return int64_t(65536) << (2 * (comp_block_id(block_id) - 4));
 }
 LZ4ADA_HD inline int64_t comp_nblocks(int64_t n, int64_t block_len) { return (n + block_len - 1) / block_len; }
-LZ4ADA_HD inline int64_t comp_header_len(uint32_t flags) { return 7 + ((flags & LZ4ADA_COMP_CONTENT_SIZE) ? 8 : 0); }
+// dflags: a dictionary call's LZ4ADA_COMP_DICT_* (DESIGN.md §18), 0 without one.
+constexpr uint32_t COMP_DICT_FLAGS_ALL = LZ4ADA_COMP_DICT_WRITE_ID;
+LZ4ADA_HD inline int64_t comp_header_len(uint32_t flags, uint32_t dflags = 0)
+{
+	return 7 + ((flags & LZ4ADA_COMP_CONTENT_SIZE) ? 8 : 0) + ((dflags & LZ4ADA_COMP_DICT_WRITE_ID) ? 4 : 0);
+}
 LZ4ADA_HD inline int64_t comp_trailer_len(uint32_t flags)
 {
 	return 4 + ((flags & LZ4ADA_COMP_CONTENT_CHECKSUM) ? 4 : 0);
@@ -66,22 +75,28 @@ LZ4ADA_HD inline int64_t comp_trailer_len(uint32_t flags)
 // A block's bytes besides its payload: the size word and the checksum.
 LZ4ADA_HD inline int64_t comp_block_extra(uint32_t flags) { return 4 + ((flags & LZ4ADA_COMP_BLOCK_CHECKSUM) ? 4 : 0); }
 // The bound of include/lz4ada_hip.h: every block stored.
-LZ4ADA_HD inline int64_t comp_frame_bound(int64_t n, uint32_t block_id, uint32_t flags)
+LZ4ADA_HD inline int64_t comp_frame_bound(int64_t n, uint32_t block_id, uint32_t flags, uint32_t dflags = 0)
 {
-	return comp_header_len(flags) + comp_nblocks(n, comp_block_len(block_id)) * comp_block_extra(flags) + n +
+	return comp_header_len(flags, dflags) + comp_nblocks(n, comp_block_len(block_id)) * comp_block_extra(flags) + n +
 	       comp_trailer_len(flags);
 }
-// Magic, FLG, BD, the content size when asked for, HC into h[0 .. 15) -> comp_header_len.
-LZ4ADA_HD inline int comp_header(uint8_t* h, uint32_t block_id, uint32_t flags, uint64_t content_size)
+// Magic, FLG, BD, the content size when asked for, the dictionary id under
+// LZ4ADA_COMP_DICT_WRITE_ID, HC (over all of them) into h[0 .. 19) -> comp_header_len.
+LZ4ADA_HD inline int comp_header(uint8_t* h, uint32_t block_id, uint32_t flags, uint64_t content_size,
+                                 uint32_t dflags = 0, uint32_t dict_id = 0)
 {
 	h[0] = 0x04, h[1] = 0x22, h[2] = 0x4d, h[3] = 0x18;
 	h[4] = uint8_t(0x40 | 0x20 | ((flags & LZ4ADA_COMP_BLOCK_CHECKSUM) ? 0x10 : 0) |
-	               ((flags & LZ4ADA_COMP_CONTENT_SIZE) ? 0x08 : 0) | ((flags & LZ4ADA_COMP_CONTENT_CHECKSUM) ? 0x04 : 0));
+	               ((flags & LZ4ADA_COMP_CONTENT_SIZE) ? 0x08 : 0) | ((flags & LZ4ADA_COMP_CONTENT_CHECKSUM) ? 0x04 : 0) |
+	               ((dflags & LZ4ADA_COMP_DICT_WRITE_ID) ? 0x01 : 0));
 	h[5] = uint8_t(comp_block_id(block_id) << 4);
 	int n = 6;
 	if (flags & LZ4ADA_COMP_CONTENT_SIZE)
 		for (int i = 0; i < 8; ++i)
 			h[n++] = uint8_t(content_size >> (8 * i));
+	if (dflags & LZ4ADA_COMP_DICT_WRITE_ID)
+		for (int i = 0; i < 4; ++i)
+			h[n++] = uint8_t(dict_id >> (8 * i));
 	h[n] = uint8_t(walk_descriptor_xxh32(h + 4, n - 4) >> 8);
 	return n + 1;
 }

@@ -16,6 +16,9 @@
 //  * k_compress_block_cksums -- the block checksums behind the payloads;
 //  * k_compress_frames -- a thread per job writes the header, the end mark and
 //    the content checksum k_xxh32_spans left, and the job's place and length.
+// A dictionary call compresses its blocks with
+// k_compress_blocks_dict (lz4ada_compress_dict.hip) and shares the rest; its
+// dflags / dict_id reach the emit and the header for the 4 bytes of the id.
 // No kernel waits for another workgroup; every loop is bounded by the block
 // length or the block count.
 #include <hip/hip_runtime.h>
@@ -224,7 +227,8 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_emit(const uint8_t* __rest
                                                            const uint64_t* __restrict__ loc,
                                                            const uint64_t* __restrict__ part,
                                                            const CompJob* __restrict__ jobs, uint32_t nblocks,
-                                                           uint32_t flags, uint64_t base, uint8_t* __restrict__ d_out,
+                                                           uint32_t flags, uint32_t dflags, uint64_t base,
+                                                           uint8_t* __restrict__ d_out,
                                                            lz4ada_block_desc* __restrict__ desc,
                                                            CompJobRec* __restrict__ rec)
 {
@@ -235,7 +239,7 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_emit(const uint8_t* __rest
 	const uint32_t c = csize[b];
 	const bool stored = c == 0;
 	const uint32_t n = stored ? B.len : c;
-	const uint64_t at = base + jobs[B.job].fixed_before + uint64_t(comp_header_len(flags)) +
+	const uint64_t at = base + jobs[B.job].fixed_before + uint64_t(comp_header_len(flags, dflags)) +
 	                    comp_off(loc, part, nblocks, b);
 	cg8* const s = stored ? gptr(d_in) + B.in_off : gptr(slots) + B.slot_off;
 	g8* const t = gptr(d_out) + at + 4;
@@ -283,7 +287,8 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_block_cksums(const lz4ada_
 __global__ __launch_bounds__(COMP_WG) void k_compress_frames(const CompJob* __restrict__ jobs, uint32_t njobs,
                                                              const uint64_t* __restrict__ loc,
                                                              const uint64_t* __restrict__ part, uint32_t nblocks,
-                                                             uint32_t block_id, uint32_t flags, uint64_t base,
+                                                             uint32_t block_id, uint32_t flags, uint32_t dflags,
+                                                             uint32_t dict_id, uint64_t base,
                                                              const FrameRec* __restrict__ frec,
                                                              uint8_t* __restrict__ d_out, CompJobRec* __restrict__ rec)
 {
@@ -294,8 +299,8 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_frames(const CompJob* __re
 	const uint64_t lo = comp_off(loc, part, nblocks, J.first);
 	const uint64_t body = comp_off(loc, part, nblocks, J.first + J.nblocks) - lo;
 	const uint64_t at = base + J.fixed_before + lo;
-	uint8_t hdr[15];
-	const int hn = comp_header(hdr, block_id, flags, J.in_len);
+	uint8_t hdr[19];
+	const int hn = comp_header(hdr, block_id, flags, J.in_len, dflags, dict_id);
 	g8* t = gptr(d_out) + at;
 	for (int i = 0; i < hn; ++i)
 		t[i] = hdr[i];
@@ -334,13 +339,13 @@ hipError_t launch_compress_scan(const CompBlock* d_blk, const uint32_t* d_csize,
 
 hipError_t launch_compress_emit(const uint8_t* d_in, const uint8_t* d_slots, const CompBlock* d_blk,
                                 const uint32_t* d_csize, const uint64_t* d_loc, const uint64_t* d_part,
-                                const CompJob* d_jobs, uint32_t nblocks, uint32_t flags, uint64_t base, uint8_t* d_out,
-                                lz4ada_block_desc* d_desc, CompJobRec* d_rec, hipStream_t stream)
+                                const CompJob* d_jobs, uint32_t nblocks, uint32_t flags, uint32_t dflags, uint64_t base,
+                                uint8_t* d_out, lz4ada_block_desc* d_desc, CompJobRec* d_rec, hipStream_t stream)
 {
 	if (nblocks == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_compress_emit, dim3(nblocks), dim3(COMP_WG), 0, stream, d_in, d_slots, d_blk, d_csize, d_loc,
-	                   d_part, d_jobs, nblocks, flags, base, d_out, d_desc, d_rec);
+	                   d_part, d_jobs, nblocks, flags, dflags, base, d_out, d_desc, d_rec);
 	return hipGetLastError();
 }
 
@@ -355,13 +360,14 @@ hipError_t launch_compress_block_cksums(const lz4ada_block_desc* d_desc, const l
 }
 
 hipError_t launch_compress_frames(const CompJob* d_jobs, uint32_t njobs, const uint64_t* d_loc, const uint64_t* d_part,
-                                  uint32_t nblocks, uint32_t block_id, uint32_t flags, uint64_t base,
-                                  const FrameRec* d_frec, uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream)
+                                  uint32_t nblocks, uint32_t block_id, uint32_t flags, uint32_t dflags,
+                                  uint32_t dict_id, uint64_t base, const FrameRec* d_frec, uint8_t* d_out,
+                                  CompJobRec* d_rec, hipStream_t stream)
 {
 	if (njobs == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_compress_frames, dim3((njobs + COMP_WG - 1) / COMP_WG), dim3(COMP_WG), 0, stream, d_jobs,
-	                   njobs, d_loc, d_part, nblocks, block_id, flags, base, d_frec, d_out, d_rec);
+	                   njobs, d_loc, d_part, nblocks, block_id, flags, dflags, dict_id, base, d_frec, d_out, d_rec);
 	return hipGetLastError();
 }
 

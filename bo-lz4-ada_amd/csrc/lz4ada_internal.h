@@ -617,22 +617,33 @@ hipError_t launch_compress_blocks(const uint8_t* d_in, const CompBlock* d_blk, u
 // The exclusive prefix sum of the blocks' bytes in the output (size word,
 // payload, checksum under `flags`): block b's is d_part[b / PLAN_TILE] +
 // d_loc[b], the total d_part[plan_tiles(nblocks)].  nblocks may be 0.
+// The same against a dictionary (lz4ada_compress_dict.hip): dl
+// bytes (4 .. 65,536) at d_tail lie in front of every block, d_seed is their
+// table as launch_compress_dict_table left it.  Reads d_tail inside [0, dl).
+hipError_t launch_compress_blocks_dict(const uint8_t* d_in, const CompBlock* d_blk, uint32_t nblocks,
+                                       const uint8_t* d_tail, uint32_t dl, const uint32_t* d_seed, uint8_t* d_slots,
+                                       uint32_t* d_csize, hipStream_t stream);
+// d_seed[0 .. COMP_TABLE): for every hash the last position + 1 of d_tail[0 .. dl)
+// whose four bytes lie inside it, 0 for none (dl < 4: all 0).
+hipError_t launch_compress_dict_table(const uint8_t* d_tail, uint32_t dl, uint32_t* d_seed, hipStream_t stream);
 hipError_t launch_compress_scan(const CompBlock* d_blk, const uint32_t* d_csize, uint32_t nblocks, uint32_t flags,
                                 uint64_t* d_loc, uint64_t* d_part, hipStream_t stream);
 // One workgroup per block: size word and payload into d_out (the pass begins
 // at d_out + base), d_desc[b] the payload inside d_out, d_rec[job].stored.
+// dflags: a dictionary call's LZ4ADA_COMP_DICT_* (the header's length), else 0.
 hipError_t launch_compress_emit(const uint8_t* d_in, const uint8_t* d_slots, const CompBlock* d_blk,
                                 const uint32_t* d_csize, const uint64_t* d_loc, const uint64_t* d_part,
-                                const CompJob* d_jobs, uint32_t nblocks, uint32_t flags, uint64_t base, uint8_t* d_out,
-                                lz4ada_block_desc* d_desc, CompJobRec* d_rec, hipStream_t stream);
+                                const CompJob* d_jobs, uint32_t nblocks, uint32_t flags, uint32_t dflags, uint64_t base,
+                                uint8_t* d_out, lz4ada_block_desc* d_desc, CompJobRec* d_rec, hipStream_t stream);
 // d_st[b].cksum (launch_block_checksums over d_out and d_desc) behind every payload.
 hipError_t launch_compress_block_cksums(const lz4ada_block_desc* d_desc, const lz4ada_block_status* d_st,
                                         uint32_t nblocks, uint8_t* d_out, hipStream_t stream);
 // One thread per job: header, end mark, the content checksum when d_frec[j]
 // carries one (launch_xxh32_spans over d_in; d_frec may be null without
-// LZ4ADA_COMP_CONTENT_CHECKSUM), and d_rec[j].out_off / out_len.
+// LZ4ADA_COMP_CONTENT_CHECKSUM), and d_rec[j].out_off / out_len.  dflags and
+// dict_id: a dictionary call's, for the header; else 0.
 hipError_t launch_compress_frames(const CompJob* d_jobs, uint32_t njobs, const uint64_t* d_loc, const uint64_t* d_part,
-                                  uint32_t nblocks, uint32_t block_id, uint32_t flags, uint64_t base,
-                                  const FrameRec* d_frec, uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream);
+                                  uint32_t nblocks, uint32_t block_id, uint32_t flags, uint32_t dflags,
+                                  uint32_t dict_id, uint64_t base, const FrameRec* d_frec, uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream);
 
 }  // namespace lz4ada

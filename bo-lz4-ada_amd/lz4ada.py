@@ -228,7 +228,16 @@ class CompressJob(ctypes.Structure):
                 ("out_len", ctypes.c_int64), ("status", ctypes.c_int32), ("stored_blocks", ctypes.c_int32)]
 
 
+class CompressDict(ctypes.Structure):
+    """lz4ada_compress_dict, the dictionary of the compress calls: the last
+    65,536 bytes of dict_len bytes of device memory at d_dict; dict_id goes
+    into every header under COMP_DICT_WRITE_ID in flags."""
+    _fields_ = [("d_dict", ctypes.c_void_p), ("dict_len", ctypes.c_int64), ("dict_id", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
 COMP_BLOCK_CHECKSUM, COMP_CONTENT_CHECKSUM, COMP_CONTENT_SIZE = 1, 2, 4
+COMP_DICT_WRITE_ID = 1
 _COMP_BLOCK_ID = {65536: 4, 262144: 5, 1 << 20: 6, 4 << 20: 7}
 
 # DeviceFrameJob.reason: 1..4 are the BATCH_* reasons
@@ -250,6 +259,7 @@ FRAMES_EXACT = 2
 
 _P = ctypes.POINTER
 _len = len  # range_blocks_host has a parameter named len, as the C-ABI has
+_dict = dict  # the compress and decode calls have a keyword named dict
 _sig = {
     "lz4ada_stream_index": ([ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                              ctypes.POINTER(ctypes.c_int64)], ctypes.c_int),
@@ -297,6 +307,11 @@ _sig = {
     "lz4ada_compress_frames_device": ([_vp, _i64, _vp, _i64, _vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
     "lz4ada_compress_block_host": ([_vp, _i64, _vp, _i64], _i64),
     "lz4ada_compress_frame_host": ([_vp, _i64, _vp, _vp, _i64], _i64),
+    "lz4ada_compress_frames_bound_dict": ([_vp, _i64, _vp, _vp], _i64),
+    "lz4ada_compress_frames_device_dict": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_compress_block_dict_host": ([_vp, _i64, _vp, _i64, _vp, _i64], _i64),
+    "lz4ada_compress_frame_dict_host": ([_vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _i64],
+                                        _i64),
     "lz4ada_abi_version": ([], ctypes.c_int),
     "lz4ada_device_check": ([], ctypes.c_int),
     "lz4ada_error_name": ([ctypes.c_int], ctypes.c_char_p),
@@ -841,30 +856,59 @@ def _compress_jobs(spans):
     return jobs
 
 
-def compress_frames_bound(lens, block=65536, block_checksum=False, content_checksum=False, content_size=False):
+def _compress_dict(dict, dict_id):
+    """The `dict` / `dict_id` keywords of the compress calls -> a CompressDict
+    or None.  dict: a CompressDict as it is, or (d_dict, dict_len) of device
+    memory; dict_id: when given, written into every header."""
+    if isinstance(dict, CompressDict):
+        return dict
+    if dict is None and dict_id is None:
+        return None
+    d_dict, dict_len = dict if dict is not None else (None, 0)
+    return CompressDict(d_dict, dict_len, 0 if dict_id is None else dict_id,
+                        0 if dict_id is None else COMP_DICT_WRITE_ID)
+
+
+def compress_frames_bound(lens, block=65536, block_checksum=False, content_checksum=False, content_size=False,
+                          dict=None, dict_id=None):
     """An out_cap that always suffices for records of these lengths, one frame
     each: the header's exact worst-case arithmetic (every block stored).  No
-    GPU involved."""
+    GPU involved.  dict, dict_id: as compress_frames_device takes them; only
+    whether an id is written enters the bound (4 bytes per frame)."""
     opt = _compress_options(block, block_checksum, content_checksum, content_size)
     jobs = _compress_jobs([(0, n) for n in lens])
-    bound = int(_lib.lz4ada_compress_frames_bound(jobs, len(lens), ctypes.byref(opt)))
+    cd = _compress_dict(dict, dict_id)
+    if cd is None:
+        bound = int(_lib.lz4ada_compress_frames_bound(jobs, len(lens), ctypes.byref(opt)))
+    else:
+        bound = int(_lib.lz4ada_compress_frames_bound_dict(jobs, len(lens), ctypes.byref(opt), ctypes.byref(cd)))
     if bound < 0:
         raise AssertionFailure("lz4ada_compress_frames_bound: a negative length, or options out of range")
     return bound
 
 
 def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0, block=65536,
-                           block_checksum=False, content_checksum=False, content_size=False):
+                           block_checksum=False, content_checksum=False, content_size=False, dict=None,
+                           dict_id=None):
     """Compress the records at spans [(in_off, in_len)] of the device buffer
     d_in into LZ4 frames laid back to back into the device buffer d_out (raw
     pointers) -> (bytes written, the CompressJob array: out_off, out_len,
     status, stored_blocks).  TooLittleMemory carries the needed size as .bound
-    and leaves d_out untouched."""
+    and leaves d_out untouched.  dict: a CompressDict, or (d_dict, dict_len)
+    of device memory, the dictionary every frame shares
+    (lz4ada_compress_frames_device_dict; decode_frames_device with the same
+    dictionary reads the frames); dict_id: when given, every header carries
+    it, None writes none."""
     opt = _compress_options(block, block_checksum, content_checksum, content_size)
     jobs = _compress_jobs(spans)
     n = _i64()
-    st = _lib.lz4ada_compress_frames_device(d_in, in_len, jobs, len(spans), ctypes.byref(opt), d_out, out_cap,
-                                            ctypes.byref(n), stream)
+    cd = _compress_dict(dict, dict_id)
+    if cd is None:
+        st = _lib.lz4ada_compress_frames_device(d_in, in_len, jobs, len(spans), ctypes.byref(opt), d_out, out_cap,
+                                                ctypes.byref(n), stream)
+    else:
+        st = _lib.lz4ada_compress_frames_device_dict(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
+                                                     ctypes.byref(cd), d_out, out_cap, ctypes.byref(n), stream)
     if st:
         exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
         exc.bound = n.value
@@ -873,18 +917,24 @@ def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: i
 
 
 def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False, content_checksum=False,
-                           content_size=False):
+                           content_size=False, dict=None, dict_id=None):
     """compress_frames_device for a CUDA torch.uint8 tensor holding the
     records, on torch's current stream -> (the frames as a uint8 tensor on the
     same device, [(off, len)] of every record's frame inside it).  out: a uint8
     tensor there to write into; by default one of compress_frames_bound bytes
-    is allocated."""
+    is allocated.  dict: a CUDA uint8 tensor on the same device holding the
+    dictionary every frame shares; dict_id: when given, written into every
+    header."""
     if torch is None:
         raise RuntimeError("compress_frames_tensor needs torch")
     if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
         raise ValueError("the records must be a contiguous CUDA uint8 tensor")
-    kw = dict(block=block, block_checksum=block_checksum, content_checksum=content_checksum,
-              content_size=content_size)
+    if dict is not None:
+        if not (dict.is_cuda and dict.device == t.device and dict.dtype == torch.uint8 and dict.is_contiguous()):
+            raise ValueError("the dictionary must be a contiguous CUDA uint8 tensor on the records' device")
+        dict = (dict.data_ptr() if dict.numel() else None, dict.numel())
+    kw = _dict(block=block, block_checksum=block_checksum, content_checksum=content_checksum,
+               content_size=content_size, dict=_compress_dict(dict, dict_id))
     with torch.cuda.device(t.device):
         if out is None:
             out = torch.empty(max(compress_frames_bound([n for _, n in spans], **kw), 1), dtype=torch.uint8,
@@ -896,31 +946,46 @@ def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False
     return out[:n], [(jobs[i].out_off, jobs[i].out_len) for i in range(len(spans))]
 
 
-def compress_block_host(data, cap=None) -> bytes:
+def compress_block_host(data, cap=None, dict=b"") -> bytes:
     """The serial statement of the block compressor (no GPU involved): data as
     one LZ4 block of at most cap bytes (default: whatever it takes) -> the
-    block, or b"" when it does not fit into cap bytes."""
-    data = bytes(data)
+    block, or b"" when it does not fit into cap bytes.  dict (bytes): the
+    dictionary in front of the block (lz4ada_compress_block_dict_host)."""
+    data, dict = bytes(data), bytes(dict)
     if cap is None:
         cap = len(data) + len(data) // 255 + 16
     buf = ctypes.create_string_buffer(max(cap, 1))
-    n = int(_lib.lz4ada_compress_block_host(_addr(data) if data else None, len(data), buf, cap))
+    if dict:
+        n = int(_lib.lz4ada_compress_block_dict_host(_addr(data) if data else None, len(data), _addr(dict),
+                                                     len(dict), buf, cap))
+    else:
+        n = int(_lib.lz4ada_compress_block_host(_addr(data) if data else None, len(data), buf, cap))
     if n < 0:
         raise AssertionFailure("lz4ada_compress_block_host: a NULL pointer or a length out of range")
     return buf.raw[:n]
 
 
 def compress_frame_host(data, block=65536, block_checksum=False, content_checksum=False, content_size=False,
-                        cap=None) -> bytes:
+                        cap=None, dict=b"", dict_id=None) -> bytes:
     """The serial statement of one frame (no GPU involved): the bytes
     compress_frames_device writes for this record.  cap: the destination's
-    size (default: the bound); below the bound: TooLittleMemory."""
-    data = bytes(data)
+    size (default: the bound); below the bound: TooLittleMemory.  dict
+    (bytes), dict_id: the dictionary and the id of that call
+    (lz4ada_compress_frame_dict_host)."""
+    data, dict = bytes(data), bytes(dict)
     opt = _compress_options(block, block_checksum, content_checksum, content_size)
     if cap is None:
-        cap = compress_frames_bound([len(data)], block, block_checksum, content_checksum, content_size)
+        cap = compress_frames_bound([len(data)], block, block_checksum, content_checksum, content_size,
+                                    dict_id=dict_id)
     buf = ctypes.create_string_buffer(max(cap, 1))
-    n = int(_lib.lz4ada_compress_frame_host(_addr(data) if data else None, len(data), ctypes.byref(opt), buf, cap))
+    if dict or dict_id is not None:
+        n = int(_lib.lz4ada_compress_frame_dict_host(_addr(data) if data else None, len(data), ctypes.byref(opt),
+                                                     _addr(dict) if dict else None, len(dict),
+                                                     0 if dict_id is None else dict_id,
+                                                     0 if dict_id is None else COMP_DICT_WRITE_ID, buf, cap))
+    else:
+        n = int(_lib.lz4ada_compress_frame_host(_addr(data) if data else None, len(data), ctypes.byref(opt), buf,
+                                                cap))
     if n < 0:
         raise _ERRORS.get(-n, LZ4AdaError)(f"lz4ada_compress_frame_host: {error_name(-n)}")
     return buf.raw[:n]

@@ -949,6 +949,61 @@ int64_t lz4ada_compress_block_host(const uint8_t *src, int64_t n, uint8_t *dst, 
 int64_t lz4ada_compress_frame_host(const uint8_t *src, int64_t n, const lz4ada_compress_options *opt,
                                    uint8_t *dst, int64_t cap);
 
+/* -------------- records compressed against a shared dictionary, on the device */
+/*
+ * The write side of lz4ada_decode_frames_device_dict:
+ * lz4ada_compress_frames_device with one dictionary, in device memory, shared
+ * by every frame of the call, as LZ4F_compressFrame_usingCDict shares one.
+ * The last min(dict_len, 65536) bytes of the dictionary lie in front of every
+ * block of every record (the blocks are independent, so each starts from the
+ * dictionary afresh), and a block's matches may begin there.  The frames
+ * decode through lz4ada_decode_frames_device_dict,
+ * lz4ada_decode_frame_dict_host and liblz4's LZ4F_decompress_usingDict with
+ * the same dictionary; a decoder without it rejects or garbles them.
+ *
+ * dict->flags: with LZ4ADA_COMP_DICT_WRITE_ID every header carries FLG bit 0
+ * and dict_id, 4 bytes after the content size and before HC (which covers
+ * them), and the bound grows by 4 per frame; without it dict_id is ignored and
+ * the header is the plain call's.  lz4ada_compress_frames_bound_dict reads
+ * dict->flags alone (host only, no HIP call; d_dict is not dereferenced; -1 on
+ * misuse).  opt is the plain call's and rejects what it rejects there.
+ * dict == NULL, or dict_len == 0 without LZ4ADA_COMP_DICT_WRITE_ID, is
+ * lz4ada_compress_frames_device itself, launch by launch.  API misuse,
+ * LZ4ADA_ASSERTION_ERROR before any launch: the plain call's, dict_len < 0,
+ * d_dict == NULL with dict_len > 0, unknown bits in dict->flags.  The rest of
+ * the contract is the plain call's: LZ4ADA_TOO_LITTLE_MEMORY below the bound
+ * with *out_len set to it and d_out untouched, dense frames in job order,
+ * nothing written at or beyond d_out + *out_len, one host synchronisation per
+ * pass.  The dictionary's hash table (16 KiB, built once per call) lies in the
+ * library's scratch.
+ *
+ * lz4ada_compress_block_dict_host and lz4ada_compress_frame_dict_host state
+ * the rule serially, as their plain twins do: the device call's bytes for a
+ * job are lz4ada_compress_frame_dict_host's for its record.  dict may be NULL
+ * with dict_len 0, which gives the plain twins' bytes; dict_flags and dict_id
+ * are dict->flags and dict->dict_id.  Host only, no HIP call.
+ */
+#define LZ4ADA_COMP_DICT_WRITE_ID 1u
+typedef struct {
+	const void *d_dict; /* device memory */
+	int64_t dict_len;   /* any length >= 0; the last 65,536 bytes are used */
+	uint32_t dict_id;   /* written into the header with LZ4ADA_COMP_DICT_WRITE_ID */
+	uint32_t flags;     /* LZ4ADA_COMP_DICT_* */
+} lz4ada_compress_dict;
+int64_t lz4ada_compress_frames_bound_dict(const lz4ada_compress_job *jobs, int64_t njobs,
+                                          const lz4ada_compress_options *opt,
+                                          const lz4ada_compress_dict *dict);
+int lz4ada_compress_frames_device_dict(const void *d_in, int64_t in_len, lz4ada_compress_job *jobs,
+                                       int64_t njobs, const lz4ada_compress_options *opt,
+                                       const lz4ada_compress_dict *dict, void *d_out,
+                                       int64_t out_cap, int64_t *out_len, void *stream);
+int64_t lz4ada_compress_block_dict_host(const uint8_t *src, int64_t n, const uint8_t *dict,
+                                        int64_t dict_len, uint8_t *dst, int64_t cap);
+int64_t lz4ada_compress_frame_dict_host(const uint8_t *src, int64_t n,
+                                        const lz4ada_compress_options *opt, const uint8_t *dict,
+                                        int64_t dict_len, uint32_t dict_id, uint32_t dict_flags,
+                                        uint8_t *dst, int64_t cap);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
