@@ -233,6 +233,8 @@ uint64_t gapped_blocks(const FramesIndex& ix, size_t k)
 	return ix.linked(k) ? 1 : ix.walk[k].nblocks;
 }
 
+}  // namespace
+
 // LZ4ADA_DICT_CHECK_ID: a taken modern frame that names another dictionary id
 // is no longer taken(), with LZ4ADA_DEVFRAME_DICT as its verdict, on the host
 // and on the device.  One host synchronisation: a word per frame.
@@ -254,6 +256,8 @@ void check_dict_ids(FramesIndex& ix, const uint8_t* d_in, uint32_t dict_id, hipS
 		if (bad[k] && ix.taken(k))
 			ix.walk[k].verdict = LZ4ADA_DEVFRAME_DICT;
 }
+
+namespace {
 
 // A dictionary pass over the sorted jobs [lo, hi), once its descriptors are
 // filled: the gaps (k_frames_dictgap from a word per frame), their bytes
@@ -405,6 +409,8 @@ void run_device_pass(const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots
 	*base += rec[m.nf - 1].out_off + rec[m.nf - 1].out_len;
 }
 
+}  // namespace
+
 // API misuse of a _dict call's dictionary, before any launch.
 void check_dict(const char* entry, const lz4ada_device_dict* dict)
 {
@@ -415,6 +421,8 @@ void check_dict(const char* entry, const lz4ada_device_dict* dict)
 	if (dict->flags & ~LZ4ADA_DICT_CHECK_ID)
 		misuse(entry, "unknown bits in dict->flags");
 }
+
+namespace {
 
 // lz4ada_decode_frames_device_opt, and with a dictionary of dict_len > 0 the
 // _dict call: the same index, sizes and passes, the gaps charged against the

@@ -23,6 +23,15 @@
 // head, fills it with the head's checkpoint (k_ckpt_fill) and decodes the
 // chains with the dictionary decoder of §15, one wave per chain, beside the
 // independent frames' launch_decode_checked; SC_TAB holds the sequence index.
+//
+// With a dictionary (lz4ada_seek_index_build_dict) the index
+// keeps its own copy of the dictionary's used bytes as a gap image, and a word
+// per frame that says which of its blocks read it.  A pass lays a second kind
+// of gap, the dictionary's, in front of every such marked block
+// (k_dictimg_fill), makes each the start of a chain, and decodes the chains of
+// all kinds -- from a checkpoint, from the dictionary -- in one launch that
+// takes the history length per chain (k_decode_idx_chains).  Legacy frames keep
+// launch_decode_checked.
 #include <climits>
 
 #include "lz4ada_host_common.h"
@@ -41,6 +50,14 @@ struct lz4ada_seek_index {
 	size_t ck_bytes = 0;
 	std::vector<uint64_t> kgrp, ckfirst;
 	bool linked = false;  // it holds a linked frame
+	// a dictionary index: the gap image (dict_gap bytes: zeros, then the last
+	// dict_used bytes of the dictionary), and by sorted position the frame's
+	// CHAIN_KIND_* (empty without a dictionary: every frame CHAIN_KIND_NONE)
+	void* d_dict = nullptr;
+	size_t dict_bytes = 0;
+	uint32_t dict_used = 0;
+	uint64_t dict_gap = 0;
+	std::vector<uint8_t> kind;
 	SeekView view{};
 	uint64_t* d_start = nullptr;
 	// by job
@@ -163,16 +180,22 @@ void select_ranges(const lz4ada_seek_index& x, Selection& s, hipStream_t stream)
 struct PassPlan {
 	uint32_t nsel = 0, span_n = 0;
 	uint64_t slots = 0, span_lo = 0;
-	bool linked = false;                            // a run is
-	std::vector<std::pair<bool, uint32_t>> runs;  // (linked, compacted blocks), in order
+	bool chains = false;                          // a run is
+	std::vector<std::pair<bool, uint32_t>> runs;  // (of chains, compacted blocks), in order
 };
 uint64_t frame_k(const lz4ada_seek_index& x, uint32_t f) { return x.kgrp.empty() ? 0 : x.kgrp[f]; }
-// what a range's own chain takes of the budget: its blocks' slots and its heads' gaps
+uint32_t frame_kind(const lz4ada_seek_index& x, uint32_t f) { return x.kind.empty() ? CHAIN_KIND_NONE : x.kind[f]; }
+// the gaps in front of the blocks [lo, hi) of frame f: its heads' and the dictionary's
+uint64_t gap_bytes(const lz4ada_seek_index& x, uint32_t f, uint64_t lo, uint64_t hi)
+{
+	return CKPT_GAP * chain_heads(frame_k(x, f), lo, hi) + x.dict_gap * chain_dict_gaps(frame_kind(x, f), lo, hi);
+}
+// what a range's own chain takes of the budget: its blocks' slots and their gaps
 uint64_t range_need(const lz4ada_seek_index& x, const Selection& s, size_t k)
 {
 	const RangeSel& r = s.sel[k];
-	const uint64_t K = frame_k(x, s.rec[k].frame);
-	return r.slot_hi - r.slot_lo + CKPT_GAP * chain_heads(K, chain_start(K, r.first), uint64_t(r.first) + r.count);
+	const uint32_t f = s.rec[k].frame;
+	return r.slot_hi - r.slot_lo + gap_bytes(x, f, chain_start(frame_k(x, f), r.first), uint64_t(r.first) + r.count);
 }
 PassPlan plan_pass(const lz4ada_seek_index& x, const Selection& s, size_t lo, size_t hi)
 {
@@ -197,14 +220,16 @@ PassPlan plan_pass(const lz4ada_seek_index& x, const Selection& s, size_t lo, si
 		// a new run of blocks takes its own slots, one that continues the open run
 		// what lies past that (slot_lo is slotp at c0, slot_hi past the last block)
 		p.slots += a.lo == c0 ? r.slot_hi - r.slot_lo : r.slot_hi - run_slot;
-		p.slots += CKPT_GAP * chain_heads(K, a.lo, a.hi);
+		p.slots += gap_bytes(x, f, a.lo, a.hi);
 		run_slot = r.slot_hi;
 		nsel += a.hi - a.lo;
-		if (!p.runs.empty() && p.runs.back().first == (K != 0))
+		// chains: a linked frame's blocks, and in a dictionary index every modern one's
+		const bool chains = K != 0 || frame_kind(x, f) != CHAIN_KIND_NONE;
+		if (!p.runs.empty() && p.runs.back().first == chains)
 			p.runs.back().second += uint32_t(a.hi - a.lo);
 		else
-			p.runs.emplace_back(K != 0, uint32_t(a.hi - a.lo));
-		p.linked |= K != 0;
+			p.runs.emplace_back(chains, uint32_t(a.hi - a.lo));
+		p.chains |= chains;
 	}
 	// the index holds fewer than 2^31 blocks
 	p.nsel = uint32_t(nsel);
@@ -215,7 +240,7 @@ PassPlan plan_pass(const lz4ada_seek_index& x, const Selection& s, size_t lo, si
 // A pass's device arrays in this thread's scratch.  SC_BATCH_META: descriptors
 // | statuses | chain records | slot | mark | cnt.  SC_OUT: the slots.  SC_TAB:
 // the sequence index.  The chain records and the sequence index only when the
-// pass decodes linked frames (in_len > 0 says so to reserve()).
+// pass decodes chains (in_len > 0 says so to reserve()).
 struct RangePass {
 	lz4ada_block_desc* d_desc = nullptr;
 	lz4ada_block_status* d_st = nullptr;
@@ -249,7 +274,7 @@ struct RangePass {
 		HIP_OK(hipMemsetAsync(d_mark, 0, std::max<size_t>(mark_b, 4), stream));
 		HIP_OK(launch_ranges_select(x.view, s.d_rec + lo, uint32_t(hi - lo), nullptr, d_mark, p.span_lo, p.span_n,
 		                            stream));
-		HIP_OK(launch_ranges_scan(d_mark, p.span_n, x.linked ? CKPT_GAP : 0, d_cnt, d_slot, stream));
+		HIP_OK(launch_ranges_scan(d_mark, p.span_n, x.linked ? CKPT_GAP : 0, x.dict_gap, d_cnt, d_slot, stream));
 	}
 };
 
@@ -268,20 +293,24 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 	const PassPlan p = plan_pass(x, s, lo, hi);
 	RangePass m;
 	const uint64_t in_len = uint64_t(x.in_len);
-	m.reserve(p, p.linked, in_len);
+	m.reserve(p, p.chains, in_len);
 	const uint32_t nr = uint32_t(hi - lo);
 	m.mark(x, s, lo, hi, p, stream);
-	if (p.linked)  // a record no block fills has flags 0: its workgroup returns at once
+	if (p.chains)  // a record no block fills has flags 0: its workgroup returns at once
 		HIP_OK(hipMemsetAsync(m.d_chain, 0, m.chain_b, stream));
 	HIP_OK(launch_ranges_fill(x.view, m.d_mark, m.d_cnt, m.d_slot, p.span_lo, p.span_n, p.nsel, p.slots, m.d_desc,
 	                          m.d_chain, stream));
 	HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
-	if (p.linked)
+	if (p.chains) {
 		HIP_OK(launch_ckpt_fill(x.view, m.d_desc, m.d_chain, p.nsel, m.d_slots, p.slots, stream));
+		HIP_OK(launch_dictimg_fill(x.view, m.d_desc, m.d_chain, p.nsel, m.d_slots, p.slots, stream));
+	}
 	// the compacted blocks run by run, as the host's sweep cut them: independent
-	// frames' with the passes' decoders, linked frames' with pass 1 and the block
-	// checksums as a linked run of a many-frame pass has them; then every chain
-	// of the pass in one launch, one wave each, its checkpoint as its dictionary
+	// frames' with the passes' decoders (in a dictionary index: legacy frames'),
+	// chains' with pass 1 and the block checksums as a linked run of a many-frame
+	// pass has them; then every chain of the pass in one launch, one wave each,
+	// its checkpoint as its dictionary -- or, in a dictionary index, whichever of
+	// the two its record names, by the record's own history length
 	uint32_t b0 = 0;
 	for (const auto& run : p.runs) {
 		const uint32_t n = run.second;
@@ -293,9 +322,14 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 		}
 		b0 += n;
 	}
-	if (p.linked) {
-		HIP_OK(launch_decode_idx_frames_dict(d_in, in_len, m.d_desc, p.nsel, m.d_tab, m.d_slots, m.d_st, m.d_chain,
-		                                     uint32_t(chain_slots(p.nsel)), uint32_t(CKPT_BYTES), stream));
+	if (p.chains) {
+		if (x.dict_used)
+			HIP_OK(launch_decode_idx_chains(d_in, in_len, m.d_desc, p.nsel, m.d_tab, m.d_slots, m.d_st, m.d_chain,
+			                                uint32_t(chain_slots(p.nsel)), stream));
+		else
+			HIP_OK(launch_decode_idx_frames_dict(d_in, in_len, m.d_desc, p.nsel, m.d_tab, m.d_slots, m.d_st,
+			                                     m.d_chain, uint32_t(chain_slots(p.nsel)), uint32_t(CKPT_BYTES),
+			                                     stream));
 		HIP_OK(join_block_checksums(stream));
 	}
 	HIP_OK(launch_ranges_verdict(x.view, s.d_rec + lo, nr, s.d_sel + lo, m.d_cnt, p.span_lo, p.span_n, m.d_desc,
@@ -330,27 +364,35 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 // (SC_DICT: nominal | tight), so an independent frame takes no block and no
 // slot.  A frame whose chain fails is no longer taken(), on the host and on the
 // device, with LZ4ADA_DEVFRAME_BLOCK (_SIZE) as its verdict.  One host
-// synchronisation per pass: the frame records.
+// synchronisation per pass: the frame records.  In a dictionary index every
+// frame's first block gets the dictionary's gap (k_frames_dictgap with
+// DICT_KIND_LINKED, k_dict_fill from the index's image), charged to the pass,
+// and the frames decode against it with the LZ4 specification's semantics
+// (launch_decode_idx_frames_dict: no quirk-D1 round state).
 void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* d_store, uint64_t* d_ckfirst,
                           uint64_t* d_kgrp, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
 {
 	const size_t n = ix.order.size(), walk_b = n * sizeof(FrameWalkRec);
 	const size_t ckf_b = (n + 1) * 8, kg_b = n * 8;
 	auto mine = [&](size_t k) { return ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0; };
-	FrameWalkRec* const d_nom = reinterpret_cast<FrameWalkRec*>(scratch(SC_DICT, 2 * walk_b));
+	const bool dict = x.dict_used != 0;
+	const size_t kind_b = dict ? n * 8 : 0;  // SC_DICT: nominal | tight | a dictionary pass's kind words
+	FrameWalkRec* const d_nom = reinterpret_cast<FrameWalkRec*>(scratch(SC_DICT, 2 * walk_b + kind_b));
 	if (!d_nom)
 		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the linked frames' records");
 	FrameWalkRec* const d_tight = d_nom + n;
+	uint64_t* const d_kind = reinterpret_cast<uint64_t*>(d_tight + n);
 	// pinned: the index's per-frame words and the records going up, and behind
 	// them room for a pass's frame records coming down, so that nothing is
 	// written while a copy may read it
 	PinBuf& h = scratch_cache().pin;
-	h.reserve(ckf_b + kg_b + 2 * walk_b + n * sizeof(FrameRec));
+	h.reserve(ckf_b + kg_b + 2 * walk_b + n * sizeof(FrameRec) + kind_b);
 	memcpy(h.p, x.ckfirst.data(), ckf_b);
 	memcpy(h.p + ckf_b, x.kgrp.data(), kg_b);
 	HIP_OK(hipMemcpyAsync(d_ckfirst, h.p, ckf_b + kg_b, hipMemcpyHostToDevice, stream));  // (kgrp follows ckfirst)
 	FrameWalkRec* const w = reinterpret_cast<FrameWalkRec*>(h.p + ckf_b + kg_b);
 	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p + ckf_b + kg_b + 2 * walk_b);
+	uint64_t* const kind = reinterpret_cast<uint64_t*>(rec + n);  // (a frame's word is written in its one pass)
 	bool any = false;
 	for (size_t k = 0; k < n; ++k) {
 		w[k] = ix.walk[k];
@@ -371,7 +413,7 @@ void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* 
 		for (; hi < n; ++hi) {
 			if (!mine(hi))
 				continue;
-			const uint64_t cost = ix.size[hi].tight;
+			const uint64_t cost = ix.size[hi].tight + x.dict_gap;  // (the gap is scratch like its slots)
 			if ((acc && acc + cost > budget) || nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
 				break;
 			acc += cost;
@@ -393,10 +435,26 @@ void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* 
 		                          true, ix.linked_max, m.d_desc, m.d_rec, stream));
 		HIP_OK(launch_frames_refit(d_tight + lo, ix.d_first, ix.d_slot, ix.d_size_first + lo, ix.d_size, nf, m.d_desc,
 		                           stream));
+		if (dict) {
+			uint64_t before = 0;
+			for (size_t k = lo; k < hi; ++k) {
+				kind[k] = (before << 2) | (mine(k) ? DICT_KIND_LINKED : DICT_KIND_NONE);
+				before += mine(k) ? 1 : 0;
+			}
+			HIP_OK(hipMemcpyAsync(d_kind + lo, kind + lo, (hi - lo) * 8, hipMemcpyHostToDevice, stream));
+			HIP_OK(launch_frames_dictgap(m.d_rec, nf, d_kind + lo, x.dict_gap, acc, m.d_desc, m.nb, stream));
+			HIP_OK(launch_dict_fill(m.d_desc, m.nb, static_cast<const uint8_t*>(x.d_dict), x.dict_gap, x.dict_used,
+			                        m.d_slots, stream));
+		}
 		HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
 		HIP_OK(launch_block_checksums_beside(d_in, m.d_desc, m.nb, m.d_st, stream));
 		HIP_OK(launch_index(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_st, stream));
-		HIP_OK(launch_decode_idx_frames(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_slots, m.d_st, m.d_rec, nf, stream));
+		if (dict)
+			HIP_OK(launch_decode_idx_frames_dict(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_slots, m.d_st, m.d_rec, nf,
+			                                     x.dict_used, stream));
+		else
+			HIP_OK(launch_decode_idx_frames(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_slots, m.d_st, m.d_rec, nf,
+			                                stream));
 		HIP_OK(join_block_checksums(stream));
 		HIP_OK(launch_frames_plan(m.d_desc, m.d_st, m.nb, m.d_rec, nf, m.d_off, m.d_loc, m.d_part, stream));
 		HIP_OK(launch_ckpt_save(d_kgrp, d_ckfirst, uint32_t(lo), nf, x.ckfirst[lo], uint32_t(x.ckfirst[hi] - x.ckfirst[lo]),
@@ -422,17 +480,40 @@ void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* 
 	}
 }
 
-// The one body of both builds.  linked: LZ4ADA_SEEK_LINKED, with a checkpoint
-// every `every` decoded bytes.
+// The one body of the builds.  linked: LZ4ADA_SEEK_LINKED, with a checkpoint
+// every `every` decoded bytes.  dict: null, or a dictionary of dict_len > 0 that
+// check_dict has passed.
 void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
-                 bool linked, uint64_t every, lz4ada_seek_index** idx, hipStream_t s)
+                 bool linked, uint64_t every, const lz4ada_device_dict* dict, lz4ada_seek_index** idx, hipStream_t s)
 {
 	FramesIndex ix;
 	index_jobs(entry, d_in, in_len, jobs, njobs, linked ? LZ4ADA_FRAMES_LINKED : 0, s, ix);
+	if (dict && (dict->flags & LZ4ADA_DICT_CHECK_ID))
+		check_dict_ids(ix, static_cast<const uint8_t*>(d_in), dict->dict_id, s);
 	size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
 	std::unique_ptr<lz4ada_seek_index, IndexDeleter> x(new lz4ada_seek_index);
 	const size_t n = ix.order.size();
 	x->in_len = in_len;
+	if (dict && n) {
+		// the index's own dictionary, as the gap every pass copies: zeros, then
+		// its last dict_used bytes (an allocation: 256-aligned)
+		x->dict_used = uint32_t(std::min<uint64_t>(uint64_t(dict->dict_len), DICT_MAX));
+		x->dict_gap = dict_gap(x->dict_used);
+		x->dict_bytes = size_t(x->dict_gap);
+		if (hipMalloc(&x->d_dict, x->dict_bytes) != hipSuccess) {
+			(void)hipGetLastError();
+			x->d_dict = nullptr;
+			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index's dictionary");
+		}
+		uint8_t* const img = static_cast<uint8_t*>(x->d_dict);
+		const size_t zeros = size_t(x->dict_gap) - x->dict_used;
+		HIP_OK(hipMemsetAsync(img, 0, zeros, s));
+		HIP_OK(hipMemcpyAsync(img + zeros,
+		                      static_cast<const uint8_t*>(dict->d_dict) + (uint64_t(dict->dict_len) - x->dict_used),
+		                      x->dict_used, hipMemcpyDeviceToDevice, s));
+		x->view.dict = img;
+		x->view.dict_used = x->dict_used;
+	}
 	if (linked && n) {
 		// the checkpoints of every linked frame the sizes stage accepted, and the
 		// linked frames decoded once into them
@@ -485,10 +566,11 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 		return;
 	}
 	// what the index keeps: 32 bytes per block, 16 for its two prefixes,
-	// 24 per frame (first, and the prefixes' end entries)
+	// 24 per frame (first, and the prefixes' end entries), and with a dictionary
+	// 8 more per frame: its kind
 	const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), first_b = (n + 1) * 8,
-	             pre_b = (size_t(nb) + n) * 8;
-	x->bytes = desc_b + first_b + 2 * pre_b;
+	             pre_b = (size_t(nb) + n) * 8, kind_b = x->dict_used ? n * 8 : 0;
+	x->bytes = desc_b + first_b + 2 * pre_b + kind_b;
 	if (hipMalloc(&x->d_mem, x->bytes) != hipSuccess) {
 		(void)hipGetLastError();
 		x->d_mem = nullptr;
@@ -504,6 +586,23 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 	x->view.start = x->d_start;
 	x->view.slotp = d_slotp;
 	x->view.nframes = uint32_t(n);
+	if (x->dict_used) {
+		// which blocks read the dictionary, by the final verdicts: every block of
+		// an independent modern frame, block 0 of a linked one, none of a legacy one
+		uint64_t* const d_kind = reinterpret_cast<uint64_t*>(m + desc_b + first_b + 2 * pre_b);
+		x->kind.assign(n, uint8_t(CHAIN_KIND_NONE));
+		HIP_OK(hipStreamSynchronize(s));  // nothing may still read the pinned buffer
+		PinBuf& h = scratch_cache().pin;
+		h.reserve(kind_b);
+		uint64_t* const w = reinterpret_cast<uint64_t*>(h.p);
+		for (size_t k = 0; k < n; ++k) {
+			if (ix.taken(k) && ix.walk[k].format == LZ4ADA_FORMAT_MODERN && ix.walk[k].nblocks > 0)
+				x->kind[k] = uint8_t(ix.linked(k) ? CHAIN_KIND_LINKED : CHAIN_KIND_INDEP);
+			w[k] = x->kind[k];
+		}
+		HIP_OK(hipMemcpyAsync(d_kind, w, kind_b, hipMemcpyHostToDevice, s));
+		x->view.fkind = d_kind;
+	}
 	FrameRec* const d_rec = reinterpret_cast<FrameRec*>(scratch(SC_BATCH_META, n * sizeof(FrameRec)));
 	if (!d_rec)
 		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index");
@@ -536,18 +635,24 @@ int lz4ada_seek_index_build(const void* d_in, int64_t in_len, lz4ada_device_fram
 			misuse(entry, "idx is NULL");
 		if (flags != 0)
 			misuse(entry, "flags must be 0");
-		build_index(entry, d_in, in_len, jobs, njobs, false, 0, idx, static_cast<hipStream_t>(stream));
+		build_index(entry, d_in, in_len, jobs, njobs, false, 0, nullptr, idx, static_cast<hipStream_t>(stream));
 	});
 }
 
-int lz4ada_seek_index_build_opt(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
-                                const lz4ada_seek_options* opt, lz4ada_seek_index** idx, void* stream)
+}  // extern "C"
+
+namespace lz4ada {
+namespace {
+
+// lz4ada_seek_index_build_opt, and with a dictionary of dict_len > 0 the _dict build.
+int seek_index_build_opt(const char* entry, const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs,
+                         int64_t njobs, const lz4ada_seek_options* opt, const lz4ada_device_dict* dict,
+                         lz4ada_seek_index** idx, void* stream)
 {
 	if (idx)
 		*idx = nullptr;
 	batch_stats() = lz4ada_batch_stats{};
 	return guarded(nullptr, [&] {
-		const char* const entry = "lz4ada_seek_index_build_opt";
 		if (!idx)
 			misuse(entry, "idx is NULL");
 		if (opt && (opt->flags & ~LZ4ADA_SEEK_LINKED))
@@ -556,10 +661,32 @@ int lz4ada_seek_index_build_opt(const void* d_in, int64_t in_len, lz4ada_device_
 			misuse(entry, "opt->reserved must be 0");
 		if (opt && opt->checkpoint_bytes < 0)
 			misuse(entry, "opt->checkpoint_bytes is negative");
+		check_dict(entry, dict);
 		const bool linked = opt && (opt->flags & LZ4ADA_SEEK_LINKED);
 		const uint64_t every = opt && opt->checkpoint_bytes ? uint64_t(opt->checkpoint_bytes) : SEEK_CHECKPOINT_BYTES;
-		build_index(entry, d_in, in_len, jobs, njobs, linked, every, idx, static_cast<hipStream_t>(stream));
+		build_index(entry, d_in, in_len, jobs, njobs, linked, every, dict && dict->dict_len > 0 ? dict : nullptr, idx,
+		            static_cast<hipStream_t>(stream));
 	});
+}
+
+}  // namespace
+}  // namespace lz4ada
+
+extern "C" {
+
+int lz4ada_seek_index_build_opt(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                                const lz4ada_seek_options* opt, lz4ada_seek_index** idx, void* stream)
+{
+	return seek_index_build_opt("lz4ada_seek_index_build_opt", d_in, in_len, jobs, njobs, opt, nullptr, idx, stream);
+}
+
+int lz4ada_seek_index_build_dict(const void* d_in, int64_t in_len, lz4ada_device_frame_job* jobs, int64_t njobs,
+                                 const lz4ada_seek_options* opt, const lz4ada_device_dict* dict,
+                                 lz4ada_seek_index** idx, void* stream)
+{
+	const bool none = !dict || dict->dict_len == 0;
+	return seek_index_build_opt(none ? "lz4ada_seek_index_build_opt" : "lz4ada_seek_index_build_dict", d_in, in_len,
+	                            jobs, njobs, opt, dict, idx, stream);
 }
 
 void lz4ada_seek_index_free(lz4ada_seek_index* idx)
@@ -570,10 +697,15 @@ void lz4ada_seek_index_free(lz4ada_seek_index* idx)
 		(void)hipFree(idx->d_mem);
 	if (idx->d_ck)
 		(void)hipFree(idx->d_ck);
+	if (idx->d_dict)
+		(void)hipFree(idx->d_dict);
 	delete idx;
 }
 
-int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index* idx) { return idx ? int64_t(idx->bytes + idx->ck_bytes) : 0; }
+int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index* idx)
+{
+	return idx ? int64_t(idx->bytes + idx->ck_bytes + idx->dict_bytes) : 0;
+}
 
 int lz4ada_decode_ranges_device(const lz4ada_seek_index* idx, const void* d_in, int64_t in_len,
                                 lz4ada_frame_range* ranges, int64_t nranges, void* d_out, int64_t out_cap,
@@ -657,6 +789,67 @@ int lz4ada_range_chains_host(int64_t nblocks, int64_t group, const int64_t* firs
 			return LZ4ADA_ASSERTION_ERROR;
 	*nchains = range_chains(uint64_t(nblocks), uint64_t(group), first, count, n, marked, head, chain_first, chain_count);
 	return LZ4ADA_OK;
+}
+
+int lz4ada_range_gaps_host(int64_t nblocks, int64_t group, int32_t kind, int64_t lo, int64_t hi, int64_t* heads,
+                           int64_t* dict_gaps)
+{
+	if (!heads || !dict_gaps || nblocks < 0 || group < 0 || kind < 0 || kind > int32_t(CHAIN_KIND_INDEP) || lo < 0 ||
+	    hi < lo || hi > nblocks)
+		return LZ4ADA_ASSERTION_ERROR;
+	*heads = int64_t(chain_heads(uint64_t(group), uint64_t(lo), uint64_t(hi)));
+	*dict_gaps = int64_t(chain_dict_gaps(uint32_t(kind), uint64_t(lo), uint64_t(hi)));
+	return LZ4ADA_OK;
+}
+
+// Test-only (lz4ada_hip.h): k_index over all the blocks, then k_decode_idx_chains
+// over chain records in the order given (no dealing), as a ranged pass over a
+// dictionary index writes them.
+int lz4ada_decode_idx_chains_debug(const void* d_frame, uint64_t frame_len, const lz4ada_block_desc* descs,
+                                   int64_t nblocks, const int64_t* first, const int64_t* count, const uint32_t* hist,
+                                   const uint8_t* gapped, int64_t nchains, void* d_out,
+                                   lz4ada_block_status* d_status, void* stream)
+{
+	return guarded(nullptr, [&] {
+		if (nblocks < 0 || nblocks >= (int64_t(1) << 31) || nchains < 0 || nchains >= (int64_t(1) << 31) ||
+		    (nblocks > 0 && (!descs || !d_status)) || (nchains > 0 && (!first || !count || !hist || !gapped)))
+			raise(LZ4ADA_CONSTRAINT_ERROR, "block or chain count out of range, or a NULL array");
+		for (int64_t i = 0; i < nchains; ++i)
+			if (first[i] < 0 || count[i] < 0 || first[i] > nblocks || count[i] > nblocks - first[i] ||
+			    (i > 0 && first[i] < first[i - 1] + count[i - 1]))
+				raise(LZ4ADA_CONSTRAINT_ERROR, "chains must rise within the blocks and not overlap");
+		if (nchains == 0 || nblocks == 0)
+			return;
+		device_check_or_raise();
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		const auto* const in = static_cast<const uint8_t*>(d_frame);
+		std::vector<lz4ada_block_desc> ds(descs, descs + nblocks);
+		std::vector<FrameRec> recs(static_cast<size_t>(nchains));
+		for (int64_t i = 0; i < nchains; ++i) {
+			FrameRec& r = recs[size_t(i)];
+			r = FrameRec{};
+			r.first = uint32_t(first[i]);
+			r.nblocks = uint32_t(count[i]);
+			r.flags = FRAME_LINKED;
+			r.hash = hist[i];
+			r.content_size = CHAIN_NO_CKPT;
+			r.fail = -1;
+			if (gapped[i] && count[i] > 0)
+				ds[size_t(first[i])].flags |= BLOCK_DICT;
+		}
+		DevBuf<lz4ada_block_desc> d_desc;
+		d_desc.reserve(ds.size());
+		DevBuf<FrameRec> d_rec;
+		d_rec.reserve(recs.size());
+		DevBuf<uint8_t> tab;
+		tab.reserve(index_table_bytes(frame_len, uint32_t(nblocks)));
+		vec_h2d(d_desc, ds, s);
+		vec_h2d(d_rec, recs, s);
+		HIP_OK(launch_index(in, frame_len, d_desc.p, uint32_t(nblocks), tab.p, d_status, s));
+		HIP_OK(launch_decode_idx_chains(in, frame_len, d_desc.p, uint32_t(nblocks), tab.p, static_cast<uint8_t*>(d_out),
+		                                d_status, d_rec.p, uint32_t(nchains), s));
+		HIP_OK(hipStreamSynchronize(s));
+	});
 }
 
 int lz4ada_seek_index_debug(const lz4ada_seek_index* idx, int64_t job, int32_t* reason, int64_t* nblocks,

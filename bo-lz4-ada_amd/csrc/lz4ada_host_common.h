@@ -537,6 +537,14 @@ void index_jobs(const char* entry, const void* d_in, int64_t in_len, const lz4ad
 void size_jobs(FramesIndex& ix, const uint8_t* d_in, uint64_t in_len, hipStream_t stream);
 int64_t report_index(const FramesIndex& ix, lz4ada_device_frame_job* jobs);
 int64_t report_sizes(const FramesIndex& ix, lz4ada_device_frame_job* jobs);
+// A dictionary call's dictionary.  check_dict: its misuse
+// (a negative length, a NULL pointer with bytes, unknown flag bits), raised
+// before any launch; dict may be null.  check_dict_ids (LZ4ADA_DICT_CHECK_ID),
+// after index_jobs: a taken modern frame naming another id is no longer
+// taken(), LZ4ADA_DEVFRAME_DICT its verdict on the host and on the device; one
+// host synchronisation.
+void check_dict(const char* entry, const lz4ada_device_dict* dict);
+void check_dict_ids(FramesIndex& ix, const uint8_t* d_in, uint32_t dict_id, hipStream_t stream);
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

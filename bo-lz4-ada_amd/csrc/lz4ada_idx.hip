@@ -2780,6 +2780,56 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 		status[r].code = DS_RETRY;
 }
 
+// The chains of a ranged pass over a dictionary index: that
+// loop with the starting history read from the chain's record (`hash`, which
+// chain records otherwise leave unused) instead of a launch argument, so one
+// launch decodes chains that start from a checkpoint (65,536 bytes) beside
+// chains that start from the dictionary (dict_used).  The history is clamped
+// to DICT_MAX, and it is believed only where the layout can hold it: the
+// chain's first block must carry BLOCK_DICT and lie at least dict_gap(hist)
+// into the slots, else the chain's blocks get DS_RETRY and nothing is decoded.
+// Same clamps: no status and no slot outside the chain's blocks is written
+// whatever the record says.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_chains(
+        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
+        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
+        lz4ada_block_status* __restrict__ status, const FrameRec* __restrict__ chains, uint32_t nchains)
+{
+	__shared__ DecLds D;
+	if (blockIdx.x >= nchains)
+		return;
+	const uint32_t flags = chains[blockIdx.x].flags;
+	if (!(flags & FRAME_LINKED))
+		return;
+	const uint32_t first = min(chains[blockIdx.x].first, nblocks);
+	const uint32_t bend = first + min(chains[blockIdx.x].nblocks, nblocks - first);
+	if (first >= bend)
+		return;
+	const uint32_t h0 = min(wave_uniform(chains[blockIdx.x].hash), DICT_MAX);
+	int64_t hist = int64_t(h0);
+	uint32_t stop = bend;  // the first block left DS_RETRY
+	if (!(wave_uniform(desc[first].flags) & BLOCK_DICT) || wave_uniform(desc[first].out_off) < dict_gap(h0))
+		stop = first;
+	for (uint32_t b = first; b < stop; ++b) {
+		int32_t len;
+		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status, hist, len);
+		vm_wait();  // the next block reads this output as history
+		__syncthreads();
+		if (code != DS_OK) {
+			stop = b + 1;  // (its own status is non-zero already)
+			break;
+		}
+		if (b + 1 < bend && (uint32_t(len) != desc[b].out_cap ||
+		                     desc[b + 1].out_off != desc[b].out_off + uint64_t(len))) {
+			stop = b + 1;  // the next block's history would not be contiguous
+			break;
+		}
+		hist += len;
+	}
+	for (uint32_t r = stop + lane_id(); r < bend; r += 64)
+		status[r].code = DS_RETRY;
+}
+
 // ============================================================ pipelined pair
 // k_decode_pp2 (round 5): two waves per block that pipeline consecutive
 // batches instead of splitting each one (k_decode_idx2), for launches of at
@@ -3500,6 +3550,18 @@ hipError_t launch_decode_idx_frames_dict(const uint8_t* d_frame, uint64_t frame_
 		return hipSuccess;
 	hipLaunchKernelGGL(idx::k_decode_idx_frames_dict, dim3(nframes), dim3(64), 0, stream, d_frame, frame_len,
 	                   d_desc, nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, d_frames, nframes, dict_used);
+	return hipGetLastError();
+}
+
+hipError_t launch_decode_idx_chains(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
+                                    uint32_t nblocks, const uint8_t* d_tab, uint8_t* d_out,
+                                    lz4ada_block_status* d_status, const FrameRec* d_chains, uint32_t nchains,
+                                    hipStream_t stream)
+{
+	if (nchains == 0 || nblocks == 0)
+		return hipSuccess;
+	hipLaunchKernelGGL(idx::k_decode_idx_chains, dim3(nchains), dim3(64), 0, stream, d_frame, frame_len, d_desc,
+	                   nblocks, const_cast<uint8_t*>(d_tab), d_out, d_status, d_chains, nchains);
 	return hipGetLastError();
 }
 

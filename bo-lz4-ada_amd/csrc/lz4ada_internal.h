@@ -481,6 +481,16 @@ hipError_t launch_decode_idx_frames_dict(const uint8_t* d_frame, uint64_t frame_
                                          const lz4ada_block_desc* d_desc, uint32_t nblocks, const uint8_t* d_tab,
                                          uint8_t* d_out, lz4ada_block_status* d_status, const FrameRec* d_frames,
                                          uint32_t nframes, uint32_t dict_used, hipStream_t stream);
+// k_decode_idx_chains: launch_decode_idx_frames_dict with the starting history
+// of every chain in its own record (`hash`, clamped to DICT_MAX) instead of one
+// for the launch: a ranged pass over a dictionary index decodes chains from
+// checkpoints (65,536) and chains from the dictionary (dict_used) side by side
+// (DESIGN.md §19).  A chain whose first block lacks BLOCK_DICT or lies less
+// than dict_gap(history) into the slots gets DS_RETRY on its blocks.
+hipError_t launch_decode_idx_chains(const uint8_t* d_frame, uint64_t frame_len, const lz4ada_block_desc* d_desc,
+                                    uint32_t nblocks, const uint8_t* d_tab, uint8_t* d_out,
+                                    lz4ada_block_status* d_status, const FrameRec* d_chains, uint32_t nchains,
+                                    hipStream_t stream);
 
 // ---- seek index and ranged decode (lz4ada_ranges.hip) ----
 // The device arrays of a seek index over nframes frames in rising in_off, as
@@ -494,6 +504,10 @@ hipError_t launch_decode_idx_frames_dict(const uint8_t* d_frame, uint64_t frame_
 // ckfirst: n + 1 entries, frame k's checkpoints are [ckfirst[k], ckfirst[k + 1])
 // among the nckpt entries of CKPT_BYTES bytes each at store.  All three are
 // null / 0 in an index built without LZ4ADA_SEEK_LINKED.
+// An index built with a dictionary has dict_used > 0, fkind:
+// frame k's DICT_KIND_* (which of its blocks read the dictionary), and dict:
+// the index's own copy as a gap image of dict_gap(dict_used) bytes, zeros and
+// then the dictionary's last dict_used bytes.  Null / 0 otherwise.
 struct SeekView {
 	const lz4ada_block_desc* desc;
 	const uint64_t* first;
@@ -504,6 +518,9 @@ struct SeekView {
 	const uint64_t* ckfirst;
 	const uint8_t* store;
 	uint64_t nckpt;
+	const uint64_t* fkind;
+	const uint8_t* dict;
+	uint32_t dict_used;
 };
 // One range with bytes to deliver, as the host hands it to the kernels.
 struct RangeRec {
@@ -531,18 +548,21 @@ hipError_t launch_block_starts(const uint64_t* d_first, const uint64_t* d_size_f
 // b of the range's chain (lz4ada_range_chains.h: the blocks it touches, and in
 // a linked frame those from its group's start on) inside [span_lo, span_lo +
 // span_n), with RANGE_MARK_GAP added for a head (the same value from every
-// writer).  Reads the index alone.
+// writer), and in a dictionary index RANGE_MARK_DICT for a block that reads the
+// dictionary (chain_dict_gapped).  Reads the index alone.
 constexpr uint32_t RANGE_MARK_GAP = 0x80000000u;
+constexpr uint32_t RANGE_MARK_DICT = 0x40000000u;
+constexpr uint32_t RANGE_MARK_BITS = RANGE_MARK_GAP | RANGE_MARK_DICT;  // the size field needs 15 bits
 // The gap in front of a head's slot: its checkpoint as a dictionary of DICT_MAX bytes.
 constexpr uint64_t CKPT_GAP = (uint64_t(DICT_MAX) + 32 + 255) & ~uint64_t(255);
 hipError_t launch_ranges_select(const SeekView& v, const RangeRec* d_ranges, uint32_t nranges, RangeSel* d_sel,
                                 uint32_t* d_mark, uint64_t span_lo, uint32_t span_n, hipStream_t stream);
 // One workgroup: d_cnt[i] / d_slot[i] get the marked blocks before span block i
 // and where block i's bytes begin: past the slot bytes of the marked blocks
-// before it and past the gaps (`gap` bytes per RANGE_MARK_GAP) up to its own;
-// entry span_n the totals.
-hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t gap, uint32_t* d_cnt,
-                              uint64_t* d_slot, hipStream_t stream);
+// before it and past the gaps (`gap` bytes per RANGE_MARK_GAP, `dict_gap` per
+// RANGE_MARK_DICT) up to its own; entry span_n the totals.
+hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t gap, uint64_t dict_gap,
+                              uint32_t* d_cnt, uint64_t* d_slot, hipStream_t stream);
 // One lane per span block: a marked block's descriptor goes to d_desc[d_cnt[i]]
 // with out_off = d_slot[i] and out_cap = its exact size.  Writes no descriptor
 // at or past nsel and places no block past slots (an empty one instead).
@@ -552,7 +572,10 @@ hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t 
 // number among the store's in content_size) or a marked block 0 of a linked
 // frame carries FRAME_LINKED, first = its own place and nblocks = the marked
 // blocks of its group from it on (a walk over at most K marks); every other
-// record has flags 0.
+// record has flags 0.  `hash` holds the chain's starting history: CKPT_BYTES
+// for a head.  In a dictionary index a block with RANGE_MARK_DICT starts a
+// chain too (BLOCK_DICT, hash = dict_used, content_size = CHAIN_NO_CKPT: of an
+// independent frame a chain of that block alone, of a linked one block 0's).
 hipError_t launch_ranges_fill(const SeekView& v, const uint32_t* d_mark, const uint32_t* d_cnt,
                               const uint64_t* d_slot, uint64_t span_lo, uint32_t span_n, uint32_t nsel,
                               uint64_t slots, lz4ada_block_desc* d_desc, FrameRec* d_chain, hipStream_t stream);
@@ -562,6 +585,14 @@ hipError_t launch_ranges_fill(const SeekView& v, const uint32_t* d_mark, const u
 // where out_off < CKPT_GAP or out_off > slots.
 hipError_t launch_ckpt_fill(const SeekView& v, const lz4ada_block_desc* d_desc, const FrameRec* d_chain,
                             uint32_t nsel, uint8_t* d_slots, uint64_t slots, hipStream_t stream);
+// A chain record's content_size when its history is the dictionary, not a checkpoint.
+constexpr uint64_t CHAIN_NO_CKPT = ~uint64_t(0);
+// k_ckpt_fill's sibling for the dictionary: in front of the slot of every
+// BLOCK_DICT block whose chain record says CHAIN_NO_CKPT, the index's gap image,
+// dict_gap(dict_used) bytes.  Writes inside [out_off - dict_gap, out_off) only,
+// and nothing where out_off < dict_gap or out_off > slots.
+hipError_t launch_dictimg_fill(const SeekView& v, const lz4ada_block_desc* d_desc, const FrameRec* d_chain,
+                               uint32_t nsel, uint8_t* d_slots, uint64_t slots, hipStream_t stream);
 // The build: the checkpoints [ck_lo, ck_lo + nck) of the index, which are those
 // of the sorted frames [f_lo, f_lo + nf) of one decode pass (d_rec: the pass's
 // frame records after launch_frames_plan, d_desc its descriptors), from the

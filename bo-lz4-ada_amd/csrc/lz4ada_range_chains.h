@@ -21,7 +21,10 @@
 // k_ranges_verdict (lz4ada_ranges.hip) and the host's sweep (plan_pass,
 // lz4ada_bulk_ranges.cpp) call it, the host states it through
 // lz4ada_range_chains_host, and tests/test_ranges_linked_cpu.py and
-// tools/range_chains_asan.cpp pin it to a brute-force definition.
+// tools/range_chains_asan.cpp pin it to a brute-force definition.  The gap
+// count of an interval (chain_heads, and for a dictionary index
+// chain_dict_gaps) goes through lz4ada_range_gaps_host, pinned likewise by
+// tests/test_ranges_dict_cpu.py and tools/range_gaps_asan.cpp.
 //
 // Depends on nothing, so a plain C++ program can include it.
 #pragma once
@@ -51,6 +54,29 @@ LZ4ADA_RC_HD inline uint64_t chain_heads(uint64_t K, uint64_t lo, uint64_t hi)
 	if (!K || hi <= lo)
 		return 0;
 	return (hi - 1) / K - (lo ? (lo - 1) / K : 0);
+}
+
+// A seek index over dictionary frames knows a second kind of
+// gap: the dictionary in front of a block that reads it.  Which blocks those
+// are depends on the frame's kind alone (the values of DICT_KIND_*,
+// lz4ada_internal.h): every block of an independent modern frame, block 0 of a
+// linked one, none of a legacy frame's or in an index without a dictionary.
+constexpr uint32_t CHAIN_KIND_NONE = 0, CHAIN_KIND_LINKED = 1, CHAIN_KIND_INDEP = 2;
+
+// Block b, when marked, is decoded with the dictionary in front of it.
+LZ4ADA_RC_HD inline bool chain_dict_gapped(uint32_t kind, uint64_t b)
+{
+	return kind == CHAIN_KIND_INDEP || (kind == CHAIN_KIND_LINKED && b == 0);
+}
+
+// The dictionary-gapped blocks among the blocks [lo, hi).  With chain_heads
+// the gap count of an interval: no block takes both gaps (a head is not block
+// 0, and an independent frame has no head).
+LZ4ADA_RC_HD inline uint64_t chain_dict_gaps(uint32_t kind, uint64_t lo, uint64_t hi)
+{
+	if (hi <= lo)
+		return 0;
+	return kind == CHAIN_KIND_INDEP ? hi - lo : kind == CHAIN_KIND_LINKED && lo == 0 ? 1 : 0;
 }
 
 // Past the last block of b's group in a frame of nb blocks.

@@ -24,6 +24,14 @@
 // marks reach back to the group's start, a head's mark carries RANGE_MARK_GAP,
 // the scan turns that bit into the gap's bytes, and the fill writes one chain
 // record per compacted block for k_decode_idx_frames_dict.
+// An index built with a dictionary adds a second gap, the
+// dictionary's: select sets RANGE_MARK_DICT on the marked blocks that read it
+// (chain_dict_gapped), the scan lays dict_gap(dict_used) bytes in front of
+// them, the fill makes each the start of a chain whose record carries its
+// history length, and
+//  * k_dictimg_fill -- one workgroup per compacted block: the index's gap
+//    image into the gap in front of such a block's slot;
+// the chains of all three kinds then decode in one k_decode_idx_chains.
 // Every bound is taken from the index's arrays and the host's counts; no
 // kernel here reads a frame byte, and none lets a block status steer an
 // address.  Plain vector stores only.
@@ -47,6 +55,9 @@ constexpr uint32_t GATHER_WG = 256;
 constexpr uint32_t CKPT_WG = 256;
 static_assert(CKPT_GAP >= CKPT_BYTES + 32 && CKPT_GAP % 256 == 0 && CKPT_BYTES == DICT_MAX,
               "a checkpoint is a dictionary of DICT_MAX bytes in a gap of dict_gap(DICT_MAX)");
+static_assert(CHAIN_KIND_NONE == DICT_KIND_NONE && CHAIN_KIND_LINKED == DICT_KIND_LINKED &&
+                  CHAIN_KIND_INDEP == DICT_KIND_INDEP,
+              "the chain rule names the frame kinds as a dictionary pass does");
 static_assert(CKPT_BYTES % (CKPT_SAVE_SPLIT * CKPT_WG * 16) == 0, "k_ckpt_save's pieces tile a checkpoint");
 
 // 16 bytes at any byte address: one global_load_dwordx4 (gfx950 takes an
@@ -137,6 +148,8 @@ __global__ __launch_bounds__(WAVE) void k_ranges_select(SeekView v, const RangeR
 	// the chain: in a linked frame the marks begin at the group's start
 	const uint64_t K = v.kgrp ? wave_uniform(v.kgrp[k]) : 0;
 	const uint64_t c0 = n ? chain_start(K, b0) : b0;
+	// a dictionary index: the frame's kind says which marked blocks read it
+	const uint32_t kind = v.dict_used && v.fkind ? uint32_t(wave_uniform(v.fkind[k])) : CHAIN_KIND_NONE;
 	if (sel && lane_id() == 0) {
 		RangeSel r;
 		r.first = uint32_t(b0);
@@ -151,24 +164,26 @@ __global__ __launch_bounds__(WAVE) void k_ranges_select(SeekView v, const RangeR
 		for (uint64_t j = c0 + lane_id(); j < b0 + n; j += WAVE) {
 			const uint64_t b = f + j;
 			if (b >= span_lo && b - span_lo < span_n)
-				mark[b - span_lo] = (1u + (uint32_t((sp[j + 1] - sp[j]) >> 8) & ~RANGE_MARK_GAP)) |
-				                    (chain_head(K, j) ? RANGE_MARK_GAP : 0u);
+				mark[b - span_lo] = (1u + (uint32_t((sp[j + 1] - sp[j]) >> 8) & ~RANGE_MARK_BITS)) |
+				                    (chain_head(K, j) ? RANGE_MARK_GAP : 0u) |
+				                    (chain_dict_gapped(kind, j) ? RANGE_MARK_DICT : 0u);
 		}
 	}
 }
 
 __global__ __launch_bounds__(RSCAN_WG) void k_ranges_scan(const uint32_t* __restrict__ mark, uint32_t span_n,
-                                                          uint64_t gap, uint32_t* __restrict__ cnt,
-                                                          uint64_t* __restrict__ slot)
+                                                          uint64_t gap, uint64_t dgap,
+                                                          uint32_t* __restrict__ cnt, uint64_t* __restrict__ slot)
 {
 	__shared__ uint64_t wsum[RSCAN_WG / 64];
 	uint64_t carry_c = 0, carry_s = 0;
 	for (uint32_t i0 = 0; i0 < span_n; i0 += RSCAN_WG) {
 		const uint32_t i = i0 + threadIdx.x;
-		const uint32_t mg = i < span_n ? mark[i] : 0u, m = mg & ~RANGE_MARK_GAP;
+		const uint32_t mg = i < span_n ? mark[i] : 0u, m = mg & ~RANGE_MARK_BITS;
 		// a head's gap lies in front of its slot: part of what it takes, and of
-		// where its own bytes begin
-		const uint64_t g = (mg & RANGE_MARK_GAP) && m ? gap : 0u;
+		// where its own bytes begin; so does the dictionary's (no block has both:
+		// should a mark carry both bits, the head's gap alone is laid)
+		const uint64_t g = !m ? 0u : (mg & RANGE_MARK_GAP) ? gap : (mg & RANGE_MARK_DICT) ? dgap : 0u;
 		const uint64_t c = m ? 1u : 0u, s = m ? (uint64_t(m - 1) << 8) + g : 0u;
 		uint64_t total_c, total_s;
 		const uint64_t off_c = wg_excl_scan<RSCAN_WG>(c, wsum, &total_c);
@@ -194,7 +209,7 @@ __global__ __launch_bounds__(FILL_WG) void k_ranges_fill(SeekView v, const uint3
                                                          FrameRec* __restrict__ chain)
 {
 	const uint32_t i = blockIdx.x * FILL_WG + threadIdx.x;
-	if (i >= span_n || (mark[i] & ~RANGE_MARK_GAP) == 0)
+	if (i >= span_n || (mark[i] & ~RANGE_MARK_BITS) == 0)
 		return;
 	const uint32_t at = cnt[i];
 	if (at >= nsel)  // the host counted the same marks: does not happen
@@ -227,7 +242,33 @@ __global__ __launch_bounds__(FILL_WG) void k_ranges_fill(SeekView v, const uint3
 		const uint64_t K = v.kgrp ? v.kgrp[k] : 0;
 		const uint64_t j = b - v.first[k], nb = v.first[k + 1] - v.first[k];
 		const bool head = (mark[i] & RANGE_MARK_GAP) != 0;
-		if (K && d.out_cap == size && (head || j == 0)) {
+		// the dictionary's gap: only where the index has one and the frame's kind agrees
+		const uint32_t kind = v.dict_used && v.fkind ? uint32_t(v.fkind[k]) : CHAIN_KIND_NONE;
+		const bool dgapped = !head && (mark[i] & RANGE_MARK_DICT) != 0;
+		if (dgapped && d.out_cap == size) {
+			// a dictionary-gapped block without its gap is an empty block
+			if (!chain_dict_gapped(kind, j) || (K != 0) != (kind == CHAIN_KIND_LINKED) ||
+			    d.out_off < dict_gap(v.dict_used)) {
+				d.in_len = 0;
+				d.flags = LZ4ADA_BLOCK_STORED;
+				d.out_cap = 0;
+				d.out_off = 0;
+			} else {
+				// block 0 of a linked frame: the marked blocks of its group ride; an
+				// independent frame's block: a chain of its own
+				uint32_t run = 1;
+				if (K) {
+					const uint64_t e = chain_group_end(K, nb, j);
+					while (j + run < e && i + run < span_n && (mark[i + run] & ~RANGE_MARK_BITS) != 0)
+						++run;
+				}
+				r.flags = FRAME_LINKED;
+				r.nblocks = run;
+				r.hash = v.dict_used;
+				r.content_size = CHAIN_NO_CKPT;
+				d.flags |= BLOCK_DICT;
+			}
+		} else if (K && d.out_cap == size && (head || j == 0)) {
 			const uint64_t ck = head ? v.ckfirst[k] + chain_checkpoint_of(K, j) : 0;
 			// a head without its gap or its checkpoint is an empty block
 			if (head && (!chain_head(K, j) || ck >= v.ckfirst[k + 1] || ck >= v.nckpt || d.out_off < CKPT_GAP)) {
@@ -238,13 +279,15 @@ __global__ __launch_bounds__(FILL_WG) void k_ranges_fill(SeekView v, const uint3
 			} else {
 				const uint64_t e = chain_group_end(K, nb, j);
 				uint32_t run = 1;
-				while (j + run < e && i + run < span_n && (mark[i + run] & ~RANGE_MARK_GAP) != 0)
+				while (j + run < e && i + run < span_n && (mark[i + run] & ~RANGE_MARK_BITS) != 0)
 					++run;
 				r.flags = FRAME_LINKED;
 				r.nblocks = run;
 				r.content_size = ck;
-				if (head)
+				if (head) {
+					r.hash = uint32_t(CKPT_BYTES);
 					d.flags |= BLOCK_DICT;
+				}
 			}
 		}
 		chain[chain_slot(at, nsel)] = r;
@@ -275,6 +318,27 @@ __global__ __launch_bounds__(CKPT_WG) void k_ckpt_fill(SeekView v, const lz4ada_
 	for (uint32_t x = 16 * t; x < uint32_t(CKPT_BYTES); x += 16 * CKPT_WG) {
 		const u32x4 w = *reinterpret_cast<const GLOBAL u32x4*>(src + x);
 		*reinterpret_cast<GLOBAL u32x4*>(dst + ZEROS + x) = w;
+	}
+}
+
+__global__ __launch_bounds__(CKPT_WG) void k_dictimg_fill(SeekView v, const lz4ada_block_desc* __restrict__ desc,
+                                                          const FrameRec* __restrict__ chain, uint32_t nsel,
+                                                          uint8_t* __restrict__ slots_p, uint64_t slots)
+{
+	if (blockIdx.x >= nsel || !v.dict || v.dict_used == 0 || v.dict_used > DICT_MAX)
+		return;
+	const lz4ada_block_desc d = desc[blockIdx.x];
+	const FrameRec r = chain[chain_slot(blockIdx.x, nsel)];
+	const uint64_t gap = dict_gap(v.dict_used);
+	if (!(d.flags & BLOCK_DICT) || !(r.flags & FRAME_LINKED) || r.content_size != CHAIN_NO_CKPT || d.out_off < gap ||
+	    d.out_off > slots)
+		return;
+	// 256-aligned on both sides: out_off and the gap are, and the image is an allocation
+	g8* const dst = gptr(slots_p) + (d.out_off - gap);
+	cg8* const src = gptr(v.dict);
+	for (uint32_t x = 16 * threadIdx.x; x < uint32_t(gap); x += 16 * CKPT_WG) {
+		const u32x4 w = *reinterpret_cast<const GLOBAL u32x4*>(src + x);
+		*reinterpret_cast<GLOBAL u32x4*>(dst + x) = w;
 	}
 }
 
@@ -404,7 +468,7 @@ __global__ __launch_bounds__(GATHER_WG) void k_ranges_gather(SeekView v, const R
 		const uint64_t in_block = x - st[j], avail = st[j + 1] - x;
 		const uint64_t take = avail < rem ? avail : rem;
 		const uint64_t b = f + j;
-		if (take && b >= span_lo && b - span_lo < span_n && (mark[b - span_lo] & ~RANGE_MARK_GAP)) {
+		if (take && b >= span_lo && b - span_lo < span_n && (mark[b - span_lo] & ~RANGE_MARK_BITS)) {
 			const uint64_t at = slot[b - span_lo] + in_block;
 			if (at + take <= slots)
 				wg_copy(dst, src + at, take);
@@ -435,10 +499,11 @@ hipError_t launch_ranges_select(const SeekView& v, const RangeRec* d_ranges, uin
 	return hipGetLastError();
 }
 
-hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t gap, uint32_t* d_cnt,
-                              uint64_t* d_slot, hipStream_t stream)
+hipError_t launch_ranges_scan(const uint32_t* d_mark, uint32_t span_n, uint64_t gap, uint64_t dict_gap,
+                              uint32_t* d_cnt, uint64_t* d_slot, hipStream_t stream)
 {
-	hipLaunchKernelGGL(k_ranges_scan, dim3(1), dim3(RSCAN_WG), 0, stream, d_mark, span_n, gap, d_cnt, d_slot);
+	hipLaunchKernelGGL(k_ranges_scan, dim3(1), dim3(RSCAN_WG), 0, stream, d_mark, span_n, gap, dict_gap, d_cnt,
+	                   d_slot);
 	return hipGetLastError();
 }
 
@@ -459,6 +524,15 @@ hipError_t launch_ckpt_fill(const SeekView& v, const lz4ada_block_desc* d_desc, 
 	if (nsel == 0 || v.nckpt == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_ckpt_fill, dim3(nsel), dim3(CKPT_WG), 0, stream, v, d_desc, d_chain, nsel, d_slots, slots);
+	return hipGetLastError();
+}
+
+hipError_t launch_dictimg_fill(const SeekView& v, const lz4ada_block_desc* d_desc, const FrameRec* d_chain,
+                               uint32_t nsel, uint8_t* d_slots, uint64_t slots, hipStream_t stream)
+{
+	if (nsel == 0 || v.dict_used == 0 || !v.dict)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_dictimg_fill, dim3(nsel), dim3(CKPT_WG), 0, stream, v, d_desc, d_chain, nsel, d_slots, slots);
 	return hipGetLastError();
 }
 

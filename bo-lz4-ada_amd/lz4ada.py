@@ -290,6 +290,10 @@ _sig = {
     "lz4ada_block_size_host": ([_vp, _i64, ctypes.c_int], _i64),
     "lz4ada_seek_index_build": ([_vp, _i64, _vp, _i64, ctypes.c_uint32, ctypes.POINTER(_vp), _vp], ctypes.c_int),
     "lz4ada_seek_index_build_opt": ([_vp, _i64, _vp, _i64, _vp, ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_seek_index_build_dict": ([_vp, _i64, _vp, _i64, _vp, _vp, ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_decode_idx_chains_debug": ([_vp, ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+                                       ctypes.c_int),
+    "lz4ada_range_gaps_host": ([_i64, _i64, ctypes.c_int32, _i64, _i64, _pi64, _pi64], ctypes.c_int),
     "lz4ada_range_chains_host": ([_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _pi64], ctypes.c_int),
     "lz4ada_seek_index_free": ([_vp], None),
     "lz4ada_seek_index_bytes": ([_vp], _i64),
@@ -1007,16 +1011,25 @@ class SeekIndex:
 
     @classmethod
     def build(cls, d_in: int, in_len: int, spans, stream: int = 0, flags: int = 0, linked: bool = False,
-              checkpoint_bytes: int = 0):
+              checkpoint_bytes: int = 0, dict=None, dict_len: int = 0, dict_id=None):
         """Index the frames at spans [(in_off, in_len)] of the device buffer
         d_in (raw pointer).  Linked frames are refused (BATCH_LINKED) unless
         linked is set: then the build decodes each once and keeps a history
         checkpoint every checkpoint_bytes decoded bytes (0: 1 MiB), through
         lz4ada_seek_index_build_opt.  flags goes to
-        lz4ada_seek_index_build as it is."""
+        lz4ada_seek_index_build as it is.  dict: a raw device pointer to
+        dict_len bytes, the dictionary every frame shares, or a DeviceDict
+        (lz4ada_seek_index_build_dict): the index keeps its own
+        copy, so the ranged calls take none.  dict_id: when given, a frame
+        naming another dictionary id is rejected (DEVFRAME_DICT)."""
         jobs = _device_jobs(spans)
         ptr = _vp()
-        if linked or checkpoint_bytes:
+        if dict is not None or dict_len or dict_id is not None:
+            dd = dict if isinstance(dict, DeviceDict) else _seek_dict(dict, dict_len, dict_id)
+            opt = SeekOptions(SEEK_LINKED if linked else 0, 0, checkpoint_bytes)
+            st = _lib.lz4ada_seek_index_build_dict(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
+                                                   ctypes.byref(dd), ctypes.byref(ptr), stream)
+        elif linked or checkpoint_bytes:
             opt = SeekOptions(SEEK_LINKED if linked else 0, 0, checkpoint_bytes)
             st = _lib.lz4ada_seek_index_build_opt(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
                                                   ctypes.byref(ptr), stream)
@@ -1026,12 +1039,20 @@ class SeekIndex:
         return cls(ptr.value, jobs, len(spans), in_len)
 
     @classmethod
-    def build_tensor(cls, t, spans, linked: bool = False, checkpoint_bytes: int = 0):
-        """build for a CUDA torch.uint8 tensor, on torch's current stream."""
+    def build_tensor(cls, t, spans, linked: bool = False, checkpoint_bytes: int = 0, dict=None, dict_id=None):
+        """build for a CUDA torch.uint8 tensor, on torch's current stream.
+        dict: a CUDA uint8 tensor on the same device holding the dictionary
+        every frame shares (it may be freed after the build); dict_id: as in
+        build."""
         _frames_tensor(t)
+        dd = None
+        if dict is not None:
+            if not (dict.is_cuda and dict.device == t.device and dict.dtype == torch.uint8 and dict.is_contiguous()):
+                raise ValueError("the dictionary must be a contiguous CUDA uint8 tensor on the frames' device")
+            dd = _seek_dict(dict.data_ptr() if dict.numel() else None, dict.numel(), dict_id)
         with torch.cuda.device(t.device):
             return cls.build(t.data_ptr(), t.numel(), spans, torch.cuda.current_stream().cuda_stream,
-                             linked=linked, checkpoint_bytes=checkpoint_bytes)
+                             linked=linked, checkpoint_bytes=checkpoint_bytes, dict=dd)
 
     @property
     def device_bytes(self) -> int:
@@ -1053,6 +1074,13 @@ class SeekIndex:
             self.free()
         except Exception:
             pass
+
+
+def _seek_dict(d_dict, dict_len, dict_id):
+    """The DeviceDict of SeekIndex.build's keywords, as decode_frames_tensor
+    makes its own: the id is compared only when one is given."""
+    return DeviceDict(d_dict if dict_len else None, dict_len, 0 if dict_id is None else dict_id,
+                      0 if dict_id is None else DICT_CHECK_ID)
 
 
 def _frames_tensor(t):
@@ -1152,6 +1180,17 @@ def range_chains_host(nblocks: int, group: int, touched):
            "range_chains_host: a NULL or out-of-range argument")
     return ([b for b in range(nblocks) if marked[b]], [b for b in range(nblocks) if head[b]],
             [(cf[i], cc[i]) for i in range(nc.value)])
+
+
+def range_gaps_host(nblocks: int, group: int, kind: int, lo: int, hi: int):
+    """Test-only: the gap count of the blocks [lo, hi) of one frame on the host
+    (lz4ada_range_chains.h) -> (heads, dictionary-gapped blocks).  kind: 0 none
+    read the dictionary, 1 a linked frame (block 0 does), 2 an independent
+    modern frame (every block does)."""
+    heads, gaps = _i64(), _i64()
+    _check(_lib.lz4ada_range_gaps_host(nblocks, group, kind, lo, hi, ctypes.byref(heads), ctypes.byref(gaps)),
+           "range_gaps_host: a NULL or out-of-range argument")
+    return heads.value, gaps.value
 
 
 def seek_index_debug(idx: SeekIndex, stream: int = 0):
@@ -1378,6 +1417,21 @@ def decode_idx_frames_debug(d_frame, frame_len, d_descs, nblocks, first, linked,
     f = (_i64 * (nframes + 1))(*first)
     m = (ctypes.c_uint8 * max(nframes, 1))(*[1 if x else 0 for x in linked])
     _check(_lib.lz4ada_decode_idx_frames_debug(d_frame, frame_len, d_descs, nblocks, f, m, nframes,
+                                               d_out, d_status, stream), _thread_error())
+
+
+def decode_idx_chains_debug(d_frame, frame_len, descs, nblocks, chains, d_out, d_status, stream=0):
+    """Test-only: k_index + k_decode_idx_chains alone.  descs: a
+    BlockDesc array on the host; chains: [(first block, count, history bytes,
+    gapped)], rising and disjoint -- the history lies in front of the first
+    block's slot in d_out, and gapped marks that block as having such a gap.
+    d_status: zeroed device statuses.  Returns after the stream has drained."""
+    n = len(chains)
+    first = (_i64 * max(n, 1))(*[c[0] for c in chains])
+    count = (_i64 * max(n, 1))(*[c[1] for c in chains])
+    hist = (ctypes.c_uint32 * max(n, 1))(*[c[2] for c in chains])
+    gapped = (ctypes.c_uint8 * max(n, 1))(*[1 if c[3] else 0 for c in chains])
+    _check(_lib.lz4ada_decode_idx_chains_debug(d_frame, frame_len, descs, nblocks, first, count, hist, gapped, n,
                                                d_out, d_status, stream), _thread_error())
 
 

@@ -831,8 +831,67 @@ int lz4ada_seek_index_build_opt(const void *d_in, int64_t in_len,
                                 const lz4ada_seek_options *opt,
                                 lz4ada_seek_index **idx, void *stream);
 
+/*
+ * Dictionary frames in the seek index: the small
+ * records a dictionary exists for are the ones a caller fetches by position.
+ * lz4ada_seek_index_build_dict is lz4ada_seek_index_build_opt with one
+ * dictionary, as lz4ada_decode_frames_device_dict takes it, shared by every
+ * frame of the index.  dict == NULL or dict_len == 0 is
+ * lz4ada_seek_index_build_opt itself, launch by launch, and the index runs every
+ * ranged call as before.  lz4ada_decode_ranges_device keeps its signature and
+ * takes no dictionary:
+ *
+ * The index owns its dictionary.  The build copies the last dict_used =
+ * min(dict_len, 65536) bytes into device memory of its own, laid out as the gap
+ * a pass puts in front of a block: G = round256(dict_used + 32) bytes, G -
+ * dict_used zeros and then the bytes.  The caller may free or overwrite d_dict
+ * once the build returns; a ranged call cannot be handed another dictionary.
+ * lz4ada_seek_index_bytes, exactly, adds to the two lines above
+ *   + G + 8 * n                                   a dictionary, n > 0
+ * (8 per job: which of the frame's blocks read the dictionary); an index over
+ * n == 0 jobs holds nothing and makes no device call.
+ *
+ * Semantics are those of lz4ada_decode_frames_device_dict, the LZ4 frame
+ * specification's: the dictionary precedes every block of an independent modern
+ * frame and block 0 of a linked one (LZ4ADA_SEEK_LINKED; the build decodes each
+ * linked frame once against the dictionary, the gap charged to the pass, and
+ * saves the checkpoints as before); legacy blocks read none and decode as in
+ * any index.  No quirk-D1 round state, at the build or in the ranges.  A match
+ * that reaches further back than dict_used bytes before such a block fails its
+ * range with LZ4ADA_DEVFRAME_BLOCK: a short dictionary is never padded.
+ * With LZ4ADA_DICT_CHECK_ID in dict->flags a frame naming another id gets
+ * LZ4ADA_EXACT_PATH / LZ4ADA_DEVFRAME_DICT in the job report, and so does every
+ * later range of it; it holds no block in the index.
+ *
+ * Ranges: everything lz4ada_decode_ranges_device says above holds, with these
+ * additions:
+ *  - the modern blocks of a dictionary index go through the index decoder
+ *    alone, one wave per chain (an independent frame's block is a chain of
+ *    one), since the fallback decoders know no history: a block whose first
+ *    pass declines it -- a block maximum over 256 KiB, or a literal-heavy
+ *    payload of 64 KiB or more -- fails its ranges with LZ4ADA_DEVFRAME_BLOCK.
+ *    The shared block decoder's one caution stands as in section 15: where
+ *    2 KiB of a block's payload decode to more than 4,080 bytes, a match that
+ *    starts before the block with an offset of 65,529 or more fails the range
+ *    the same way;
+ *  - every marked block that reads the dictionary has G bytes in front of its
+ *    slot, charged against LZ4ADA_BATCH_BYTES like a head's 65,792: a range
+ *    whose slots and gaps alone exceed the budget is LZ4ADA_BATCH_OVER_BUDGET
+ *    in place;
+ *  - a delivered range asserts what it did before, decoded against the
+ *    dictionary the index was built with.
+ * Misuse, LZ4ADA_ASSERTION_ERROR before any device call with *idx = NULL: what
+ * lz4ada_seek_index_build_opt rejects, dict_len < 0, d_dict == NULL with
+ * dict_len > 0, unknown bits in dict->flags.
+ */
+int lz4ada_seek_index_build_dict(const void *d_in, int64_t in_len,
+                                 lz4ada_device_frame_job *jobs, int64_t njobs,
+                                 const lz4ada_seek_options *opt,
+                                 const lz4ada_device_dict *dict,
+                                 lz4ada_seek_index **idx, void *stream);
+
 typedef struct {
-	int64_t job;              /* in: which of the njobs frames the index was built over */
+	int64_t job;             /* in: which of the njobs frames the index was built over */
 	int64_t off, len;         /* in: decoded bytes [off, off + len) of that frame */
 	int64_t out_off, out_len; /* out: where its bytes lie in d_out, and how many */
 	int32_t status;           /* out: LZ4ADA_OK, or LZ4ADA_EXACT_PATH: not delivered */
@@ -864,6 +923,32 @@ int lz4ada_range_blocks_host(const uint64_t *start, int64_t nblocks, const int64
 int lz4ada_range_chains_host(int64_t nblocks, int64_t group, const int64_t *first,
                              const int64_t *count, int64_t n, uint8_t *marked, uint8_t *head,
                              int64_t *chain_first, int64_t *chain_count, int64_t *nchains);
+/* The gap count of an interval on the host (lz4ada_range_chains.h, what the
+ * ranged decode charges and lays out): among the blocks [lo, hi) of a frame of
+ * nblocks blocks in groups of `group`, *heads = those decoded from a checkpoint
+ * (65,792 bytes in front of each) and *dict_gaps = those that read the
+ * dictionary of a dictionary index, by the frame's kind (0: none of them -- a
+ * legacy frame, or no dictionary; 1: a linked frame, block 0; 2: an independent
+ * modern frame, every block).  LZ4ADA_ASSERTION_ERROR on a NULL or out-of-range
+ * argument.  Host only, no HIP call. */
+int lz4ada_range_gaps_host(int64_t nblocks, int64_t group, int32_t kind, int64_t lo, int64_t hi,
+                           int64_t *heads, int64_t *dict_gaps);
+/* Like lz4ada_decode_idx_frames_debug: k_index + k_decode_idx_chains alone, the
+ * chain decoder of a ranged pass over a dictionary index.  descs: nblocks
+ * descriptors (host array) laid out as such a pass lays them; chain i holds the
+ * blocks [first[i], first[i] + count[i]) (rising, disjoint) and starts with
+ * hist[i] bytes of history, which the caller has put in front of its first
+ * block's slot in d_out; gapped[i] != 0 marks that block as having such a gap.
+ * d_status (device, zeroed by the caller) gets a code per block of a chain: 0
+ * with out_len, or non-zero from the block that ended the chain on; the blocks
+ * of a chain whose first block is not gapped, or lies less than
+ * round256(min(hist, 65536) + 32) bytes into d_out, get a non-zero code and
+ * nothing of theirs is written.  Returns after the stream has drained. */
+int lz4ada_decode_idx_chains_debug(const void *d_frame, uint64_t frame_len,
+                                   const lz4ada_block_desc *descs, int64_t nblocks,
+                                   const int64_t *first, const int64_t *count, const uint32_t *hist,
+                                   const uint8_t *gapped, int64_t nchains, void *d_out,
+                                   lz4ada_block_status *d_status, void *stream);
 /* One job of an index: its reason (0: accepted), its block count, and, when
  * start is not NULL, its start[0 .. nblocks] copied to the host (start_cap
  * entries of room). */
