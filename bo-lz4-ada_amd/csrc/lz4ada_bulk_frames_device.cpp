@@ -214,16 +214,6 @@ int64_t report_sizes(const FramesIndex& ix, lz4ada_device_frame_job* jobs)
 	return int64_t(total);
 }
 
-namespace {
-
-// The dictionary of a _dict call as the passes see it (null: none, the _opt call).
-struct DictCtx {
-	const uint8_t* d_dict;
-	uint64_t len;
-	uint32_t used;  // min(len, DICT_MAX)
-	uint64_t gap;   // dict_gap(used)
-};
-
 // The blocks of sorted job k that get a gap: every block of an independent
 // modern frame, the first of a linked one.
 uint64_t gapped_blocks(const FramesIndex& ix, size_t k)
@@ -232,8 +222,6 @@ uint64_t gapped_blocks(const FramesIndex& ix, size_t k)
 		return 0;
 	return ix.linked(k) ? 1 : ix.walk[k].nblocks;
 }
-
-}  // namespace
 
 // LZ4ADA_DICT_CHECK_ID: a taken modern frame that names another dictionary id
 // is no longer taken(), with LZ4ADA_DEVFRAME_DICT as its verdict, on the host
@@ -257,28 +245,26 @@ void check_dict_ids(FramesIndex& ix, const uint8_t* d_in, uint32_t dict_id, hipS
 			ix.walk[k].verdict = LZ4ADA_DEVFRAME_DICT;
 }
 
-namespace {
-
 // A dictionary pass over the sorted jobs [lo, hi), once its descriptors are
-// filled: the gaps (k_frames_dictgap from a word per frame), their bytes
-// (k_dict_fill), and the runs cut again so that legacy frames, which read no
-// dictionary, keep launch_decode_checked while modern ones take the dictionary
-// decoders.  `total`: the pass's slots and gaps, what SC_OUT holds.
+// filled: the gaps (k_frames_dictgap from a word per frame, written to the
+// pinned h_kind and sent up from there), their bytes (k_dict_fill), and the
+// runs cut again so that legacy frames, which read no dictionary, keep
+// launch_decode_checked while modern ones take the dictionary decoders.
+// `total`: the pass's slots and gaps, what SC_OUT holds.
 void lay_dict_pass(PassArrays& m, const FramesIndex& ix, size_t lo, size_t hi, uint64_t total, uint64_t in_len,
-                   const DictCtx& dc, PinBuf& h, hipStream_t stream)
+                   const DictCtx& dc, uint64_t* h_kind, hipStream_t stream)
 {
 	const size_t kind_b = size_t(m.nf) * 8;
 	uint64_t* const d_kind = reinterpret_cast<uint64_t*>(scratch(SC_DICT, kind_b));
 	if (!d_kind)
 		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the pass's gaps");
-	uint64_t* const kind = reinterpret_cast<uint64_t*>(h.p);
 	uint64_t before = 0;
 	for (size_t k = lo; k < hi; ++k) {
 		const uint64_t g = gapped_blocks(ix, k);
-		kind[k - lo] = (before << 2) | (g == 0 ? DICT_KIND_NONE : ix.linked(k) ? DICT_KIND_LINKED : DICT_KIND_INDEP);
+		h_kind[k - lo] = (before << 2) | (g == 0 ? DICT_KIND_NONE : ix.linked(k) ? DICT_KIND_LINKED : DICT_KIND_INDEP);
 		before += g;
 	}
-	HIP_OK(hipMemcpyAsync(d_kind, kind, kind_b, hipMemcpyHostToDevice, stream));
+	HIP_OK(hipMemcpyAsync(d_kind, h_kind, kind_b, hipMemcpyHostToDevice, stream));
 	HIP_OK(launch_frames_dictgap(m.d_rec, m.nf, d_kind, dc.gap, total, m.d_desc, m.nb, stream));
 	HIP_OK(launch_dict_fill(m.d_desc, m.nb, dc.d_dict, dc.len, dc.used, m.d_slots, stream));
 	// the runs: a linked run takes the dictionary as it is; an independent one
@@ -337,6 +323,8 @@ void fill_pass(const FramesIndex& ix, size_t lo, size_t hi, const uint8_t* d_in,
 		                           m.d_desc, stream));
 }
 
+namespace {
+
 void job_rejected(lz4ada_device_frame_job& j, int reason)
 {
 	j.out_off = j.out_len = j.consumed = 0;
@@ -367,7 +355,7 @@ void run_device_pass(const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots
 	PinBuf& h = scratch_cache().pin;  // this thread's small pinned transfers
 	h.reserve(std::max(m.rec_b, dc ? size_t(m.nf) * 8 : size_t(0)));
 	if (dc)
-		lay_dict_pass(m, ix, lo, hi, slots, in_len, *dc, h, stream);
+		lay_dict_pass(m, ix, lo, hi, slots, in_len, *dc, reinterpret_cast<uint64_t*>(h.p), stream);
 	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p);
 	decode_pass(m, d_in, in_len, dst, hash_max, rec, stream);
 	lz4ada_batch_stats& stats = batch_stats();
@@ -467,23 +455,19 @@ int decode_frames_device(const char* entry, const void* d_in, int64_t in_len, lz
 		size_t lo = 0;
 		while (lo < n) {
 			// the sorted jobs [lo, hi): as many frames as the budget takes
-			size_t hi = lo;
-			uint64_t acc = 0, nb = 0, real = 0;
-			for (; hi < n; ++hi) {
-				if (!ix.taken(hi))
-					continue;
-				// (a dictionary pass's gaps are scratch like its slots)
-				const uint64_t cost = ix.slots(hi) + (dc ? dc->gap * gapped_blocks(ix, hi) : 0);
-				if ((acc && acc + cost > budget) || nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
-					break;
-				acc += cost;
-				nb += ix.walk[hi].nblocks;
-				real += ix.skippable(hi) ? 0 : 1;
-			}
+			// (a dictionary pass's gaps are scratch like its slots)
+			const PassCut cut = pass_cut(lo, n, budget, [&](size_t k) {
+				return PassCost{ ix.taken(k), ix.slots(k) + (dc ? dc->gap * gapped_blocks(ix, k) : 0),
+					         ix.walk[k].nblocks };
+			});
+			const size_t hi = cut.hi;
 			if (hi == lo)  // one frame of 2^31 blocks or more
 				raise(LZ4ADA_CONSTRAINT_ERROR, "a frame holds more blocks than a pass takes");
+			bool real = false;  // a frame that is taken and not skippable
+			for (size_t k = lo; k < hi; ++k)
+				real |= ix.taken(k) && !ix.skippable(k);
 			if (real) {
-				run_device_pass(ix, lo, hi, acc, static_cast<const uint8_t*>(d_in), uint64_t(in_len), jobs,
+				run_device_pass(ix, lo, hi, cut.bytes, static_cast<const uint8_t*>(d_in), uint64_t(in_len), jobs,
 				                static_cast<uint8_t*>(d_out), &base, hash_max, s, dc);
 			} else {  // nothing but skippable frames, if any: no launch
 				for (size_t k = lo; k < hi; ++k)

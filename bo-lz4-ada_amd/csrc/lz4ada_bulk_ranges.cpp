@@ -17,8 +17,9 @@
 //
 // With LZ4ADA_SEEK_LINKED (lz4ada_seek_index_build_opt) the
 // index takes linked frames: the build decodes each once with the linked run
-// of §12 (decode_linked_frames) and keeps the 64 KiB in front of every K-th
-// block in a store of its own (k_ckpt_save).  A range of a linked frame marks
+// of §12 (decode_linked_frames: the device engine's own pass stages and
+// decode_pass_blocks over a view of the index) and keeps the
+// 64 KiB in front of every K-th block in a store of its own (k_ckpt_save).  A range of a linked frame marks
 // its chain (lz4ada_range_chains.h): the pass lays a gap in front of every
 // head, fills it with the head's checkpoint (k_ckpt_fill) and decodes the
 // chains with the dictionary decoder of §15, one wave per chain, beside the
@@ -40,23 +41,50 @@
 
 using namespace lz4ada;
 
+namespace lz4ada {
+
+// One hipMalloc'd block, freed with its owner.
+struct DevMem {
+	uint8_t* p = nullptr;
+	size_t bytes = 0;
+	DevMem() = default;
+	DevMem(const DevMem&) = delete;
+	DevMem& operator=(const DevMem&) = delete;
+	~DevMem()
+	{
+		if (p)
+			(void)hipFree(p);
+	}
+	// `what`: whose memory, for the text when the device has none
+	uint8_t* alloc(size_t n, const char* what)
+	{
+		void* q = nullptr;
+		if (hipMalloc(&q, n) != hipSuccess) {
+			(void)hipGetLastError();
+			raise(LZ4ADA_DEVICE_ERROR, std::string("no device memory for ") + what);
+		}
+		p = static_cast<uint8_t*>(q);
+		bytes = n;
+		return p;
+	}
+};
+
+}  // namespace lz4ada
+
 struct lz4ada_seek_index {
 	int64_t in_len = 0;  // the input it was built over
-	void* d_mem = nullptr;
-	size_t bytes = 0;  // desc | first | start | slotp
+	DevMem mem;          // desc | first | start | slotp | with a dictionary: fkind
 	// LZ4ADA_SEEK_LINKED: store | ckfirst | kgrp, and by sorted position what the
 	// last two hold (kgrp: n entries, K or 0; ckfirst: n + 1)
-	void* d_ck = nullptr;
-	size_t ck_bytes = 0;
+	DevMem ck;
 	std::vector<uint64_t> kgrp, ckfirst;
 	bool linked = false;  // it holds a linked frame
-	// a dictionary index: the gap image (dict_gap bytes: zeros, then the last
-	// dict_used bytes of the dictionary), and by sorted position the frame's
-	// CHAIN_KIND_* (empty without a dictionary: every frame CHAIN_KIND_NONE)
-	void* d_dict = nullptr;
-	size_t dict_bytes = 0;
-	uint32_t dict_used = 0;
-	uint64_t dict_gap = 0;
+	// a dictionary index: the gap image (dict.gap bytes: zeros, then the last
+	// dict.used bytes of the dictionary) as the passes' dictionary, and by sorted
+	// position the frame's CHAIN_KIND_* (empty without a dictionary: every frame
+	// CHAIN_KIND_NONE); all zero without one
+	DevMem dict_mem;
+	DictCtx dict{};
 	std::vector<uint8_t> kind;
 	SeekView view{};
 	uint64_t* d_start = nullptr;
@@ -81,10 +109,6 @@ namespace {
 // A choice, not a measurement taken beforehand (DESIGN.md §16 has the table): the
 // store is then at most 1/16 of the decoded size for any block maximum up to 1 MiB.
 constexpr uint64_t SEEK_CHECKPOINT_BYTES = uint64_t(1) << 20;
-
-struct IndexDeleter {
-	void operator()(lz4ada_seek_index* x) const { lz4ada_seek_index_free(x); }
-};
 
 void check_ranges(const char* entry, const lz4ada_seek_index* idx, const lz4ada_frame_range* ranges,
                   int64_t nranges)
@@ -188,7 +212,7 @@ uint32_t frame_kind(const lz4ada_seek_index& x, uint32_t f) { return x.kind.empt
 // the gaps in front of the blocks [lo, hi) of frame f: its heads' and the dictionary's
 uint64_t gap_bytes(const lz4ada_seek_index& x, uint32_t f, uint64_t lo, uint64_t hi)
 {
-	return CKPT_GAP * chain_heads(frame_k(x, f), lo, hi) + x.dict_gap * chain_dict_gaps(frame_kind(x, f), lo, hi);
+	return CKPT_GAP * chain_heads(frame_k(x, f), lo, hi) + x.dict.gap * chain_dict_gaps(frame_kind(x, f), lo, hi);
 }
 // what a range's own chain takes of the budget: its blocks' slots and their gaps
 uint64_t range_need(const lz4ada_seek_index& x, const Selection& s, size_t k)
@@ -274,7 +298,7 @@ struct RangePass {
 		HIP_OK(hipMemsetAsync(d_mark, 0, std::max<size_t>(mark_b, 4), stream));
 		HIP_OK(launch_ranges_select(x.view, s.d_rec + lo, uint32_t(hi - lo), nullptr, d_mark, p.span_lo, p.span_n,
 		                            stream));
-		HIP_OK(launch_ranges_scan(d_mark, p.span_n, x.linked ? CKPT_GAP : 0, x.dict_gap, d_cnt, d_slot, stream));
+		HIP_OK(launch_ranges_scan(d_mark, p.span_n, x.linked ? CKPT_GAP : 0, x.dict.gap, d_cnt, d_slot, stream));
 	}
 };
 
@@ -323,7 +347,7 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 		b0 += n;
 	}
 	if (p.chains) {
-		if (x.dict_used)
+		if (x.dict.used)
 			HIP_OK(launch_decode_idx_chains(d_in, in_len, m.d_desc, p.nsel, m.d_tab, m.d_slots, m.d_st, m.d_chain,
 			                                uint32_t(chain_slots(p.nsel)), stream));
 		else
@@ -360,111 +384,79 @@ void run_range_pass(const lz4ada_seek_index& x, Selection& s, size_t lo, size_t 
 // with the linked run of a many-frame pass (pass 1, one wave per
 // frame with quirk D1's round state, the block checksums beside them), in
 // passes under the byte budget, and the checkpoints of each pass saved from its
-// slots.  The passes see walk records in which only those frames are accepted
-// (SC_DICT: nominal | tight), so an independent frame takes no block and no
-// slot.  A frame whose chain fails is no longer taken(), on the host and on the
-// device, with LZ4ADA_DEVFRAME_BLOCK (_SIZE) as its verdict.  One host
-// synchronisation per pass: the frame records.  In a dictionary index every
-// frame's first block gets the dictionary's gap (k_frames_dictgap with
-// DICT_KIND_LINKED, k_dict_fill from the index's image), charged to the pass,
-// and the frames decode against it with the LZ4 specification's semantics
-// (launch_decode_idx_frames_dict: no quirk-D1 round state).
+// slots.  The passes are the device engine's stages over a view of the index
+// in which only those frames are taken (its walk records in SC_SEEK: nominal |
+// tight), so an independent frame takes no block and no slot and every pass is
+// one linked run.  A frame whose chain fails is no longer taken(), on the host
+// and on the device, with LZ4ADA_DEVFRAME_BLOCK (_SIZE) as its verdict.  One
+// host synchronisation per pass: the frame records.  In a dictionary index
+// every frame's first block gets the dictionary's gap from the index's image,
+// charged to the pass, and the frames decode against it with the LZ4
+// specification's semantics (no quirk-D1 round state).
 void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* d_store, uint64_t* d_ckfirst,
                           uint64_t* d_kgrp, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
 {
 	const size_t n = ix.order.size(), walk_b = n * sizeof(FrameWalkRec);
 	const size_t ckf_b = (n + 1) * 8, kg_b = n * 8;
-	auto mine = [&](size_t k) { return ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0; };
-	const bool dict = x.dict_used != 0;
-	const size_t kind_b = dict ? n * 8 : 0;  // SC_DICT: nominal | tight | a dictionary pass's kind words
-	FrameWalkRec* const d_nom = reinterpret_cast<FrameWalkRec*>(scratch(SC_DICT, 2 * walk_b + kind_b));
-	if (!d_nom)
+	const bool dict = x.dict.used != 0;
+	FramesIndex v = ix;  // the view: any other frame rides along
+	bool any = false;
+	for (size_t k = 0; k < n; ++k) {
+		if (ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0)
+			any = true;
+		else if (ix.taken(k))
+			v.walk[k].verdict = LZ4ADA_BATCH_LINKED;
+	}
+	v.d_walk = reinterpret_cast<FrameWalkRec*>(scratch(SC_SEEK, 2 * walk_b));
+	if (!v.d_walk)
 		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the linked frames' records");
-	FrameWalkRec* const d_tight = d_nom + n;
-	uint64_t* const d_kind = reinterpret_cast<uint64_t*>(d_tight + n);
+	v.d_tight = v.d_walk + n;
 	// pinned: the index's per-frame words and the records going up, and behind
-	// them room for a pass's frame records coming down, so that nothing is
-	// written while a copy may read it
+	// them room for a pass's frame records coming down and a dictionary pass's
+	// kind words going up (a frame's word is written in its one pass), so that
+	// nothing is written while a copy may read it
 	PinBuf& h = scratch_cache().pin;
-	h.reserve(ckf_b + kg_b + 2 * walk_b + n * sizeof(FrameRec) + kind_b);
+	h.reserve(ckf_b + kg_b + 2 * walk_b + n * sizeof(FrameRec) + (dict ? n * 8 : 0));
 	memcpy(h.p, x.ckfirst.data(), ckf_b);
 	memcpy(h.p + ckf_b, x.kgrp.data(), kg_b);
 	HIP_OK(hipMemcpyAsync(d_ckfirst, h.p, ckf_b + kg_b, hipMemcpyHostToDevice, stream));  // (kgrp follows ckfirst)
-	FrameWalkRec* const w = reinterpret_cast<FrameWalkRec*>(h.p + ckf_b + kg_b);
-	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p + ckf_b + kg_b + 2 * walk_b);
-	uint64_t* const kind = reinterpret_cast<uint64_t*>(rec + n);  // (a frame's word is written in its one pass)
-	bool any = false;
-	for (size_t k = 0; k < n; ++k) {
-		w[k] = ix.walk[k];
-		if (!mine(k))
-			w[k].verdict = w[k].verdict == LZ4ADA_BATCH_OK ? LZ4ADA_BATCH_LINKED : w[k].verdict;  // rides along
-		w[n + k] = w[k];
-		w[n + k].slots = ix.size[k].tight;
-		any |= mine(k);
-	}
 	if (!any)
 		return;
-	HIP_OK(hipMemcpyAsync(d_nom, w, 2 * walk_b, hipMemcpyHostToDevice, stream));
+	FrameWalkRec* const w = reinterpret_cast<FrameWalkRec*>(h.p + ckf_b + kg_b);
+	FrameRec* const rec = reinterpret_cast<FrameRec*>(h.p + ckf_b + kg_b + 2 * walk_b);
+	uint64_t* const kind = reinterpret_cast<uint64_t*>(rec + n);
+	for (size_t k = 0; k < n; ++k) {
+		w[k] = w[n + k] = v.walk[k];
+		w[n + k].slots = ix.size[k].tight;
+	}
+	HIP_OK(hipMemcpyAsync(v.d_walk, w, 2 * walk_b, hipMemcpyHostToDevice, stream));
 	const uint64_t budget = uint64_t(batch_budget());
 	bool failed = false;
 	for (size_t lo = 0; lo < n;) {
-		size_t hi = lo;
-		uint64_t acc = 0, nb = 0;
-		for (; hi < n; ++hi) {
-			if (!mine(hi))
-				continue;
-			const uint64_t cost = ix.size[hi].tight + x.dict_gap;  // (the gap is scratch like its slots)
-			if ((acc && acc + cost > budget) || nb + ix.walk[hi].nblocks >= (uint64_t(1) << 31))
-				break;
-			acc += cost;
-			nb += ix.walk[hi].nblocks;
-		}
-		if (nb == 0) {
+		// (the gap is scratch like its slots)
+		const PassCut cut = pass_cut(lo, n, budget, [&](size_t k) {
+			return PassCost{ v.taken(k), ix.size[k].tight + x.dict.gap, ix.walk[k].nblocks };
+		});
+		const size_t hi = cut.hi;
+		if (cut.blocks == 0) {  // nothing of the view's, or one frame of 2^31 blocks or more: skipped
 			lo = std::max(hi, lo + 1);
 			continue;
 		}
-		std::vector<PassFrame> frames;
-		for (size_t k = lo; k < hi; ++k)
-			frames.push_back(PassFrame{ mine(k) ? uint32_t(ix.walk[k].nblocks) : 0u, true });
 		PassArrays m;
-		if (const char* what = m.reserve(frames, acc, in_len))
-			raise(LZ4ADA_DEVICE_ERROR, std::string("no device memory for the build pass's ") + what);
-		const uint32_t nf = m.nf;
-		HIP_OK(launch_frames_scan(d_tight + lo, nf, ix.d_first, ix.d_slot, stream));
-		HIP_OK(launch_frames_fill(d_in, ix.d_span + lo, d_nom + lo, ix.d_first, ix.d_slot, nf, lone_blocks_disabled(),
-		                          true, ix.linked_max, m.d_desc, m.d_rec, stream));
-		HIP_OK(launch_frames_refit(d_tight + lo, ix.d_first, ix.d_slot, ix.d_size_first + lo, ix.d_size, nf, m.d_desc,
-		                           stream));
-		if (dict) {
-			uint64_t before = 0;
-			for (size_t k = lo; k < hi; ++k) {
-				kind[k] = (before << 2) | (mine(k) ? DICT_KIND_LINKED : DICT_KIND_NONE);
-				before += mine(k) ? 1 : 0;
-			}
-			HIP_OK(hipMemcpyAsync(d_kind + lo, kind + lo, (hi - lo) * 8, hipMemcpyHostToDevice, stream));
-			HIP_OK(launch_frames_dictgap(m.d_rec, nf, d_kind + lo, x.dict_gap, acc, m.d_desc, m.nb, stream));
-			HIP_OK(launch_dict_fill(m.d_desc, m.nb, static_cast<const uint8_t*>(x.d_dict), x.dict_gap, x.dict_used,
-			                        m.d_slots, stream));
-		}
-		HIP_OK(hipMemsetAsync(m.d_st, 0, m.st_b, stream));
-		HIP_OK(launch_block_checksums_beside(d_in, m.d_desc, m.nb, m.d_st, stream));
-		HIP_OK(launch_index(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_st, stream));
+		reserve_pass(m, v, lo, hi, cut.bytes, in_len);
+		fill_pass(v, lo, hi, d_in, m, stream);
 		if (dict)
-			HIP_OK(launch_decode_idx_frames_dict(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_slots, m.d_st, m.d_rec, nf,
-			                                     x.dict_used, stream));
-		else
-			HIP_OK(launch_decode_idx_frames(d_in, in_len, m.d_desc, m.nb, m.d_tab, m.d_slots, m.d_st, m.d_rec, nf,
-			                                stream));
-		HIP_OK(join_block_checksums(stream));
-		HIP_OK(launch_frames_plan(m.d_desc, m.d_st, m.nb, m.d_rec, nf, m.d_off, m.d_loc, m.d_part, stream));
-		HIP_OK(launch_ckpt_save(d_kgrp, d_ckfirst, uint32_t(lo), nf, x.ckfirst[lo], uint32_t(x.ckfirst[hi] - x.ckfirst[lo]),
-		                        x.ckfirst[n], m.d_desc, m.nb, m.d_rec, m.d_slots, acc, d_store, stream));
+			lay_dict_pass(m, v, lo, hi, cut.bytes, in_len, x.dict, kind + lo, stream);
+		decode_pass_blocks(m, d_in, in_len, stream);
+		HIP_OK(launch_ckpt_save(d_kgrp, d_ckfirst, uint32_t(lo), m.nf, x.ckfirst[lo],
+		                        uint32_t(x.ckfirst[hi] - x.ckfirst[lo]), x.ckfirst[n], m.d_desc, m.nb, m.d_rec,
+		                        m.d_slots, cut.bytes, d_store, stream));
 		// the pass's host synchronisation: the frame records
 		HIP_OK(hipMemcpyAsync(rec, m.d_rec, m.rec_b, hipMemcpyDeviceToHost, stream));
 		HIP_OK(hipStreamSynchronize(stream));
 		++batch_stats().passes;
 		for (size_t k = lo; k < hi; ++k) {
-			if (!mine(k))
+			if (!v.taken(k))
 				continue;
 			const FrameRec& r = rec[k - lo];
 			if (r.fail >= 0 || (r.verdict & FRAME_SIZE_BAD)) {
@@ -491,28 +483,22 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 	if (dict && (dict->flags & LZ4ADA_DICT_CHECK_ID))
 		check_dict_ids(ix, static_cast<const uint8_t*>(d_in), dict->dict_id, s);
 	size_jobs(ix, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
-	std::unique_ptr<lz4ada_seek_index, IndexDeleter> x(new lz4ada_seek_index);
+	std::unique_ptr<lz4ada_seek_index> x(new lz4ada_seek_index);
 	const size_t n = ix.order.size();
 	x->in_len = in_len;
 	if (dict && n) {
 		// the index's own dictionary, as the gap every pass copies: zeros, then
-		// its last dict_used bytes (an allocation: 256-aligned)
-		x->dict_used = uint32_t(std::min<uint64_t>(uint64_t(dict->dict_len), DICT_MAX));
-		x->dict_gap = dict_gap(x->dict_used);
-		x->dict_bytes = size_t(x->dict_gap);
-		if (hipMalloc(&x->d_dict, x->dict_bytes) != hipSuccess) {
-			(void)hipGetLastError();
-			x->d_dict = nullptr;
-			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index's dictionary");
-		}
-		uint8_t* const img = static_cast<uint8_t*>(x->d_dict);
-		const size_t zeros = size_t(x->dict_gap) - x->dict_used;
+		// its last `used` bytes (an allocation: 256-aligned)
+		const uint32_t used = uint32_t(std::min<uint64_t>(uint64_t(dict->dict_len), DICT_MAX));
+		const uint64_t gap = dict_gap(used);
+		uint8_t* const img = x->dict_mem.alloc(size_t(gap), "the seek index's dictionary");
+		x->dict = DictCtx{ img, gap, used, gap };
+		const size_t zeros = size_t(gap) - used;
 		HIP_OK(hipMemsetAsync(img, 0, zeros, s));
-		HIP_OK(hipMemcpyAsync(img + zeros,
-		                      static_cast<const uint8_t*>(dict->d_dict) + (uint64_t(dict->dict_len) - x->dict_used),
-		                      x->dict_used, hipMemcpyDeviceToDevice, s));
+		HIP_OK(hipMemcpyAsync(img + zeros, static_cast<const uint8_t*>(dict->d_dict) + (uint64_t(dict->dict_len) - used),
+		                      used, hipMemcpyDeviceToDevice, s));
 		x->view.dict = img;
-		x->view.dict_used = x->dict_used;
+		x->view.dict_used = used;
 	}
 	if (linked && n) {
 		// the checkpoints of every linked frame the sizes stage accepted, and the
@@ -527,13 +513,7 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 		}
 		const uint64_t nck = x->ckfirst[n];
 		const size_t store_b = size_t(nck) * CKPT_BYTES, ckf_b = (n + 1) * 8, kg_b = n * 8;
-		x->ck_bytes = store_b + ckf_b + kg_b;
-		if (hipMalloc(&x->d_ck, x->ck_bytes) != hipSuccess) {
-			(void)hipGetLastError();
-			x->d_ck = nullptr;
-			raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index's checkpoints");
-		}
-		uint8_t* const c = static_cast<uint8_t*>(x->d_ck);
+		uint8_t* const c = x->ck.alloc(store_b + ckf_b + kg_b, "the seek index's checkpoints");
 		uint64_t* const d_ckfirst = reinterpret_cast<uint64_t*>(c + store_b);
 		uint64_t* const d_kgrp = d_ckfirst + n + 1;
 		// (which also sends the two arrays up, from pinned memory with its records)
@@ -569,14 +549,8 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 	// 24 per frame (first, and the prefixes' end entries), and with a dictionary
 	// 8 more per frame: its kind
 	const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), first_b = (n + 1) * 8,
-	             pre_b = (size_t(nb) + n) * 8, kind_b = x->dict_used ? n * 8 : 0;
-	x->bytes = desc_b + first_b + 2 * pre_b + kind_b;
-	if (hipMalloc(&x->d_mem, x->bytes) != hipSuccess) {
-		(void)hipGetLastError();
-		x->d_mem = nullptr;
-		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the seek index");
-	}
-	uint8_t* const m = static_cast<uint8_t*>(x->d_mem);
+	             pre_b = (size_t(nb) + n) * 8, kind_b = x->dict.used ? n * 8 : 0;
+	uint8_t* const m = x->mem.alloc(desc_b + first_b + 2 * pre_b + kind_b, "the seek index");
 	lz4ada_block_desc* const d_desc = reinterpret_cast<lz4ada_block_desc*>(m);
 	uint64_t* const d_first = reinterpret_cast<uint64_t*>(m + desc_b);
 	x->d_start = reinterpret_cast<uint64_t*>(m + desc_b + first_b);
@@ -586,7 +560,7 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 	x->view.start = x->d_start;
 	x->view.slotp = d_slotp;
 	x->view.nframes = uint32_t(n);
-	if (x->dict_used) {
+	if (x->dict.used) {
 		// which blocks read the dictionary, by the final verdicts: every block of
 		// an independent modern frame, block 0 of a linked one, none of a legacy one
 		uint64_t* const d_kind = reinterpret_cast<uint64_t*>(m + desc_b + first_b + 2 * pre_b);
@@ -691,20 +665,12 @@ int lz4ada_seek_index_build_dict(const void* d_in, int64_t in_len, lz4ada_device
 
 void lz4ada_seek_index_free(lz4ada_seek_index* idx)
 {
-	if (!idx)
-		return;
-	if (idx->d_mem)
-		(void)hipFree(idx->d_mem);
-	if (idx->d_ck)
-		(void)hipFree(idx->d_ck);
-	if (idx->d_dict)
-		(void)hipFree(idx->d_dict);
-	delete idx;
+	delete idx;  // (its device memory with it)
 }
 
 int64_t lz4ada_seek_index_bytes(const lz4ada_seek_index* idx)
 {
-	return idx ? int64_t(idx->bytes + idx->ck_bytes + idx->dict_bytes) : 0;
+	return idx ? int64_t(idx->mem.bytes + idx->ck.bytes + idx->dict_mem.bytes) : 0;
 }
 
 int lz4ada_decode_ranges_device(const lz4ada_seek_index* idx, const void* d_in, int64_t in_len,

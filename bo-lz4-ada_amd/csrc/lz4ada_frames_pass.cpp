@@ -1,7 +1,8 @@
-// lz4ada_frames_pass.cpp -- what the two many-frame engines do on the device,
-// stated once (declared in lz4ada_host_common.h): a pass's
-// arrays, the decode launches of its runs, the device half of the pass up to
-// its one synchronisation, a frame's verdict, the tuning values and counters.
+// lz4ada_frames_pass.cpp -- what the two many-frame engines and the seek
+// index's linked build do on the device, stated once (DESIGN.md §10-§12, §20;
+// declared in lz4ada_host_common.h): a pass's arrays, the decode launches of
+// its runs, the device half of the pass up to its one synchronisation (the
+// build's up to k_frames_plan), a frame's verdict, the tuning values and counters.
 #include "lz4ada_host_common.h"
 
 namespace lz4ada {
@@ -90,14 +91,19 @@ const char* PassArrays::reserve(const std::vector<PassFrame>& frames, uint64_t s
 	return any_linked && !d_tab ? "sequence index" : nullptr;
 }
 
-void decode_pass(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, uint8_t* dst, uint64_t hash_max,
-                 FrameRec* h_rec, hipStream_t stream)
+void decode_pass_blocks(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, hipStream_t stream)
 {
 	if (a.nb)
 		HIP_OK(hipMemsetAsync(a.d_st, 0, a.st_b, stream));
 	for (const PassRun& run : a.runs)
 		decode_pass_run(a, d_in, in_len, run, stream);
 	HIP_OK(launch_frames_plan(a.d_desc, a.d_st, a.nb, a.d_rec, a.nf, a.d_off, a.d_loc, a.d_part, stream));
+}
+
+void decode_pass(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, uint8_t* dst, uint64_t hash_max,
+                 FrameRec* h_rec, hipStream_t stream)
+{
+	decode_pass_blocks(a, d_in, in_len, stream);
 	HIP_OK(launch_compact(a.d_slots, a.d_desc, a.d_off, a.d_st, a.nb, dst, stream));
 	HIP_OK(launch_xxh32_spans(dst, a.d_rec, a.nf, hash_max, stream));
 	// the pass's one host synchronisation: the per-frame records

@@ -393,8 +393,10 @@ inline bool try_reserve(DevBuf<T>& b, size_t count)
 // SC_SIZES: what the sizes stage of a device call leaves for its passes
 // (lz4ada_bulk_frames_device.cpp).
 // SC_DICT: a dictionary call's small per-frame words.
+// SC_SEEK: the walk records a seek index's linked build keeps beside the
+// index's own for all its passes (lz4ada_bulk_ranges.cpp).
 enum ScratchRole { SC_FRAME, SC_OUT, SC_COMPACT, SC_X, SC_Y, SC_H, SC_Z, SC_TAB, SC_P, SC_F, SC_LONE, SC_U,
-	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_SIZES, SC_DICT, SC_N };
+	           SC_LINK, SC_M, SC_BATCH, SC_BATCH_META, SC_SIZES, SC_DICT, SC_SEEK, SC_N };
 struct ScratchCache {
 	DevBuf<uint8_t> b[SC_N];
 	PinBuf pin;  // the linked path's small host transfers (pinned: no staging copy)
@@ -480,14 +482,17 @@ struct PassArrays {
 	uint32_t dict_used = 0;     // a dictionary pass: the history of a BLOCK_DICT block (runs with .dict)
 	const char* reserve(const std::vector<PassFrame>& frames, uint64_t slots, uint64_t in_len);
 };
-// The device half of a pass, once a.d_desc and a.d_rec are queued on stream:
-// the status memset, each run's decode launches, k_frames_plan, k_compact into
-// dst, k_xxh32_spans, the frame records into the pinned h_rec, the pass's one
-// synchronisation, ++passes.  in_off must rise strictly over the whole pass
-// (frame order, block order) and in_len cover every block: the index decoder's
-// table keeps block b's records at ((in_off >> 8) + b) and is sized from in_len
-// (index_table_bytes), or two blocks' records would overlap or leave the table.
-// A linked run indexes into d_tab + b0 * 64, as one launch_index over the pass.
+// The device half of a pass, once a.d_desc and a.d_rec are queued on stream.
+// decode_pass_blocks: the status memset, each run's decode launches and
+// k_frames_plan (where the seek index's linked build goes its own way).
+// decode_pass: that, k_compact into dst, k_xxh32_spans, the frame records into
+// the pinned h_rec, the pass's one synchronisation, ++passes.  in_off must rise
+// strictly over the whole pass (frame order, block order) and in_len cover every
+// block: the index decoder's table keeps block b's records at ((in_off >> 8) + b)
+// and is sized from in_len (index_table_bytes), or two blocks' records would
+// overlap or leave the table.  A linked run indexes into d_tab + b0 * 64, as one
+// launch_index over the pass.
+void decode_pass_blocks(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, hipStream_t stream);
 void decode_pass(const PassArrays& a, const uint8_t* d_in, uint64_t in_len, uint8_t* dst, uint64_t hash_max,
                  FrameRec* h_rec, hipStream_t stream);
 // A frame's record after the pass, against its declared content checksum: the
@@ -545,6 +550,27 @@ int64_t report_sizes(const FramesIndex& ix, lz4ada_device_frame_job* jobs);
 // host synchronisation.
 void check_dict(const char* entry, const lz4ada_device_dict* dict);
 void check_dict_ids(FramesIndex& ix, const uint8_t* d_in, uint32_t dict_id, hipStream_t stream);
+// The dictionary as the passes see it: k_dict_fill copies the last `used` of
+// its `len` bytes (a _dict call's dictionary, or a seek index's gap image).
+struct DictCtx {
+	const uint8_t* d_dict;
+	uint64_t len;
+	uint32_t used;  // min(the dictionary's length, DICT_MAX)
+	uint64_t gap;   // dict_gap(used)
+};
+// A pass over the sorted jobs [lo, hi) up to its decode (bodies and comments in
+// lz4ada_bulk_frames_device.cpp), for the device engine and for the seek
+// index's linked build, which passes a view of its index in which only the
+// linked frames are taken.  reserve_pass: the arrays (`slots`: slot bytes, gaps
+// included).  fill_pass: descriptors and frame records.  lay_dict_pass: a
+// dictionary's gaps (gapped_blocks of each job) and the runs cut for its
+// decoders; h_kind: pinned room for hi - lo words no queued copy may still read.
+uint64_t gapped_blocks(const FramesIndex& ix, size_t k);
+void reserve_pass(PassArrays& a, const FramesIndex& ix, size_t lo, size_t hi, uint64_t slots, uint64_t in_len);
+void fill_pass(const FramesIndex& ix, size_t lo, size_t hi, const uint8_t* d_in, const PassArrays& m,
+               hipStream_t stream);
+void lay_dict_pass(PassArrays& m, const FramesIndex& ix, size_t lo, size_t hi, uint64_t total, uint64_t in_len,
+                   const DictCtx& dc, uint64_t* h_kind, hipStream_t stream);
 
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.

@@ -25,9 +25,11 @@
 //    (a leader loop: the first pending item always runs, every other whose
 //    source is already final runs with it).
 //
-//  * k_decode_idx_frames (pass 2 of the linked frames of a many-frame pass,
-//    one wave per frame): the frame's blocks in order, each reading the
-//    earlier output as history.
+//  * k_decode_idx_frames, k_decode_idx_frames_dict, k_decode_idx_chains (pass 2
+//    of linked blocks, one wave per chain): the chain's blocks in order, each
+//    reading the earlier output as history.  The walk is stated once, in
+//    decode_chain; the kernels differ in where the history starts (DESIGN.md
+//    §12, §15, §19, §20).
 //
 // Blocks either pass declines (DS_RETRY: malformed data, a back-reference
 // before the block start, an oversize block) are redone by k_decode_pc,
@@ -2638,46 +2640,41 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	decode_block(D, frame, frame_len, desc, blockIdx.x, tab_all, out, status, LINK_HIST, len, false, true);
 }
 
-// Many linked frames side by side (a many-frame pass, DESIGN.md §12): one wave
-// per frame of the pass.  Workgroup f takes the blocks [first, first + nblocks)
-// of frames[f] when the record carries FRAME_LINKED (any other frame is
-// another launch's) and runs pass 2 over them in order, as K_SERIAL does for
-// one frame: each block reads the earlier output as history while every block
-// so far is full and its slot continues the previous one; from the first
-// block that is declined, short or not contiguous on, the later blocks of the
-// frame get DS_RETRY and the ones before keep DS_OK.  Pass 1 is an ordinary
-// launch_index over the same descriptors, ahead of this kernel.
+// One chain of linked blocks [first, bend), walked by one wave: pass 2 over
+// them in order, as K_SERIAL does for one frame.  Each block reads `hist` bytes
+// in front of its slot as history: what the caller starts with (nothing, a
+// dictionary's tail, a checkpoint) and the earlier blocks' output, while every
+// block so far is full and its slot continues the previous one.  The walk ends
+// before `stop` (the caller passes bend, or first when it refuses the chain's
+// layout) and at the first block that is declined, short or not followed by a
+// contiguous slot; the blocks before that one keep DS_OK, its own status is
+// pass 2's, and every later block of the chain gets DS_RETRY.  Pass 1 is an
+// ordinary launch_index over the same descriptors, ahead of the kernel.  The
+// caller clamps [first, bend) to the launch's blocks, so no status and no slot
+// outside the chain is written whatever its record says.
 //
-// Quirk D1 from the real round state: the wave knows every decoded length, so
-// it replays Output_Pos / Output_Pos_History as the host does for one linked
-// frame (lz4ada_bulk_linked.cpp: opos = 0 when >= 65536 at a block's start,
-// opos += len, oph = opos when >= 65536).  A block that pass 2 flagged
+// D1: quirk D1 from the real round state.  The wave knows every decoded
+// length, so it replays Output_Pos / Output_Pos_History as the host does for one
+// linked frame (lz4ada_bulk_linked.cpp: opos = 0 when >= 65536 at a block's
+// start, opos += len, oph = opos when >= 65536).  A block that pass 2 flagged
 // AUX_D1_RISK while oph is in [65536, 65542] gets DS_RETRY and ends the chain
 // (nothing is emulated here: D1E stays false); outside that state the flagged
-// match reads plain history.
+// match reads plain history.  Without D1 the semantics are the LZ4
+// specification's and the flag is ignored.
 //
-// The range is clamped to the launch's nblocks, so no status and no slot
-// outside the frame's blocks is written whatever the record says, and every
-// loop ends with the range.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_frames(
-        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
-        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
-        lz4ada_block_status* __restrict__ status, const FrameRec* __restrict__ frames, uint32_t nframes)
+// (The pointers are the kernels' __restrict__ parameters; saying it here again
+// cost k_decode_idx_frames three VGPRs.)
+template <bool D1>
+__device__ __forceinline__ void decode_chain(DecLds& D, const uint8_t* frame, uint64_t frame_len,
+                                             const lz4ada_block_desc* desc, uint8_t* tab_all, uint8_t* out,
+                                             lz4ada_block_status* status, uint32_t first, uint32_t bend,
+                                             uint32_t stop, int64_t hist)
 {
-	__shared__ DecLds D;
-	if (blockIdx.x >= nframes)
-		return;
-	const uint32_t flags = frames[blockIdx.x].flags;
-	if (!(flags & FRAME_LINKED))
-		return;
-	const uint32_t first = min(frames[blockIdx.x].first, nblocks);
-	const uint32_t bend = first + min(frames[blockIdx.x].nblocks, nblocks - first);
-	int64_t hist = 0, opos = 0, oph = 0;
-	uint32_t stop = bend;  // the first block left DS_RETRY
-	for (uint32_t b = first; b < bend; ++b) {
-		if (opos >= HISTORY_SIZE)
+	int64_t opos = 0, oph = 0;
+	for (uint32_t b = first; b < stop; ++b) {
+		if (D1 && opos >= HISTORY_SIZE)
 			opos = 0;
-		const bool in_d1 = oph >= HISTORY_SIZE && oph <= HISTORY_SIZE + 6;
+		const bool in_d1 = D1 && oph >= HISTORY_SIZE && oph <= HISTORY_SIZE + 6;
 		int32_t len;
 		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status, hist, len);
 		vm_wait();  // the next block reads this output as history
@@ -2696,9 +2693,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 				break;
 			}
 		}
-		opos += len;
-		if (opos >= HISTORY_SIZE)
-			oph = opos;
+		if (D1) {
+			opos += len;
+			if (opos >= HISTORY_SIZE)
+				oph = opos;
+		}
 		if (b + 1 < bend && (uint32_t(len) != desc[b].out_cap ||
 		                     desc[b + 1].out_off != desc[b].out_off + uint64_t(len))) {
 			stop = b + 1;  // the next block's history would not be contiguous
@@ -2708,6 +2707,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	}
 	for (uint32_t r = stop + lane_id(); r < bend; r += 64)
 		status[r].code = DS_RETRY;
+}
+
+// Many linked frames side by side (a many-frame pass, DESIGN.md §12): one wave
+// per frame of the pass.  Workgroup f takes the blocks [first, first + nblocks)
+// of frames[f] when the record carries FRAME_LINKED (any other frame is
+// another launch's) and walks them as one chain without history in front, with
+// quirk D1's round state (decode_chain<true>).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_frames(
+        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
+        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
+        lz4ada_block_status* __restrict__ status, const FrameRec* __restrict__ frames, uint32_t nframes)
+{
+	__shared__ DecLds D;
+	if (blockIdx.x >= nframes)
+		return;
+	const uint32_t flags = frames[blockIdx.x].flags;
+	if (!(flags & FRAME_LINKED))
+		return;
+	const uint32_t first = min(frames[blockIdx.x].first, nblocks);
+	const uint32_t bend = first + min(frames[blockIdx.x].nblocks, nblocks - first);
+	decode_chain<true>(D, frame, frame_len, desc, tab_all, out, status, first, bend, bend, 0);
 }
 
 // Dictionary frames.  A block whose descriptor carries
@@ -2739,9 +2759,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 }
 
 // k_decode_idx_frames with the dictionary before each linked frame's first
-// block: hist starts at dict_used when that block carries BLOCK_DICT and grows
-// block by block as there.  Same clamps: no status and no slot outside the
-// frame's blocks is written whatever the record says.
+// block: the chain starts with dict_used bytes of history when that block
+// carries BLOCK_DICT, with none when it does not (decode_chain<false>).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_frames_dict(
         const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
         uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
@@ -2758,38 +2777,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	const uint32_t bend = first + min(frames[blockIdx.x].nblocks, nblocks - first);
 	if (first >= bend)
 		return;
-	int64_t hist = (wave_uniform(desc[first].flags) & BLOCK_DICT) ? int64_t(dict_used) : 0;
-	uint32_t stop = bend;  // the first block left DS_RETRY
-	for (uint32_t b = first; b < bend; ++b) {
-		int32_t len;
-		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status, hist, len);
-		vm_wait();  // the next block reads this output as history
-		__syncthreads();
-		if (code != DS_OK) {
-			stop = b + 1;  // (its own status is non-zero already)
-			break;
-		}
-		if (b + 1 < bend && (uint32_t(len) != desc[b].out_cap ||
-		                     desc[b + 1].out_off != desc[b].out_off + uint64_t(len))) {
-			stop = b + 1;  // the next block's history would not be contiguous
-			break;
-		}
-		hist += len;
-	}
-	for (uint32_t r = stop + lane_id(); r < bend; r += 64)
-		status[r].code = DS_RETRY;
+	const int64_t hist = (wave_uniform(desc[first].flags) & BLOCK_DICT) ? int64_t(dict_used) : 0;
+	decode_chain<false>(D, frame, frame_len, desc, tab_all, out, status, first, bend, bend, hist);
 }
 
-// The chains of a ranged pass over a dictionary index: that
-// loop with the starting history read from the chain's record (`hash`, which
-// chain records otherwise leave unused) instead of a launch argument, so one
-// launch decodes chains that start from a checkpoint (65,536 bytes) beside
-// chains that start from the dictionary (dict_used).  The history is clamped
-// to DICT_MAX, and it is believed only where the layout can hold it: the
-// chain's first block must carry BLOCK_DICT and lie at least dict_gap(hist)
-// into the slots, else the chain's blocks get DS_RETRY and nothing is decoded.
-// Same clamps: no status and no slot outside the chain's blocks is written
-// whatever the record says.
+// The chains of a ranged pass over a dictionary index: the
+// starting history is read from the chain's record (`hash`, which chain records
+// otherwise leave unused) instead of a launch argument, so one launch decodes
+// chains that start from a checkpoint (65,536 bytes) beside chains that start
+// from the dictionary (dict_used).  The history is clamped to DICT_MAX, and it
+// is believed only where the layout can hold it: the chain's first block must
+// carry BLOCK_DICT and lie at least dict_gap(hist) into the slots, else the
+// chain's blocks get DS_RETRY and nothing is decoded (stop = first).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_idx_chains(
         const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
         uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
@@ -2806,28 +2805,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	if (first >= bend)
 		return;
 	const uint32_t h0 = min(wave_uniform(chains[blockIdx.x].hash), DICT_MAX);
-	int64_t hist = int64_t(h0);
-	uint32_t stop = bend;  // the first block left DS_RETRY
-	if (!(wave_uniform(desc[first].flags) & BLOCK_DICT) || wave_uniform(desc[first].out_off) < dict_gap(h0))
-		stop = first;
-	for (uint32_t b = first; b < stop; ++b) {
-		int32_t len;
-		const int32_t code = decode_block(D, frame, frame_len, desc, b, tab_all, out, status, hist, len);
-		vm_wait();  // the next block reads this output as history
-		__syncthreads();
-		if (code != DS_OK) {
-			stop = b + 1;  // (its own status is non-zero already)
-			break;
-		}
-		if (b + 1 < bend && (uint32_t(len) != desc[b].out_cap ||
-		                     desc[b + 1].out_off != desc[b].out_off + uint64_t(len))) {
-			stop = b + 1;  // the next block's history would not be contiguous
-			break;
-		}
-		hist += len;
-	}
-	for (uint32_t r = stop + lane_id(); r < bend; r += 64)
-		status[r].code = DS_RETRY;
+	const bool holds = (wave_uniform(desc[first].flags) & BLOCK_DICT) && wave_uniform(desc[first].out_off) >= dict_gap(h0);
+	decode_chain<false>(D, frame, frame_len, desc, tab_all, out, status, first, bend, holds ? bend : first,
+	                    int64_t(h0));
 }
 
 // ============================================================ pipelined pair

@@ -1,7 +1,10 @@
-// lz4ada_pass_runs.h -- how the frames of a many-frame pass are cut into runs
-// of one kind.  Standard library only, so a plain C++ program
-// can include it (tools/pass_runs_check.cpp).
+// lz4ada_pass_runs.h -- how the sorted frames of a device call are cut into
+// passes by the byte budget (pass_cut), and how the frames of a
+// pass are cut into runs of one kind (pass_runs).  Standard
+// library only, so a plain C++ program can include it
+// (tools/pass_cut_check.cpp, tools/pass_runs_check.cpp).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <vector>
 
@@ -43,6 +46,38 @@ inline std::vector<PassRun> pass_runs(const std::vector<PassFrame>& fr)
 		k = r.f1;
 	}
 	return runs;
+}
+
+// What a frame asks of the pass that holds it: nothing when it is not taken
+// (it rides along), else its scratch bytes (slots, a dictionary's gaps) and
+// its blocks.
+struct PassCost {
+	bool taken;
+	uint64_t bytes, blocks;
+};
+// The next pass over the sorted frames: [lo, hi), and its taken frames' sums.
+struct PassCut {
+	size_t hi;
+	uint64_t bytes, blocks;
+};
+// As many frames from lo on as `budget` bytes take;
+// frame(k) -> PassCost.  A frame that is not taken costs nothing; the first
+// taken frame is accepted whatever it costs; a pass holds fewer than 2^31
+// blocks, so hi == lo says that frame lo alone holds as many.
+template <class F>
+inline PassCut pass_cut(size_t lo, size_t n, uint64_t budget, F&& frame)
+{
+	PassCut c{ lo, 0, 0 };
+	for (; c.hi < n; ++c.hi) {
+		const PassCost f = frame(c.hi);
+		if (!f.taken)
+			continue;
+		if ((c.bytes && c.bytes + f.bytes > budget) || c.blocks + f.blocks >= (uint64_t(1) << 31))
+			break;
+		c.bytes += f.bytes;
+		c.blocks += f.blocks;
+	}
+	return c;
 }
 
 }  // namespace lz4ada

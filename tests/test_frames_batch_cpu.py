@@ -175,3 +175,22 @@ def test_pass_runs_against_its_definition(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "488281 sequences: no sanitizer report, every run as defined" in r.stdout
     assert "FAIL" not in r.stdout
+
+
+def test_pass_cut_against_its_rules(tmp_path):
+    """The stand-alone program, host code only, under the sanitizers: the cut of
+    the sorted frames into passes against a brute-force statement of its rules,
+    over every sequence of up to 6 frames (not taken, or taken with 1 or 3 blocks
+    at a cost below, equal to or above the budget) from every start, and four
+    cases whose block counts reach 2^31."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "pass_cut_check")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                           "-static-libasan", "-static-libubsan", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "bo-lz4-ada_amd", "csrc"),
+                           os.path.join(ROOT, "tools", "pass_cut_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "137261 sequences: no sanitizer report, every cut as the rules state" in r.stdout
+    assert "FAIL" not in r.stdout
