@@ -212,20 +212,15 @@ static BulkResult bulk_independent(const uint8_t* d_frame, const uint8_t* host_f
 
 
 // The stream state before block `fail`, the first one the bulk path could
-// not take (its predecessors are committed): Output_Pos and
-// Output_Pos_History as lz4ada.adb:678-690 and 785-787 leave them.
+// not take (its predecessors are committed): the round state as the decoded
+// lengths leave it.
 static void resume_state(const std::vector<uint32_t>& lens, Resume& rs)
 {
-	int64_t pos = 0, oph = 0;
+	rs.round = RoundState{};
 	for (uint32_t n : lens) {
-		if (pos >= HISTORY_SIZE)  // :678-680
-			pos = 0;
-		pos += n;
-		if (pos >= HISTORY_SIZE)  // :688-690, 785-787
-			oph = pos;
+		rs.round.start();
+		rs.round.advance(n);
 	}
-	rs.output_pos = pos;
-	rs.output_pos_history = oph;
 }
 
 // One frame from host memory (Single_Frame semantics): the bulk path when
@@ -262,12 +257,10 @@ void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consume
 	if (indexed && info.frame_len <= len && info.format != LZ4ADA_FORMAT_SKIPPABLE &&
 	    !getenv("LZ4ADA_EXACT_ONLY")) {
 		device_check_or_raise();
-		struct {
-			uint8_t* p;
-		} d_frame{ scratch(SC_FRAME, size_t(info.frame_len)) };
+		uint8_t* const d_frame = scratch(SC_FRAME, size_t(info.frame_len));
 		phase("index");
-		if (d_frame.p) {
-			HIP_OK(hipMemcpy(d_frame.p, f, size_t(info.frame_len), hipMemcpyHostToDevice));
+		if (d_frame) {
+			HIP_OK(hipMemcpy(d_frame, f, size_t(info.frame_len), hipMemcpyHostToDevice));
 			phase("h2d");
 			lz4ada_xxh32_state hs;
 			lz4ada_xxh32_reset(&hs, 0);
@@ -279,7 +272,7 @@ void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consume
 			std::vector<uint32_t> lens;
 			int64_t fail = -1;
 			if (info.independent && !getenv("LZ4ADA_FORCE_LINKED"))
-				r = bulk_independent(d_frame.p, f, info, descs, out, h, total, lens, fail);
+				r = bulk_independent(d_frame, f, info, descs, out, h, total, lens, fail);
 			phase("bulk");
 			const bool linked = r == BULK_PRE_REF;
 			if (linked) {
@@ -297,7 +290,7 @@ void decode_one_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& consume
 						HIP_OK(hipMemcpy(dst, F, size_t(n), hipMemcpyDeviceToHost));
 					out.commit(n);
 				};
-				r = bulk_linked(d_frame.p, uint64_t(info.frame_len), info.block_max, descs, ls, total,
+				r = bulk_linked(d_frame, uint64_t(info.frame_len), info.block_max, descs, ls, total,
 				                lens, fail, nullptr);
 			}
 			// blocks before `fail` that already decode past the declared content

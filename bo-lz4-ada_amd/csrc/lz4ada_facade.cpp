@@ -15,8 +15,7 @@ struct lz4ada_decompressor {
 	Meta m;
 	bool is_at_end_mark = false;
 	std::vector<uint8_t> input_buffer;  // Input_Buffer(0 .. In_Last)
-	int64_t output_pos = 0;
-	int64_t output_pos_history = 0;
+	RoundState round;  // Output_Pos / Output_Pos_History
 	int64_t input_length = -1;
 	std::string err;
 	int64_t exact_blocks = 0;  // blocks decoded by the reference-exact serial kernel (diagnostics)
@@ -116,8 +115,7 @@ struct lz4ada_decompressor {
 		ahead.clear();
 		is_at_end_mark = false;
 		input_length = -1;
-		output_pos = 0;
-		output_pos_history = 0;
+		round = RoundState{};
 		reset_content_hash();
 	}
 
@@ -308,8 +306,8 @@ struct lz4ada_decompressor {
 			return;
 		}
 		SerialState s{};
-		s.output_pos = output_pos;
-		s.output_pos_history = output_pos_history;
+		s.output_pos = round.pos;
+		s.output_pos_history = round.history;
 		s.size_remaining = m.size_remaining;
 		s.has_content_size = m.has_content_size ? 1 : 0;
 		HIP_OK(hipMemcpyAsync(d_serial.p, &s, sizeof s, hipMemcpyHostToDevice, stream));
@@ -320,8 +318,8 @@ struct lz4ada_decompressor {
 		HIP_OK(hipMemcpyAsync(&s, d_serial.p, sizeof s, hipMemcpyDeviceToHost, stream));
 		HIP_OK(hipStreamSynchronize(stream));
 		// state changes before a raise persist, as with the Ada record
-		output_pos = s.output_pos;
-		output_pos_history = s.output_pos_history;
+		round.pos = s.output_pos;
+		round.history = s.output_pos_history;
 		if (m.has_content_size)
 			m.size_remaining = s.size_remaining;
 		if (s.code != DS_OK)
@@ -424,13 +422,7 @@ struct lz4ada_decompressor {
 	void history_of(int64_t start, int64_t& n0, int64_t& n1) const
 	{
 		n1 = start;
-		n0 = std::min<int64_t>(65535, start + output_pos_history) - n1;
-	}
-	// Quirk D1 can only strike right after a round that ended within the
-	// reference's 8-byte wild copy of 64 KiB (lz4ada.adb:811-817, 862-879).
-	bool d1_window() const
-	{
-		return output_pos_history >= HISTORY_SIZE && output_pos_history <= HISTORY_SIZE + 6;
+		n0 = std::min<int64_t>(65535, start + round.history) - n1;
 	}
 
 	std::pair<bool, std::string> block_checksum(const uint8_t* blk, int64_t blen) const
@@ -471,7 +463,7 @@ struct lz4ada_decompressor {
 		const int fv = facade_variant();
 		if (!linked && !(fv < 0 && (raw_len >= LONE_MIN || fv == -2)))
 			return false;
-		const int64_t start = output_pos >= HISTORY_SIZE ? 0 : output_pos;  // :678-680
+		const int64_t start = round.next_start();
 		if (buflen - start <= 0)
 			return false;
 		int64_t cap = block_room(buflen - start, raw_len, true);
@@ -522,9 +514,9 @@ struct lz4ada_decompressor {
 		stage_st.reserve(sizeof(lz4ada_block_status));
 		lz4ada_block_status* hst = reinterpret_cast<lz4ada_block_status*>(stage_st.p);
 		HIP_OK(launch_decode_lone_parse(pin_blk.p, raw_len, cap, hst, d_lone.p, sb, stream,
-		                                linked ? d_buf.p + output_pos_history - n0 : nullptr, int32_t(n0),
+		                                linked ? d_buf.p + round.history - n0 : nullptr, int32_t(n0),
 		                                linked ? d_buf.p : nullptr, int32_t(n1),
-		                                linked && d1_window() ? int(output_pos_history) : 0, d_blk.p, blen,
+		                                linked && round.in_d1() ? int(round.history) : 0, d_blk.p, blen,
 		                                true));
 		lap("parse");
 		if (bcl > 0) {
@@ -547,9 +539,8 @@ struct lz4ada_decompressor {
 		const int64_t nout = int64_t(st.out_len);
 		if (m.has_content_size)
 			m.size_remaining -= uint64_t(nout);
-		output_pos = start + nout;
-		if (output_pos >= HISTORY_SIZE)  // :785-787
-			output_pos_history = output_pos;
+		round.start();
+		round.advance(nout);
 		first = start;
 		last = start + nout - 1;
 		if (nout > 0)
@@ -563,7 +554,7 @@ struct lz4ada_decompressor {
 		const bool linked = m.is_format == F_MODERN && !(m.flg & 0x20u);
 		if (getenv("LZ4ADA_FACADE_EXACT"))
 			return -1;
-		const int64_t start = output_pos >= HISTORY_SIZE ? 0 : output_pos;  // :678-680
+		const int64_t start = round.next_start();
 		if (buflen - start <= 0 || raw_len > INT32_MAX)
 			return -1;
 		const int64_t cap = std::max<int64_t>(block_room(buflen - start, raw_len, m.is_compressed), 1);
@@ -597,9 +588,8 @@ struct lz4ada_decompressor {
 		if (nout > 0)  // deliver() reads it from the mirror, after this copy
 			HIP_OK(hipMemcpyAsync(d_buf.p + start, d_scr.p, size_t(nout), hipMemcpyDeviceToDevice,
 			                      stream));
-		output_pos = start + nout;
-		if (output_pos >= HISTORY_SIZE)  // :785-787 (:688-690 for stored blocks)
-			output_pos_history = output_pos;
+		round.start();
+		round.advance(nout);
 		first = start;
 		last = start + nout - 1;
 		return true;
@@ -693,13 +683,12 @@ struct lz4ada_decompressor {
 	{
 		if (buflen > d_buf_len)
 			grow_mirror(buflen);
-		const int64_t start = output_pos >= HISTORY_SIZE ? 0 : output_pos;
+		const int64_t start = round.next_start();
 		LinkedHist lh;
 		history_of(start, lh.n0, lh.n1);
-		lh.h0 = d_buf.p + output_pos_history - lh.n0;
+		lh.h0 = d_buf.p + round.history - lh.n0;
 		lh.h1 = d_buf.p;
-		lh.output_pos = output_pos;
-		lh.output_pos_history = output_pos_history;
+		lh.round = round;
 		const int64_t bmax = int64_t(1) << (8 + 2 * ((m.bd & 0x70u) >> 4));
 		int64_t room = 0;
 		for (const auto& d : ahead.descs)
@@ -770,7 +759,7 @@ struct lz4ada_decompressor {
 		const size_t k = ahead.next++;
 		const lz4ada_block_desc& d = ahead.descs[k];
 		const lz4ada_block_status& st = ahead.st[k];
-		const int64_t start = output_pos >= HISTORY_SIZE ? 0 : output_pos;  // :678-680
+		const int64_t start = round.next_start();
 		const int64_t nout = int64_t(st.out_len);
 		if (st.code != DS_OK || (bcl && st.cksum != d.cksum) || start + nout > buflen ||
 		    (m.has_content_size && uint64_t(nout) > m.size_remaining)) {
@@ -794,9 +783,8 @@ struct lz4ada_decompressor {
 		}
 		if (m.has_content_size)
 			m.size_remaining -= uint64_t(nout);
-		output_pos = start + nout;
-		if (output_pos >= HISTORY_SIZE)
-			output_pos_history = output_pos;
+		round.start();
+		round.advance(nout);
 		first = start;
 		last = start + nout - 1;
 		return true;
@@ -1187,8 +1175,7 @@ void lz4ada::exact_frame(const uint8_t* f, int64_t len, Sink& out, int64_t& cons
 	int eof = LZ4ADA_EOF_NO;
 	int64_t pos = consumed;
 	if (resume) {
-		ctx->output_pos = resume->output_pos;
-		ctx->output_pos_history = resume->output_pos_history;
+		ctx->round = resume->round;
 		if (ctx->m.has_content_size)
 			ctx->m.size_remaining -= resume->committed;
 		ctx->hash_all = resume->hash;

@@ -113,7 +113,7 @@ LZ4ADA_HD inline bool walk_is_any_magic(uint32_t v)
 	return v == 0x184d2204u || v == 0x184c2102u || (v >= 0x184d2a50u && v <= 0x184d2a5fu);
 }
 
-// slot_cap (lz4ada_host_common.cpp)
+// slot_cap (lz4ada_linked_accept.h)
 LZ4ADA_HD inline uint32_t walk_slot_cap(uint32_t in_len, bool stored, int64_t bmax)
 {
 	if (stored)

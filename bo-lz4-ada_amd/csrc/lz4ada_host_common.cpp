@@ -619,13 +619,6 @@ bool decode_lone_blocks(const uint8_t* host_in, const uint8_t* d_in,
 	return ok;
 }
 
-uint32_t slot_cap(const lz4ada_block_desc& d, int64_t bmax)
-{
-	if (d.flags & LZ4ADA_BLOCK_STORED)
-		return d.in_len;
-	return uint32_t(std::min<uint64_t>(uint64_t(bmax), 255ull * d.in_len + 64));
-}
-
 std::vector<std::pair<uint32_t, uint32_t>> batches_of(const std::vector<lz4ada_block_desc>& descs,
                                                       int64_t bmax, uint64_t extra, uint64_t budget)
 {

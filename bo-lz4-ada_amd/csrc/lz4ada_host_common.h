@@ -7,7 +7,10 @@
 // instance of the shared state and every non-template body.  Units that
 // include it: lz4ada_facade.cpp (the streaming Update facade and the
 // XXHash32 C-ABI), lz4ada_bulk.cpp (the bulk frame paths and their C-ABI),
-// lz4ada_bulk_linked.cpp (the linked-frame bulk path), lz4ada_bulk_frames.cpp
+// lz4ada_bulk_linked.cpp (the linked-frame bulk path in stages; its round
+// state is lz4ada_round_state.h's, its host decisions -- laying a batch,
+// accepting blocks, plane modes -- lz4ada_linked_accept.h's, both plain C++ for
+// tools/linked_accept_check.cpp), lz4ada_bulk_frames.cpp
 // (many frames in one device pass), lz4ada_bulk_frames_device.cpp (the same
 // pass from device memory to device memory), lz4ada_frames_pass.cpp (the
 // device half of that pass, which both share), lz4ada_bulk_ranges.cpp (the
@@ -37,6 +40,7 @@
 
 #include "lz4ada_hip.h"
 #include "lz4ada_internal.h"
+#include "lz4ada_linked_accept.h"
 #include "lz4ada_pass_runs.h"
 
 namespace lz4ada {
@@ -306,14 +310,14 @@ struct LinkedSink {
 
 // A linked batch that starts mid-frame (the facade's read-ahead): the
 // history before its first block, as device bytes oldest first (the
-// reference's Buffer keeps it in two places), and the reference's
-// Output_Pos / Output_Pos_History there (quirk D1).
+// reference's Buffer keeps it in two places), and the round state there
+// (quirk D1).
 struct LinkedHist {
 	const uint8_t* h0 = nullptr;
 	int64_t n0 = 0;
 	const uint8_t* h1 = nullptr;
 	int64_t n1 = 0;
-	int64_t output_pos = 0, output_pos_history = 0;
+	RoundState round;
 };
 BulkResult bulk_linked(const uint8_t* d_frame, uint64_t frame_len, int64_t block_max,
                               const std::vector<lz4ada_block_desc>& descs, LinkedSink& sink,
@@ -352,8 +356,7 @@ struct Sink {
 // the content hash (:709-714) over the bytes already committed.
 struct Resume {
 	int64_t at = 0;          // frame offset of the resume block's size word
-	int64_t output_pos = 0;  // Ctx.Output_Pos before it
-	int64_t output_pos_history = 0;
+	RoundState round;        // the round state before it
 	uint64_t committed = 0;  // bytes of the blocks before it
 	lz4ada_xxh32_state hash{};
 	const uint8_t* output = nullptr;  // those bytes, and each block's length
@@ -410,13 +413,7 @@ uint8_t* scratch(int role, size_t bytes);
 // a positive byte count from the environment, else dflt
 int64_t env_bytes(const char* name, int64_t dflt);
 
-// Output slot capacity of one block: a stored block is its payload; a
-// compressed one decodes to at most 255 bytes per payload byte (a length
-// extension byte adds <= 255 to a match; everything else expands less), so
-// a frame of many small flushed blocks does not reserve block_max each.
-uint32_t slot_cap(const lz4ada_block_desc& d, int64_t bmax);
-
-inline uint64_t round256(uint64_t v) { return (v + 255) & ~uint64_t(255); }
+// (slot_cap, a block's output slot capacity, and round256: lz4ada_linked_accept.h)
 
 // Contiguous runs of blocks [lo, hi) whose slot bytes (plus `extra` per
 // block) stay within `budget` (at least one block each).

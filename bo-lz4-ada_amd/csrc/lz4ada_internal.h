@@ -12,6 +12,7 @@
 #include <string>
 
 #include "lz4ada_hip.h"
+#include "lz4ada_round_state.h"
 
 namespace lz4ada {
 
@@ -22,38 +23,13 @@ constexpr uint32_t P3 = 3266489917u;
 constexpr uint32_t P4 = 668265263u;
 constexpr uint32_t P5 = 374761393u;
 
-constexpr int64_t HISTORY_SIZE = 65536;  // lz4ada.ads:350
 constexpr int64_t BLOCK_SIZE_BYTES = 4;  // lz4ada.ads:351
 
 // Linked frames (lz4ada_linked.hip): every block slot is preceded by this
 // many readable history bytes (the largest LZ4 offset).
 constexpr int32_t LINK_HIST = 65535;
-// Quirk D1: the reference's 8-byte wild copy (lz4ada.adb:811-817) may
-// clobber history bytes [Output_Pos + 1, Output_Pos + 7] before a match
-// reads them; that needs Output_Pos_History in [65536, 65542] and an offset
-// >= Output_Pos_History - 7 >= D1_OFF.  The decoders flag every block with
-// such a match reaching before its start (status aux bit AUX_D1_RISK on a
-// DS_OK block) and the host sends those frames to the exact path.
-constexpr int32_t D1_OFF = int32_t(HISTORY_SIZE) - 7;
-constexpr int32_t AUX_D1_RISK = 1;
-// Quirk D1 in the linked bulk path, emulated (round 6): the host predicts
-// each block's round state from the slot sizes (every block full) and
-// passes it in the descriptor's flags -- BLOCK_D1_ROUND: the block's round
-// follows one that ended at Output_Pos_History = 65536 + the 3 bits at
-// BLOCK_D1_OPH_SHIFT; bits from BLOCK_N1_SHIFT: Output_Pos at the block's
-// start (its place in the round).  The index decoder then writes a D1
-// match's first bytes as the reference's wild literal copy leaves them
-// (lz4ada.adb:811-817, 862-879; the lone decoder's k_lone_words does the
-// same); its status carries AUX_D1_EMU (decoded under a prediction), and
-// the host accepts such a block only if the real round state equals the
-// prediction.  (Bits 0-1 are the public flags.)
-constexpr uint32_t BLOCK_D1_ROUND = 8u;
-constexpr int BLOCK_D1_OPH_SHIFT = 4;
-constexpr int BLOCK_N1_SHIFT = 16;
-constexpr int32_t AUX_D1_EMU = 4;
-// the linked path's literal-zero decode (k_decode_idx_zl): a match reads
-// history positions below 256, whose high byte is 0 like a literal's
-constexpr int32_t AUX_DEEP_HIST = 2;
+// (HISTORY_SIZE, quirk D1's constants and the linked path's aux bits:
+// lz4ada_round_state.h)
 
 // Device status codes written by the decode kernels (per block).
 enum DevStatus : int32_t {
