@@ -9,7 +9,10 @@
 // (one D2H per pass); no payload byte crosses, except that a content checksum
 // over more than lz4ada_batch_hash_max() bytes is hashed by the host chain
 // (content_xxh32_d2h with no host destination).  The jobs are cut into passes
-// only when their slots exceed LZ4ADA_BATCH_BYTES.
+// only when their slots exceed LZ4ADA_BATCH_BYTES.  A linked call (DESIGN.md
+// §21) differs in the kernel of a pass that holds a continuation block
+// (k_compress_blocks_linked, which reads a block's history from d_in, never
+// from a slot) and in the header's B.Indep bit.
 #include "lz4ada_compress.h"
 #include "lz4ada_host_common.h"
 
@@ -32,8 +35,8 @@ inline size_t up16(size_t v) { return (v + 15) & ~size_t(15); }
 // One pass over the jobs [lo, hi), nb blocks and slot_b slot bytes in all:
 // their frames go to d_out from *base on, which then moves past them.
 void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* jobs, size_t lo, size_t hi,
-                   uint64_t nb64, uint64_t slot_b, uint32_t id, uint32_t flags, const PassDict& dict, uint8_t* d_out,
-                   uint64_t* base, uint64_t hash_max, hipStream_t stream)
+                   uint64_t nb64, uint64_t slot_b, uint32_t id, uint32_t flags, const PassDict& dict, bool linked,
+                   uint8_t* d_out, uint64_t* base, uint64_t hash_max, hipStream_t stream)
 {
 	const bool bck = (flags & LZ4ADA_COMP_BLOCK_CHECKSUM) != 0, cck = (flags & LZ4ADA_COMP_CONTENT_CHECKSUM) != 0;
 	const uint32_t nb = uint32_t(nb64), nj = uint32_t(hi - lo);
@@ -74,9 +77,11 @@ void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* 
 	const CompJobRec* const rec = reinterpret_cast<const CompJobRec*>(h.p + up_b);
 	uint64_t fixed = 0, slot = 0;
 	uint32_t b = 0;
+	bool cont = false;  // a linked pass with a block that has its record in front of it
 	for (size_t k = lo; k < hi; ++k) {
 		const lz4ada_compress_job& j = jobs[k];
 		const uint32_t n = uint32_t(comp_nblocks(j.in_len, blen));
+		cont = cont || (linked && n > 1);
 		cj[k - lo] = CompJob{ uint64_t(j.in_off), uint64_t(j.in_len), fixed, b, n };
 		fixed += uint64_t(comp_header_len(flags, dict.dflags) + comp_trailer_len(flags));
 		for (uint32_t i = 0; i < n; ++i, ++b) {
@@ -97,7 +102,10 @@ void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* 
 	HIP_OK(hipMemsetAsync(d_rec, 0, rec_b, stream));
 	if (cck)  // over the records where they lie; the longer ones are the host chain's
 		HIP_OK(launch_xxh32_spans(d_in, d_frec, nj, hash_max, stream));
-	if (dict.dl)
+	if (cont)  // every block of the pass, each with the history its place gives it (read from d_in)
+		HIP_OK(launch_compress_blocks_linked(d_in, d_blk, d_jobs, nb, dict.d_tail, dict.dl, dict.d_seed, d_slots,
+		                                     d_csize, stream));
+	else if (dict.dl)
 		HIP_OK(launch_compress_blocks_dict(d_in, d_blk, nb, dict.d_tail, dict.dl, dict.d_seed, d_slots, d_csize,
 		                                   stream));
 	else
@@ -109,8 +117,8 @@ void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* 
 		HIP_OK(launch_block_checksums(d_out, d_desc, nb, d_st, stream));
 		HIP_OK(launch_compress_block_cksums(d_desc, d_st, nb, d_out, stream));
 	}
-	HIP_OK(launch_compress_frames(d_jobs, nj, d_loc, d_part, nb, id, flags, dict.dflags, dict.dict_id, *base, d_frec,
-	                              d_out, d_rec, stream));
+	HIP_OK(launch_compress_frames(d_jobs, nj, d_loc, d_part, nb, id, flags, dict.dflags, dict.dict_id, linked, *base,
+	                              d_frec, d_out, d_rec, stream));
 	// the pass's host synchronisation: places, lengths and counts, no payload byte
 	HIP_OK(hipMemcpyAsync(h.p + up_b, d_rec, rec_b, hipMemcpyDeviceToHost, stream));
 	HIP_OK(hipStreamSynchronize(stream));
@@ -139,10 +147,11 @@ void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* 
 		HIP_OK(hipStreamSynchronize(stream));
 }
 
-// Both entries: cdict null is the plain call.
+// Every entry: cdict null is the plain call; linked: frames of linked blocks
+// (DESIGN.md §21), with the same slots and the same passes.
 int compress_frames(const char* ENTRY, const void* d_in, int64_t in_len, lz4ada_compress_job* jobs, int64_t njobs,
-                    const lz4ada_compress_options* opt, const lz4ada_compress_dict* cdict, void* d_out, int64_t out_cap,
-                    int64_t* out_len, void* stream)
+                    const lz4ada_compress_options* opt, const lz4ada_compress_dict* cdict, bool linked, void* d_out,
+                    int64_t out_cap, int64_t* out_len, void* stream)
 {
 	if (out_len)
 		*out_len = 0;
@@ -216,7 +225,7 @@ int compress_frames(const char* ENTRY, const void* d_in, int64_t in_len, lz4ada_
 			}
 			if (nb >= (uint64_t(1) << 31))
 				raise(LZ4ADA_CONSTRAINT_ERROR, std::string(ENTRY) + ": a record holds more blocks than a pass takes");
-			compress_pass(ENTRY, static_cast<const uint8_t*>(d_in), jobs, lo, hi, nb, acc, id, flags, dict,
+			compress_pass(ENTRY, static_cast<const uint8_t*>(d_in), jobs, lo, hi, nb, acc, id, flags, dict, linked,
 			              static_cast<uint8_t*>(d_out), &base, hash_max, s);
 			lo = hi;
 		}
@@ -231,8 +240,8 @@ extern "C" int lz4ada_compress_frames_device(const void* d_in, int64_t in_len, l
                                              int64_t njobs, const lz4ada_compress_options* opt, void* d_out,
                                              int64_t out_cap, int64_t* out_len, void* stream)
 {
-	return compress_frames("lz4ada_compress_frames_device", d_in, in_len, jobs, njobs, opt, nullptr, d_out, out_cap,
-	                       out_len, stream);
+	return compress_frames("lz4ada_compress_frames_device", d_in, in_len, jobs, njobs, opt, nullptr, false, d_out,
+	                       out_cap, out_len, stream);
 }
 
 extern "C" int lz4ada_compress_frames_device_dict(const void* d_in, int64_t in_len, lz4ada_compress_job* jobs,
@@ -240,6 +249,15 @@ extern "C" int lz4ada_compress_frames_device_dict(const void* d_in, int64_t in_l
                                                   const lz4ada_compress_dict* dict, void* d_out, int64_t out_cap,
                                                   int64_t* out_len, void* stream)
 {
-	return compress_frames("lz4ada_compress_frames_device_dict", d_in, in_len, jobs, njobs, opt, dict, d_out, out_cap,
-	                       out_len, stream);
+	return compress_frames("lz4ada_compress_frames_device_dict", d_in, in_len, jobs, njobs, opt, dict, false, d_out,
+	                       out_cap, out_len, stream);
+}
+
+extern "C" int lz4ada_compress_frames_device_linked(const void* d_in, int64_t in_len, lz4ada_compress_job* jobs,
+                                                    int64_t njobs, const lz4ada_compress_options* opt,
+                                                    const lz4ada_compress_dict* dict, void* d_out, int64_t out_cap,
+                                                    int64_t* out_len, void* stream)
+{
+	return compress_frames("lz4ada_compress_frames_device_linked", d_in, in_len, jobs, njobs, opt, dict, true, d_out,
+	                       out_cap, out_len, stream);
 }

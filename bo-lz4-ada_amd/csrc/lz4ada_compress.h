@@ -32,6 +32,9 @@ constexpr int64_t COMP_MAX_INPUT = 0x7E000000;  // LZ4_MAX_INPUT_SIZE
 // min(dict_len, COMP_DICT_MAX) bytes D lie at [-dl, 0) in front of every block,
 // and the table holds virtual position + dl + 1.
 constexpr int64_t COMP_DICT_MAX = 65536;
+// In a linked frame block i >= 1 of a record has the
+// COMP_LINK_WINDOW record bytes in front of it in the dictionary's place.
+constexpr int64_t COMP_LINK_WINDOW = 65536;
 
 LZ4ADA_HD inline uint32_t comp_hash(uint32_t four_bytes)
 {
@@ -82,11 +85,12 @@ LZ4ADA_HD inline int64_t comp_frame_bound(int64_t n, uint32_t block_id, uint32_t
 }
 // Magic, FLG, BD, the content size when asked for, the dictionary id under
 // LZ4ADA_COMP_DICT_WRITE_ID, HC (over all of them) into h[0 .. 19) -> comp_header_len.
+// linked: a frame of linked blocks, FLG 0x20 (B.Indep) clear.
 LZ4ADA_HD inline int comp_header(uint8_t* h, uint32_t block_id, uint32_t flags, uint64_t content_size,
-                                 uint32_t dflags = 0, uint32_t dict_id = 0)
+                                 uint32_t dflags = 0, uint32_t dict_id = 0, bool linked = false)
 {
 	h[0] = 0x04, h[1] = 0x22, h[2] = 0x4d, h[3] = 0x18;
-	h[4] = uint8_t(0x40 | 0x20 | ((flags & LZ4ADA_COMP_BLOCK_CHECKSUM) ? 0x10 : 0) |
+	h[4] = uint8_t(0x40 | (linked ? 0 : 0x20) | ((flags & LZ4ADA_COMP_BLOCK_CHECKSUM) ? 0x10 : 0) |
 	               ((flags & LZ4ADA_COMP_CONTENT_SIZE) ? 0x08 : 0) | ((flags & LZ4ADA_COMP_CONTENT_CHECKSUM) ? 0x04 : 0) |
 	               ((dflags & LZ4ADA_COMP_DICT_WRITE_ID) ? 0x01 : 0));
 	h[5] = uint8_t(comp_block_id(block_id) << 4);

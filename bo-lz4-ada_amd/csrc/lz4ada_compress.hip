@@ -19,6 +19,9 @@
 // A dictionary call compresses its blocks with
 // k_compress_blocks_dict (lz4ada_compress_dict.hip) and shares the rest; its
 // dflags / dict_id reach the emit and the header for the 4 bytes of the id.
+// A linked call compresses a pass that holds a continuation
+// block with k_compress_blocks_linked (lz4ada_compress_linked.hip); the header
+// learns its B.Indep bit from `linked`.
 // No kernel waits for another workgroup; every loop is bounded by the block
 // length or the block count.
 #include <hip/hip_runtime.h>
@@ -288,7 +291,7 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_frames(const CompJob* __re
                                                              const uint64_t* __restrict__ loc,
                                                              const uint64_t* __restrict__ part, uint32_t nblocks,
                                                              uint32_t block_id, uint32_t flags, uint32_t dflags,
-                                                             uint32_t dict_id, uint64_t base,
+                                                             uint32_t dict_id, uint32_t linked, uint64_t base,
                                                              const FrameRec* __restrict__ frec,
                                                              uint8_t* __restrict__ d_out, CompJobRec* __restrict__ rec)
 {
@@ -300,7 +303,7 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_frames(const CompJob* __re
 	const uint64_t body = comp_off(loc, part, nblocks, J.first + J.nblocks) - lo;
 	const uint64_t at = base + J.fixed_before + lo;
 	uint8_t hdr[19];
-	const int hn = comp_header(hdr, block_id, flags, J.in_len, dflags, dict_id);
+	const int hn = comp_header(hdr, block_id, flags, J.in_len, dflags, dict_id, linked != 0);
 	g8* t = gptr(d_out) + at;
 	for (int i = 0; i < hn; ++i)
 		t[i] = hdr[i];
@@ -361,13 +364,14 @@ hipError_t launch_compress_block_cksums(const lz4ada_block_desc* d_desc, const l
 
 hipError_t launch_compress_frames(const CompJob* d_jobs, uint32_t njobs, const uint64_t* d_loc, const uint64_t* d_part,
                                   uint32_t nblocks, uint32_t block_id, uint32_t flags, uint32_t dflags,
-                                  uint32_t dict_id, uint64_t base, const FrameRec* d_frec, uint8_t* d_out,
-                                  CompJobRec* d_rec, hipStream_t stream)
+                                  uint32_t dict_id, uint32_t linked, uint64_t base, const FrameRec* d_frec,
+                                  uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream)
 {
 	if (njobs == 0)
 		return hipSuccess;
 	hipLaunchKernelGGL(k_compress_frames, dim3((njobs + COMP_WG - 1) / COMP_WG), dim3(COMP_WG), 0, stream, d_jobs,
-	                   njobs, d_loc, d_part, nblocks, block_id, flags, dflags, dict_id, base, d_frec, d_out, d_rec);
+	                   njobs, d_loc, d_part, nblocks, block_id, flags, dflags, dict_id, linked, base, d_frec, d_out,
+	                   d_rec);
 	return hipGetLastError();
 }
 

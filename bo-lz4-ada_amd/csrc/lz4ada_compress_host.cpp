@@ -31,6 +31,13 @@
 // into the block; it still ends at n - 5.  The offset is p - c.  D and the block
 // are indexed as two arrays, never as a concatenated copy.  With dl == 0 this
 // is the statement above, byte for byte.
+//
+// Linked blocks.  Block 0 of a record is compressed as above,
+// against the dictionary or nothing.  Block i >= 1 at `at` is the same
+// function with D = src + at - 65,536 and dl = 65,536, the record's own bytes
+// in front of it, whether or not there is a dictionary (it has slid out of
+// the window).  Nothing else differs: position -65,536 is seeded and never
+// valid, and the two arrays happen to be one.
 #include <stdint.h>
 #include <string.h>
 
@@ -113,9 +120,11 @@ int64_t compress_block(const uint8_t* src, int64_t n, const uint8_t* D, int64_t 
 	return op + lit;
 }
 
-// One record as one frame; dl bytes at D in front of every block.
+// One record as one frame; dl bytes at D in front of every block, or, linked,
+// in front of block 0 alone, and the record's own 65,536 bytes in front of
+// every later block.
 int64_t compress_frame(const uint8_t* src, int64_t n, const lz4ada_compress_options* opt, const uint8_t* D, int64_t dl,
-                       uint32_t dict_id, uint32_t dflags, uint8_t* dst, int64_t cap)
+                       uint32_t dict_id, uint32_t dflags, uint8_t* dst, int64_t cap, bool linked = false)
 {
 	const uint32_t id = opt ? opt->block_id : 0, flags = opt ? opt->flags : 0;
 	if (n < 0 || cap < 0 || (n > 0 && !src) || (cap > 0 && !dst) || !comp_options_ok(id, flags) ||
@@ -124,11 +133,13 @@ int64_t compress_frame(const uint8_t* src, int64_t n, const lz4ada_compress_opti
 	if (cap < comp_frame_bound(n, id, flags, dflags))
 		return -int64_t(LZ4ADA_TOO_LITTLE_MEMORY);
 	const int64_t blen = comp_block_len(id);
-	int64_t pos = comp_header(dst, id, flags, uint64_t(n), dflags, dict_id);
+	int64_t pos = comp_header(dst, id, flags, uint64_t(n), dflags, dict_id, linked);
 	for (int64_t at = 0; at < n; at += blen) {
 		const int64_t len = n - at < blen ? n - at : blen;
+		const bool cont = linked && at > 0;  // at >= blen >= COMP_LINK_WINDOW
 		// compressed only when shorter than the block
-		int64_t c = compress_block(src + at, len, D, dl, dst + pos + 4, len - 1);
+		int64_t c = compress_block(src + at, len, cont ? src + at - COMP_LINK_WINDOW : D, cont ? COMP_LINK_WINDOW : dl,
+		                           dst + pos + 4, len - 1);
 		const bool stored = c == 0;
 		if (stored) {
 			memcpy(dst + pos + 4, src + at, size_t(len));
@@ -217,6 +228,16 @@ int64_t lz4ada_compress_frame_dict_host(const uint8_t* src, int64_t n, const lz4
 		return -int64_t(LZ4ADA_ASSERTION_ERROR);
 	const int64_t dl = dict_len < COMP_DICT_MAX ? dict_len : COMP_DICT_MAX;
 	return compress_frame(src, n, opt, dl ? dict + (dict_len - dl) : nullptr, dl, dict_id, dict_flags, dst, cap);
+}
+
+int64_t lz4ada_compress_frame_linked_host(const uint8_t* src, int64_t n, const lz4ada_compress_options* opt,
+                                          const uint8_t* dict, int64_t dict_len, uint32_t dict_id, uint32_t dict_flags,
+                                          uint8_t* dst, int64_t cap)
+{
+	if (dict_len < 0 || (dict_len > 0 && !dict))
+		return -int64_t(LZ4ADA_ASSERTION_ERROR);
+	const int64_t dl = dict_len < COMP_DICT_MAX ? dict_len : COMP_DICT_MAX;
+	return compress_frame(src, n, opt, dl ? dict + (dict_len - dl) : nullptr, dl, dict_id, dict_flags, dst, cap, true);
 }
 
 }  // extern "C"

@@ -633,6 +633,14 @@ hipError_t launch_compress_blocks_dict(const uint8_t* d_in, const CompBlock* d_b
 // d_seed[0 .. COMP_TABLE): for every hash the last position + 1 of d_tail[0 .. dl)
 // whose four bytes lie inside it, 0 for none (dl < 4: all 0).
 hipError_t launch_compress_dict_table(const uint8_t* d_tail, uint32_t dl, uint32_t* d_seed, hipStream_t stream);
+// The blocks of linked frames (lz4ada_compress_linked.hip):
+// block b begins its record when its in_off is d_jobs[d_blk[b].job].in_off and
+// is then compressed as by the two launches above (dl == 0: no dictionary,
+// d_tail and d_seed are not read); any other block has the 65,536 bytes in
+// front of it in d_in as its history and seeds its own table from them.
+hipError_t launch_compress_blocks_linked(const uint8_t* d_in, const CompBlock* d_blk, const CompJob* d_jobs,
+                                         uint32_t nblocks, const uint8_t* d_tail, uint32_t dl, const uint32_t* d_seed,
+                                         uint8_t* d_slots, uint32_t* d_csize, hipStream_t stream);
 hipError_t launch_compress_scan(const CompBlock* d_blk, const uint32_t* d_csize, uint32_t nblocks, uint32_t flags,
                                 uint64_t* d_loc, uint64_t* d_part, hipStream_t stream);
 // One workgroup per block: size word and payload into d_out (the pass begins
@@ -648,9 +656,11 @@ hipError_t launch_compress_block_cksums(const lz4ada_block_desc* d_desc, const l
 // One thread per job: header, end mark, the content checksum when d_frec[j]
 // carries one (launch_xxh32_spans over d_in; d_frec may be null without
 // LZ4ADA_COMP_CONTENT_CHECKSUM), and d_rec[j].out_off / out_len.  dflags and
-// dict_id: a dictionary call's, for the header; else 0.
+// dict_id: a dictionary call's, for the header; else 0.  linked: nonzero for
+// frames of linked blocks (B.Indep clear).
 hipError_t launch_compress_frames(const CompJob* d_jobs, uint32_t njobs, const uint64_t* d_loc, const uint64_t* d_part,
                                   uint32_t nblocks, uint32_t block_id, uint32_t flags, uint32_t dflags,
-                                  uint32_t dict_id, uint64_t base, const FrameRec* d_frec, uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream);
+                                  uint32_t dict_id, uint32_t linked, uint64_t base, const FrameRec* d_frec,
+                                  uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream);
 
 }  // namespace lz4ada

@@ -314,6 +314,9 @@ _sig = {
     "lz4ada_compress_frames_bound_dict": ([_vp, _i64, _vp, _vp], _i64),
     "lz4ada_compress_frames_device_dict": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
     "lz4ada_compress_block_dict_host": ([_vp, _i64, _vp, _i64, _vp, _i64], _i64),
+    "lz4ada_compress_frames_device_linked": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_compress_frame_linked_host": ([_vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _i64],
+                                          _i64),
     "lz4ada_compress_frame_dict_host": ([_vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _i64],
                                         _i64),
     "lz4ada_abi_version": ([], ctypes.c_int),
@@ -893,7 +896,7 @@ def compress_frames_bound(lens, block=65536, block_checksum=False, content_check
 
 def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0, block=65536,
                            block_checksum=False, content_checksum=False, content_size=False, dict=None,
-                           dict_id=None):
+                           dict_id=None, linked=False):
     """Compress the records at spans [(in_off, in_len)] of the device buffer
     d_in into LZ4 frames laid back to back into the device buffer d_out (raw
     pointers) -> (bytes written, the CompressJob array: out_off, out_len,
@@ -902,12 +905,19 @@ def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: i
     of device memory, the dictionary every frame shares
     (lz4ada_compress_frames_device_dict; decode_frames_device with the same
     dictionary reads the frames); dict_id: when given, every header carries
-    it, None writes none."""
+    it, None writes none.  linked: frames of linked blocks
+    (lz4ada_compress_frames_device_linked): a block after a
+    record's first is compressed against the 65,536 bytes in front of it;
+    decode_frames_device(linked=True) reads the frames."""
     opt = _compress_options(block, block_checksum, content_checksum, content_size)
     jobs = _compress_jobs(spans)
     n = _i64()
     cd = _compress_dict(dict, dict_id)
-    if cd is None:
+    if linked:
+        st = _lib.lz4ada_compress_frames_device_linked(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
+                                                       None if cd is None else ctypes.byref(cd), d_out, out_cap,
+                                                       ctypes.byref(n), stream)
+    elif cd is None:
         st = _lib.lz4ada_compress_frames_device(d_in, in_len, jobs, len(spans), ctypes.byref(opt), d_out, out_cap,
                                                 ctypes.byref(n), stream)
     else:
@@ -921,14 +931,14 @@ def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: i
 
 
 def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False, content_checksum=False,
-                           content_size=False, dict=None, dict_id=None):
+                           content_size=False, dict=None, dict_id=None, linked=False):
     """compress_frames_device for a CUDA torch.uint8 tensor holding the
     records, on torch's current stream -> (the frames as a uint8 tensor on the
     same device, [(off, len)] of every record's frame inside it).  out: a uint8
     tensor there to write into; by default one of compress_frames_bound bytes
     is allocated.  dict: a CUDA uint8 tensor on the same device holding the
     dictionary every frame shares; dict_id: when given, written into every
-    header."""
+    header.  linked: frames of linked blocks, as compress_frames_device's."""
     if torch is None:
         raise RuntimeError("compress_frames_tensor needs torch")
     if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
@@ -946,7 +956,7 @@ def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False
         elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8 and out.is_contiguous()):
             raise ValueError("out must be a contiguous CUDA uint8 tensor on the records' device")
         n, jobs = compress_frames_device(t.data_ptr() if t.numel() else None, t.numel(), spans, out.data_ptr(),
-                                         out.numel(), torch.cuda.current_stream().cuda_stream, **kw)
+                                         out.numel(), torch.cuda.current_stream().cuda_stream, linked=linked, **kw)
     return out[:n], [(jobs[i].out_off, jobs[i].out_len) for i in range(len(spans))]
 
 
@@ -970,19 +980,25 @@ def compress_block_host(data, cap=None, dict=b"") -> bytes:
 
 
 def compress_frame_host(data, block=65536, block_checksum=False, content_checksum=False, content_size=False,
-                        cap=None, dict=b"", dict_id=None) -> bytes:
+                        cap=None, dict=b"", dict_id=None, linked=False) -> bytes:
     """The serial statement of one frame (no GPU involved): the bytes
     compress_frames_device writes for this record.  cap: the destination's
     size (default: the bound); below the bound: TooLittleMemory.  dict
     (bytes), dict_id: the dictionary and the id of that call
-    (lz4ada_compress_frame_dict_host)."""
+    (lz4ada_compress_frame_dict_host).  linked: the frame of linked blocks of
+    compress_frames_device(linked=True) (lz4ada_compress_frame_linked_host)."""
     data, dict = bytes(data), bytes(dict)
     opt = _compress_options(block, block_checksum, content_checksum, content_size)
     if cap is None:
         cap = compress_frames_bound([len(data)], block, block_checksum, content_checksum, content_size,
                                     dict_id=dict_id)
     buf = ctypes.create_string_buffer(max(cap, 1))
-    if dict or dict_id is not None:
+    if linked:
+        n = int(_lib.lz4ada_compress_frame_linked_host(_addr(data) if data else None, len(data), ctypes.byref(opt),
+                                                       _addr(dict) if dict else None, len(dict),
+                                                       0 if dict_id is None else dict_id,
+                                                       0 if dict_id is None else COMP_DICT_WRITE_ID, buf, cap))
+    elif dict or dict_id is not None:
         n = int(_lib.lz4ada_compress_frame_dict_host(_addr(data) if data else None, len(data), ctypes.byref(opt),
                                                      _addr(dict) if dict else None, len(dict),
                                                      0 if dict_id is None else dict_id,

@@ -1089,6 +1089,55 @@ int64_t lz4ada_compress_frame_dict_host(const uint8_t *src, int64_t n,
                                         int64_t dict_len, uint32_t dict_id, uint32_t dict_flags,
                                         uint8_t *dst, int64_t cap);
 
+/* ------------------- records compressed into frames of linked blocks, on the device */
+/*
+ * lz4ada_compress_frames_device_dict writing frames of linked blocks, the
+ * LZ4F default: FLG bit 5 (B.Indep) is clear, and
+ * block i >= 1 of a record is compressed with the 65,536 bytes of its own
+ * record in front of it, so its matches may begin there -- a record that
+ * repeats itself across a block boundary, or ends in a short block, no longer
+ * pays for the boundary.  Block 0 is compressed against the dictionary's tail,
+ * or against nothing, and its bytes are exactly the unlinked call's; from block
+ * 1 on the dictionary has slid out of the 64 KiB window and is not read,
+ * as in LZ4F_compressFrame_usingCDict.  A record of at most one block yields
+ * the unlinked frame with B.Indep clear (and so another HC) and nothing else
+ * different.  The history is read from d_in: a block's lies wholly inside its
+ * own record, so jobs may overlap and come in any order as before.
+ *
+ * dict may be NULL (no dictionary); otherwise it is the dictionary call's in
+ * every respect.  The contract is lz4ada_compress_frames_device_dict's word
+ * for word: the same misuse is LZ4ADA_ASSERTION_ERROR before any launch,
+ * out_cap below lz4ada_compress_frames_bound_dict(jobs, njobs, opt, dict) --
+ * the bound of this call too -- is LZ4ADA_TOO_LITTLE_MEMORY with *out_len set
+ * to the bound and d_out untouched, the frames lie dense in job order, nothing
+ * at or beyond d_out + *out_len is written, and the host synchronises `stream`
+ * once per pass.  opt->flags stays closed: linking is this entry, not a flag.
+ * A pass without a block i >= 1 queues exactly the launches of the unlinked
+ * call.
+ *
+ * The frames decode through the calls that take linked frames:
+ * lz4ada_decode_frame_dict_host, lz4ada_decode_frames_device(_dict) with
+ * LZ4ADA_FRAMES_LINKED, a seek index built with LZ4ADA_SEEK_LINKED, and liblz4.
+ * A linked frame may carry offsets of 65,529 and more across a block boundary.
+ * A decoder with the reference's quirk D1 -- the
+ * reference itself, the oracle, lz4ada_decode_frame and the facade -- may read
+ * such a frame differently from the specification, as it may liblz4's own
+ * linked frames.
+ *
+ * lz4ada_compress_frame_linked_host states one record serially: the device
+ * call's bytes for a job are its bytes for that record.  It is
+ * lz4ada_compress_frame_dict_host with the history of block i >= 1 replaced;
+ * dict may be NULL with dict_len 0.  Host only, no HIP call.
+ */
+int lz4ada_compress_frames_device_linked(const void *d_in, int64_t in_len, lz4ada_compress_job *jobs,
+                                         int64_t njobs, const lz4ada_compress_options *opt,
+                                         const lz4ada_compress_dict *dict, void *d_out,
+                                         int64_t out_cap, int64_t *out_len, void *stream);
+int64_t lz4ada_compress_frame_linked_host(const uint8_t *src, int64_t n,
+                                          const lz4ada_compress_options *opt, const uint8_t *dict,
+                                          int64_t dict_len, uint32_t dict_id, uint32_t dict_flags,
+                                          uint8_t *dst, int64_t cap);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
