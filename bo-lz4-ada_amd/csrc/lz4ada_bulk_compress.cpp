@@ -102,14 +102,8 @@ void compress_pass(const char* ENTRY, const uint8_t* d_in, lz4ada_compress_job* 
 	HIP_OK(hipMemsetAsync(d_rec, 0, rec_b, stream));
 	if (cck)  // over the records where they lie; the longer ones are the host chain's
 		HIP_OK(launch_xxh32_spans(d_in, d_frec, nj, hash_max, stream));
-	if (cont)  // every block of the pass, each with the history its place gives it (read from d_in)
-		HIP_OK(launch_compress_blocks_linked(d_in, d_blk, d_jobs, nb, dict.d_tail, dict.dl, dict.d_seed, d_slots,
-		                                     d_csize, stream));
-	else if (dict.dl)
-		HIP_OK(launch_compress_blocks_dict(d_in, d_blk, nb, dict.d_tail, dict.dl, dict.d_seed, d_slots, d_csize,
-		                                   stream));
-	else
-		HIP_OK(launch_compress_blocks(d_in, d_blk, nb, d_slots, d_csize, stream));
+	HIP_OK(launch_compress_blocks(d_in, d_blk, d_jobs, nb, cont, dict.d_tail, dict.dl, dict.d_seed, d_slots, d_csize,
+	                              stream));
 	HIP_OK(launch_compress_scan(d_blk, d_csize, nb, flags, d_loc, d_part, stream));
 	HIP_OK(launch_compress_emit(d_in, d_slots, d_blk, d_csize, d_loc, d_part, d_jobs, nb, flags, dict.dflags, *base,
 	                            d_out, d_desc, d_rec, stream));

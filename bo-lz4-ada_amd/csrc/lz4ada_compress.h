@@ -1,8 +1,11 @@
 // lz4ada_compress.h -- what the three statements of the compressor share
 // (DESIGN.md §17): the frame arithmetic and the header bytes, as host/device
 // code, and the matching rule's constants.  lz4ada_compress_host.cpp states
-// the rule serially, k_compress_blocks (lz4ada_compress.hip) runs it with one
-// wave per block, lz4ada_bulk_compress.cpp lays the jobs out.
+// the rule serially, in one compress_block that a dictionary or a linked
+// record calls with another history; lz4ada_compress_block.inc is its 64-lane
+// reading, one device body with one wave per block, compiled once per history
+// as k_compress_blocks, k_compress_blocks_dict and k_compress_blocks_linked;
+// lz4ada_bulk_compress.cpp lays the jobs out.
 //
 // Depends on lz4ada_hip.h and lz4ada_frame_walk.h alone, so a plain C++ program
 // can include it (tools/compress_host_asan.cpp).

@@ -1,12 +1,10 @@
 // lz4ada_compress.hip -- gfx950 kernels that compress device-resident records
 // into LZ4 frames (lz4ada_bulk_compress.cpp):
-//  * k_compress_blocks -- one wave per block, the matching rule of
-//    lz4ada_compress_host.cpp read 64 positions at a time: the window's lookups
-//    are one LDS read per lane, the lowest valid lane is a ballot, the inserts
-//    are ds_max_u32 (two lanes with one hash: the higher position stays, as
-//    the serial loop's later store), the match is extended 256 bytes per step.
-//    The block goes into a scratch slot of its own; a block that would not
-//    come out shorter than it went in stops there and is marked stored;
+//  * k_compress_blocks -- one wave per block: the one device body
+//    (lz4ada_compress_block.inc, the matching rule of lz4ada_compress_host.cpp
+//    read 64 positions at a time) with nothing in front of the block,
+//    CompHist::None.  The block goes into a scratch slot of its own; a block
+//    that would not come out shorter than it went in is marked stored;
 //  * k_compress_scan_tiles / k_compress_scan_carry -- the exclusive prefix sum
 //    of the blocks' bytes in the output (size word, payload, checksum), two
 //    levels as in lz4ada_frames.hip;
@@ -16,7 +14,8 @@
 //  * k_compress_block_cksums -- the block checksums behind the payloads;
 //  * k_compress_frames -- a thread per job writes the header, the end mark and
 //    the content checksum k_xxh32_spans left, and the job's place and length.
-// A dictionary call compresses its blocks with
+// launch_compress_blocks picks the pass's kernel of that one body: a
+// dictionary call compresses its blocks with
 // k_compress_blocks_dict (lz4ada_compress_dict.hip) and shares the rest; its
 // dflags / dict_id reach the emit and the header for the 4 bytes of the id.
 // A linked call compresses a pass that holds a continuation
@@ -27,9 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lz4ada_compress.h"
-#include "lz4ada_dev.h"
-#include "lz4ada_internal.h"
+#include "lz4ada_compress_block.h"
 
 namespace lz4ada {
 
@@ -45,124 +42,18 @@ __device__ __forceinline__ uint64_t comp_off(const uint64_t* loc, const uint64_t
 	return b < nblocks ? part[b / PLAN_TILE] + loc[b] : part[plan_tiles(nblocks)];
 }
 
-// 255* and the rest of a length v >= 15 at dst[o ..) -> the bytes written
-// (comp_ext_len(v)); the caller has checked them against the slot's end.
-__device__ __forceinline__ int32_t put_ext(g8* dst, int32_t o, int32_t v, uint32_t lane)
-{
-	if (v < 15)
-		return 0;
-	const int32_t k = (v - 15) / 255;
-	for (int32_t i = int32_t(lane); i < k; i += 64)
-		dst[o + i] = 255;
-	if (lane == 0)
-		dst[o + k] = uint8_t((v - 15) - 255 * k);
-	return k + 1;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(64) void k_compress_blocks(const uint8_t* __restrict__ d_in,
                                                          const CompBlock* __restrict__ blk, uint32_t nblocks,
                                                          uint8_t* __restrict__ slots, uint32_t* __restrict__ csize)
 {
-	__shared__ uint32_t table[COMP_TABLE];  // position + 1; 0: none
-	const uint32_t b = blockIdx.x;
-	if (b >= nblocks)
-		return;
-	const uint32_t lane = lane_id();
-	const uint64_t in_off = wave_uniform(blk[b].in_off), slot_off = wave_uniform(blk[b].slot_off);
-	const int32_t n = wave_uniform(int32_t(blk[b].len));
-	cg8* const src = gptr(d_in) + in_off;
-	g8* const dst = gptr(slots) + slot_off;
-	const int32_t cap = n - 1;  // compressed only when shorter than the block; the slot holds n bytes
-	for (uint32_t i = lane; i < COMP_TABLE; i += 64)
-		table[i] = 0;
-	__syncthreads();
-	int32_t op = 0, anchor = 0;
-	bool stored = false;
-	if (n >= COMP_MIN_BLOCK) {
-		const int32_t mlast = n - int32_t(COMP_MFLIMIT), mend = n - int32_t(COMP_LAST_LITERALS);
-		int32_t w = 0;
-		while (w <= mlast) {  // every turn moves w on by a window or a match
-			const int32_t wn = min(mlast - w + 1, int32_t(COMP_WINDOW));
-			const int32_t p = w + int32_t(lane);
-			const bool active = int32_t(lane) < wn;
-			const uint32_t v = active ? ld32u_cached(src + p) : 0u;
-			const uint32_t h = comp_hash(v);
-			const uint32_t e = active ? table[h] : 0u;  // read before any position of the window is inserted
-			bool ok = e != 0 && p - int32_t(e - 1) <= int32_t(COMP_MAX_OFF);
-			if (ok)
-				ok = ld32u_cached(src + (e - 1)) == v;
-			const uint64_t won = __ballot(ok);
-			const int32_t wl = won ? int32_t(__builtin_ctzll(won)) : wn - 1;
-			if (active && int32_t(lane) <= wl)
-				atomicMax(&table[h], uint32_t(p + 1));
-			wave_lds_fence();
-			if (!won) {
-				w += wn;
-				continue;
-			}
-			const int32_t win = w + wl;
-			const int32_t cand = wave_uniform(int32_t(__shfl(e, wl))) - 1;
-			// the match's length: 4 bytes per lane, the first lane with a
-			// mismatch or at the end (n - 5) ends it
-			int32_t ml = 4;
-			for (;;) {
-				const int32_t q = win + ml + 4 * int32_t(lane);
-				const int32_t rem = mend - q;  // bytes of this lane's four the match may still take
-				uint32_t x = 1;
-				if (rem > 0) {
-					x = ld32u_cached(src + q) ^ ld32u_cached(src + (cand + ml + 4 * int32_t(lane)));
-					if (rem < 4)
-						x |= 1u << (8 * rem);
-				}
-				const int32_t same = x ? int32_t(__builtin_ctz(x) >> 3) : 4;
-				const uint64_t ends = __ballot(same < 4);
-				if (ends) {
-					const int32_t fl = int32_t(__builtin_ctzll(ends));
-					ml += 4 * fl + wave_uniform(int32_t(__shfl(same, fl)));
-					break;
-				}
-				ml += 256;
-			}
-			const int32_t lit = win - anchor;
-			if (op + int32_t(comp_seq_len(lit, ml)) > cap) {
-				stored = true;
-				break;
-			}
-			if (lane == 0)
-				dst[op] = uint8_t((min(lit, 15) << 4) | min(ml - 4, 15));
-			int32_t o = op + 1;
-			o += put_ext(dst, o, lit, lane);
-			for (int32_t i = int32_t(lane); i < lit; i += 64)
-				dst[o + i] = src[anchor + i];
-			o += lit;
-			if (lane == 0) {
-				dst[o] = uint8_t(win - cand);
-				dst[o + 1] = uint8_t((win - cand) >> 8);
-			}
-			o += 2;
-			o += put_ext(dst, o, ml - 4, lane);
-			op = o;
-			w = anchor = win + ml;
-		}
-	}
-	if (!stored) {
-		const int32_t lit = n - anchor;
-		if (op + int32_t(comp_last_len(lit)) > cap) {
-			stored = true;
-		} else {
-			if (lane == 0)
-				dst[op] = uint8_t(min(lit, 15) << 4);
-			int32_t o = op + 1;
-			o += put_ext(dst, o, lit, lane);
-			for (int32_t i = int32_t(lane); i < lit; i += 64)
-				dst[o + i] = src[anchor + i];
-			op = o + lit;
-		}
-	}
-	if (lane == 0)
-		csize[b] = stored ? 0u : uint32_t(op);
+	constexpr CompHist H = CompHist::None;
+	constexpr const CompJob* jobs = nullptr;  // what only a history reads: named, never used
+	constexpr const uint8_t* d_tail = nullptr;
+	constexpr uint32_t dict_len = 0;
+	constexpr const uint32_t* seed = nullptr;
+#include "lz4ada_compress_block.inc"
 }
 
 // Level 1: tile-relative exclusive offsets into loc[], the tile's total into
@@ -319,13 +210,21 @@ __global__ __launch_bounds__(COMP_WG) void k_compress_frames(const CompJob* __re
 	rec[j].out_len = uint64_t(hn) + body + uint64_t(comp_trailer_len(flags));
 }
 
-hipError_t launch_compress_blocks(const uint8_t* d_in, const CompBlock* d_blk, uint32_t nblocks, uint8_t* d_slots,
-                                  uint32_t* d_csize, hipStream_t stream)
+hipError_t launch_compress_blocks(const uint8_t* d_in, const CompBlock* d_blk, const CompJob* d_jobs, uint32_t nblocks,
+                                  bool cont, const uint8_t* d_tail, uint32_t dl, const uint32_t* d_seed,
+                                  uint8_t* d_slots, uint32_t* d_csize, hipStream_t stream)
 {
 	if (nblocks == 0)
 		return hipSuccess;
-	hipLaunchKernelGGL(k_compress_blocks, dim3(nblocks), dim3(64), 0, stream, d_in, d_blk, nblocks, d_slots,
-	                   d_csize);
+	if (cont)  // every block of the pass, each with the history its place gives it (read from d_in)
+		hipLaunchKernelGGL(k_compress_blocks_linked, dim3(nblocks), dim3(64), 0, stream, d_in, d_blk, d_jobs, nblocks,
+		                   d_tail, dl, d_seed, d_slots, d_csize);
+	else if (dl)
+		hipLaunchKernelGGL(k_compress_blocks_dict, dim3(nblocks), dim3(64), 0, stream, d_in, d_blk, nblocks, d_tail, dl,
+		                   d_seed, d_slots, d_csize);
+	else
+		hipLaunchKernelGGL(k_compress_blocks, dim3(nblocks), dim3(64), 0, stream, d_in, d_blk, nblocks, d_slots,
+		                   d_csize);
 	return hipGetLastError();
 }
 

@@ -618,29 +618,27 @@ struct CompJobRec {
 };
 // One wave per block: block b compressed into its slot, d_csize[b] its length
 // there, or 0 for a block to be stored (the compressed form would not be
-// shorter).  Writes inside [slot_off, slot_off + len - 1) only.
-hipError_t launch_compress_blocks(const uint8_t* d_in, const CompBlock* d_blk, uint32_t nblocks, uint8_t* d_slots,
-                                  uint32_t* d_csize, hipStream_t stream);
-// The exclusive prefix sum of the blocks' bytes in the output (size word,
-// payload, checksum under `flags`): block b's is d_part[b / PLAN_TILE] +
-// d_loc[b], the total d_part[plan_tiles(nblocks)].  nblocks may be 0.
-// The same against a dictionary (lz4ada_compress_dict.hip): dl
-// bytes (4 .. 65,536) at d_tail lie in front of every block, d_seed is their
-// table as launch_compress_dict_table left it.  Reads d_tail inside [0, dl).
-hipError_t launch_compress_blocks_dict(const uint8_t* d_in, const CompBlock* d_blk, uint32_t nblocks,
-                                       const uint8_t* d_tail, uint32_t dl, const uint32_t* d_seed, uint8_t* d_slots,
-                                       uint32_t* d_csize, hipStream_t stream);
+// shorter).  Writes inside [slot_off, slot_off + len - 1) only.  The pass's
+// history picks the kernel (lz4ada_compress_block.inc):
+//  * dl == 0, no cont: k_compress_blocks, nothing in front of a block; d_jobs,
+//    d_tail and d_seed are not read;
+//  * dl != 0, no cont: k_compress_blocks_dict: dl bytes
+//    (4 .. 65,536) at d_tail lie in front of every block, d_seed is their table
+//    as launch_compress_dict_table left it.  Reads d_tail inside [0, dl);
+//  * cont, a linked pass that holds a continuation block:
+//    k_compress_blocks_linked.  Block b begins its record when
+//    its in_off is d_jobs[d_blk[b].job].in_off and is then compressed as above
+//    (dl == 0: no dictionary); any other block has the 65,536 bytes in front of
+//    it in d_in as its history and seeds its own table from them.
+hipError_t launch_compress_blocks(const uint8_t* d_in, const CompBlock* d_blk, const CompJob* d_jobs, uint32_t nblocks,
+                                  bool cont, const uint8_t* d_tail, uint32_t dl, const uint32_t* d_seed,
+                                  uint8_t* d_slots, uint32_t* d_csize, hipStream_t stream);
 // d_seed[0 .. COMP_TABLE): for every hash the last position + 1 of d_tail[0 .. dl)
 // whose four bytes lie inside it, 0 for none (dl < 4: all 0).
 hipError_t launch_compress_dict_table(const uint8_t* d_tail, uint32_t dl, uint32_t* d_seed, hipStream_t stream);
-// The blocks of linked frames (lz4ada_compress_linked.hip):
-// block b begins its record when its in_off is d_jobs[d_blk[b].job].in_off and
-// is then compressed as by the two launches above (dl == 0: no dictionary,
-// d_tail and d_seed are not read); any other block has the 65,536 bytes in
-// front of it in d_in as its history and seeds its own table from them.
-hipError_t launch_compress_blocks_linked(const uint8_t* d_in, const CompBlock* d_blk, const CompJob* d_jobs,
-                                         uint32_t nblocks, const uint8_t* d_tail, uint32_t dl, const uint32_t* d_seed,
-                                         uint8_t* d_slots, uint32_t* d_csize, hipStream_t stream);
+// The exclusive prefix sum of the blocks' bytes in the output (size word,
+// payload, checksum under `flags`): block b's is d_part[b / PLAN_TILE] +
+// d_loc[b], the total d_part[plan_tiles(nblocks)].  nblocks may be 0.
 hipError_t launch_compress_scan(const CompBlock* d_blk, const uint32_t* d_csize, uint32_t nblocks, uint32_t flags,
                                 uint64_t* d_loc, uint64_t* d_part, hipStream_t stream);
 // One workgroup per block: size word and payload into d_out (the pass begins
