@@ -166,6 +166,36 @@ package LZ4Ada.GPU is
 			return Interfaces.Integer_32;
 	pragma Import(C, Decode_Frame_Dict_Host, "lz4ada_decode_frame_dict_host");
 
+	-- lz4ada_compress_frames_device_indexed: records that lie in device
+	-- memory compressed into LZ4 frames there, with the frames' seek index
+	-- written by the same call (lz4ada_compress_index_options of
+	-- include/lz4ada_hip.h; no reference twin).  The thin import, in the
+	-- style of the dictionary calls above: Jobs is the address of the first
+	-- of N_Jobs lz4ada_compress_job records, Opt that of an
+	-- lz4ada_compress_options (null: 64 KiB blocks, no flag), Dict may be
+	-- null, X_Opt may be null (frames of independent blocks), Frames is null
+	-- or the address of a Device_Frame_Jobs' first element, Idx receives the
+	-- index (an lz4ada_seek_index, to be handed to the ranged decode and
+	-- freed with lz4ada_seek_index_free).  The result is the status of the
+	-- call (0, or 5: Too_Little_Memory with Out_Len the bound, or 6: misuse;
+	-- Idx is then null).
+	Comp_Index_Linked: constant Interfaces.Unsigned_32 := 1;
+	type Compress_Index_Options is record
+		Flags:            Interfaces.Unsigned_32;
+		Reserved:         Interfaces.Unsigned_32 := 0;
+		Checkpoint_Bytes: Interfaces.Integer_64 := 0;
+	end record;
+	pragma Convention(C, Compress_Index_Options);
+	function Compress_Frames_Device_Indexed(D_In: System.Address; In_Len: Interfaces.Integer_64;
+			Jobs: System.Address; N_Jobs: Interfaces.Integer_64;
+			Opt: System.Address; Dict: System.Address;
+			X_Opt: access constant Compress_Index_Options;
+			D_Out: System.Address; Out_Cap: Interfaces.Integer_64;
+			Out_Len: access Interfaces.Integer_64; Frames: System.Address;
+			Idx: access System.Address; Stream: System.Address)
+			return Interfaces.Integer_32;
+	pragma Import(C, Compress_Frames_Device_Indexed, "lz4ada_compress_frames_device_indexed");
+
 	-- lz4ada_rccl_version: the RCCL this process bound (22606 = 2.26.6).
 	function RCCL_Version return Interfaces.Integer_32;
 	pragma Import(C, RCCL_Version, "lz4ada_rccl_version");

@@ -33,8 +33,16 @@
 // all kinds -- from a checkpoint, from the dictionary -- in one launch that
 // takes the history length per chain (k_decode_idx_chains).  Legacy frames keep
 // launch_decode_checked.
+//
+// An index may also come from the compress call that wrote the frames
+// (lz4ada_compress_frames_device_indexed): comp_index_open / _pass
+// / _close below fill the same object from what the writer knows, through the
+// allocation layouts and the dictionary image the builds use (alloc_index,
+// alloc_checkpoints, lay_dict_image), and the ranged calls cannot tell the two
+// apart.
 #include <climits>
 
+#include "lz4ada_compress_index.h"
 #include "lz4ada_host_common.h"
 #include "lz4ada_range_blocks.h"
 #include "lz4ada_range_chains.h"
@@ -472,6 +480,70 @@ void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* 
 	}
 }
 
+// The index's own dictionary, queued on s: the gap every pass copies, zeros and
+// then the last `used` bytes of the caller's (an allocation: 256-aligned).  For
+// the builds and for the index a compress call writes; dict_len > 0.
+void lay_dict_image(lz4ada_seek_index& x, const void* d_dict, int64_t dict_len, hipStream_t s)
+{
+	const uint32_t used = uint32_t(std::min<uint64_t>(uint64_t(dict_len), DICT_MAX));
+	const uint64_t gap = dict_gap(used);
+	uint8_t* const img = x.dict_mem.alloc(size_t(gap), "the seek index's dictionary");
+	x.dict = DictCtx{ img, gap, used, gap };
+	const size_t zeros = size_t(gap) - used;
+	HIP_OK(hipMemsetAsync(img, 0, zeros, s));
+	HIP_OK(hipMemcpyAsync(img + zeros, static_cast<const uint8_t*>(d_dict) + (uint64_t(dict_len) - used), used,
+	                      hipMemcpyDeviceToDevice, s));
+	x.view.dict = img;
+	x.view.dict_used = used;
+}
+
+// What the index keeps of nb blocks in n > 0 frames, allocated and named in its
+// view: 32 bytes per block, 16 for its two prefixes, 24 per frame (first, and
+// the prefixes' end entries), and with a dictionary (lay_dict_image comes
+// first) 8 more per frame: its kind.
+struct IndexArrays {
+	lz4ada_block_desc* d_desc;
+	uint64_t *d_first, *d_slotp, *d_kind;
+};
+IndexArrays alloc_index(lz4ada_seek_index& x, uint64_t nb, size_t n)
+{
+	const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), first_b = (n + 1) * 8,
+	             pre_b = (size_t(nb) + n) * 8, kind_b = x.dict.used ? n * 8 : 0;
+	uint8_t* const m = x.mem.alloc(desc_b + first_b + 2 * pre_b + kind_b, "the seek index");
+	IndexArrays a;
+	a.d_desc = reinterpret_cast<lz4ada_block_desc*>(m);
+	a.d_first = reinterpret_cast<uint64_t*>(m + desc_b);
+	x.d_start = reinterpret_cast<uint64_t*>(m + desc_b + first_b);
+	a.d_slotp = reinterpret_cast<uint64_t*>(m + desc_b + first_b + pre_b);
+	a.d_kind = x.dict.used ? reinterpret_cast<uint64_t*>(m + desc_b + first_b + 2 * pre_b) : nullptr;
+	x.view.desc = a.d_desc;
+	x.view.first = a.d_first;
+	x.view.start = x.d_start;
+	x.view.slotp = a.d_slotp;
+	x.view.nframes = uint32_t(n);
+	x.view.fkind = a.d_kind;
+	return a;
+}
+
+// The checkpoints of a linked index over n > 0 frames: store | ckfirst | kgrp.
+struct CkptArrays {
+	uint8_t* d_store;
+	uint64_t *d_ckfirst, *d_kgrp;
+};
+CkptArrays alloc_checkpoints(lz4ada_seek_index& x, uint64_t nck, size_t n)
+{
+	const size_t store_b = size_t(nck) * CKPT_BYTES, ckf_b = (n + 1) * 8, kg_b = n * 8;
+	CkptArrays c;
+	c.d_store = x.ck.alloc(store_b + ckf_b + kg_b, "the seek index's checkpoints");
+	c.d_ckfirst = reinterpret_cast<uint64_t*>(c.d_store + store_b);
+	c.d_kgrp = c.d_ckfirst + n + 1;
+	x.view.kgrp = c.d_kgrp;
+	x.view.ckfirst = c.d_ckfirst;
+	x.view.store = c.d_store;
+	x.view.nckpt = nck;
+	return c;
+}
+
 // The one body of the builds.  linked: LZ4ADA_SEEK_LINKED, with a checkpoint
 // every `every` decoded bytes.  dict: null, or a dictionary of dict_len > 0 that
 // check_dict has passed.
@@ -486,20 +558,8 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 	std::unique_ptr<lz4ada_seek_index> x(new lz4ada_seek_index);
 	const size_t n = ix.order.size();
 	x->in_len = in_len;
-	if (dict && n) {
-		// the index's own dictionary, as the gap every pass copies: zeros, then
-		// its last `used` bytes (an allocation: 256-aligned)
-		const uint32_t used = uint32_t(std::min<uint64_t>(uint64_t(dict->dict_len), DICT_MAX));
-		const uint64_t gap = dict_gap(used);
-		uint8_t* const img = x->dict_mem.alloc(size_t(gap), "the seek index's dictionary");
-		x->dict = DictCtx{ img, gap, used, gap };
-		const size_t zeros = size_t(gap) - used;
-		HIP_OK(hipMemsetAsync(img, 0, zeros, s));
-		HIP_OK(hipMemcpyAsync(img + zeros, static_cast<const uint8_t*>(dict->d_dict) + (uint64_t(dict->dict_len) - used),
-		                      used, hipMemcpyDeviceToDevice, s));
-		x->view.dict = img;
-		x->view.dict_used = used;
-	}
+	if (dict && n)
+		lay_dict_image(*x, dict->d_dict, dict->dict_len, s);
 	if (linked && n) {
 		// the checkpoints of every linked frame the sizes stage accepted, and the
 		// linked frames decoded once into them
@@ -511,17 +571,10 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 				x->kgrp[k] = chain_group(every, chain_block_max(ix.walk[k].nblocks, ix.size[k].exact));
 			x->ckfirst[k + 1] = x->ckfirst[k] + (lk ? chain_checkpoints(x->kgrp[k], ix.walk[k].nblocks) : 0);
 		}
-		const uint64_t nck = x->ckfirst[n];
-		const size_t store_b = size_t(nck) * CKPT_BYTES, ckf_b = (n + 1) * 8, kg_b = n * 8;
-		uint8_t* const c = x->ck.alloc(store_b + ckf_b + kg_b, "the seek index's checkpoints");
-		uint64_t* const d_ckfirst = reinterpret_cast<uint64_t*>(c + store_b);
-		uint64_t* const d_kgrp = d_ckfirst + n + 1;
+		const CkptArrays c = alloc_checkpoints(*x, x->ckfirst[n], n);
 		// (which also sends the two arrays up, from pinned memory with its records)
-		decode_linked_frames(ix, *x, c, d_ckfirst, d_kgrp, static_cast<const uint8_t*>(d_in), uint64_t(in_len), s);
-		x->view.kgrp = d_kgrp;
-		x->view.ckfirst = d_ckfirst;
-		x->view.store = c;
-		x->view.nckpt = nck;
+		decode_linked_frames(ix, *x, c.d_store, c.d_ckfirst, c.d_kgrp, static_cast<const uint8_t*>(d_in),
+		                     uint64_t(in_len), s);
 	}
 	report_sizes(ix, jobs);
 	x->pos.resize(n);
@@ -545,25 +598,14 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 		*idx = x.release();
 		return;
 	}
-	// what the index keeps: 32 bytes per block, 16 for its two prefixes,
-	// 24 per frame (first, and the prefixes' end entries), and with a dictionary
-	// 8 more per frame: its kind
-	const size_t desc_b = size_t(nb) * sizeof(lz4ada_block_desc), first_b = (n + 1) * 8,
-	             pre_b = (size_t(nb) + n) * 8, kind_b = x->dict.used ? n * 8 : 0;
-	uint8_t* const m = x->mem.alloc(desc_b + first_b + 2 * pre_b + kind_b, "the seek index");
-	lz4ada_block_desc* const d_desc = reinterpret_cast<lz4ada_block_desc*>(m);
-	uint64_t* const d_first = reinterpret_cast<uint64_t*>(m + desc_b);
-	x->d_start = reinterpret_cast<uint64_t*>(m + desc_b + first_b);
-	uint64_t* const d_slotp = reinterpret_cast<uint64_t*>(m + desc_b + first_b + pre_b);
-	x->view.desc = d_desc;
-	x->view.first = d_first;
-	x->view.start = x->d_start;
-	x->view.slotp = d_slotp;
-	x->view.nframes = uint32_t(n);
+	const IndexArrays a = alloc_index(*x, nb, n);
+	lz4ada_block_desc* const d_desc = a.d_desc;
+	uint64_t *const d_first = a.d_first, *const d_slotp = a.d_slotp;
+	const size_t first_b = (n + 1) * 8, kind_b = x->dict.used ? n * 8 : 0;
 	if (x->dict.used) {
 		// which blocks read the dictionary, by the final verdicts: every block of
 		// an independent modern frame, block 0 of a linked one, none of a legacy one
-		uint64_t* const d_kind = reinterpret_cast<uint64_t*>(m + desc_b + first_b + 2 * pre_b);
+		uint64_t* const d_kind = a.d_kind;
 		x->kind.assign(n, uint8_t(CHAIN_KIND_NONE));
 		HIP_OK(hipStreamSynchronize(s));  // nothing may still read the pinned buffer
 		PinBuf& h = scratch_cache().pin;
@@ -575,7 +617,6 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 			w[k] = x->kind[k];
 		}
 		HIP_OK(hipMemcpyAsync(d_kind, w, kind_b, hipMemcpyHostToDevice, s));
-		x->view.fkind = d_kind;
 	}
 	FrameRec* const d_rec = reinterpret_cast<FrameRec*>(scratch(SC_BATCH_META, n * sizeof(FrameRec)));
 	if (!d_rec)
@@ -591,6 +632,158 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 	HIP_OK(hipStreamSynchronize(s));
 	*idx = x.release();
 }
+
+}  // namespace
+
+// ---- the index a compress call writes (lz4ada_bulk_compress.cpp) ----
+// The host knows every count before the first pass but one thing: whether a
+// frame of at most WALK_LONE_BLOCKS blocks of 1 or 4 MiB falls to the lone-block
+// rule, which asks for a written payload of WALK_LONE_MIN_IN bytes.  So the
+// index is laid out pass by pass: its two blocks are allocated for every frame
+// taken, each pass's kernels place its frames behind those of the passes
+// before (k_compress_index_frames), and the host replays the places from the
+// pass's records.  Only when the rule did turn a frame down are the arrays, by
+// then dense at the front of blocks that are too large, moved into exact ones.
+
+CompIndexSink::~CompIndexSink() { delete x; }
+
+uint64_t seek_checkpoint_every(int64_t checkpoint_bytes)
+{
+	return checkpoint_bytes ? uint64_t(checkpoint_bytes) : SEEK_CHECKPOINT_BYTES;
+}
+
+void comp_index_open(CompIndexSink& k, const lz4ada_compress_job* jobs, size_t n, uint32_t block_id, bool linked,
+                     int64_t checkpoint_bytes, const lz4ada_compress_dict* cdict, hipStream_t s)
+{
+	k.linked = linked;
+	k.every = seek_checkpoint_every(checkpoint_bytes);
+	k.no_lone = lone_blocks_disabled();
+	const bool dict = cdict && cdict->dict_len > 0;
+	k.kind = !dict ? CHAIN_KIND_NONE : linked ? CHAIN_KIND_LINKED : CHAIN_KIND_INDEP;
+	const uint64_t blen = uint64_t(comp_block_len(block_id));
+	uint64_t nb = 0, nck = 0;
+	for (size_t i = 0; i < n; ++i) {
+		const uint64_t b = uint64_t(comp_nblocks(jobs[i].in_len, int64_t(blen)));
+		nb += b;
+		if (linked && b)
+			nck += chain_checkpoints(chain_group(k.every, chain_block_max(b, uint64_t(jobs[i].in_len))), b);
+	}
+	if (nb >= (uint64_t(1) << 31))
+		raise(LZ4ADA_CONSTRAINT_ERROR, "the frames hold more blocks than a seek index takes");
+	std::unique_ptr<lz4ada_seek_index> x(new lz4ada_seek_index);
+	x->pos.resize(n);
+	for (size_t i = 0; i < n; ++i)
+		x->pos[i] = uint32_t(i);  // the frames lie in job order
+	x->reason.assign(n, LZ4ADA_DEVFRAME_OK);
+	x->size.assign(n, 0);
+	x->first.assign(n + 1, 0);
+	if (n) {
+		if (dict) {
+			lay_dict_image(*x, cdict->d_dict, cdict->dict_len, s);
+			x->kind.assign(n, uint8_t(CHAIN_KIND_NONE));
+		}
+		const IndexArrays a = alloc_index(*x, nb, n);
+		k.out = CompIndexOut{};
+		k.out.desc = a.d_desc;
+		k.out.first = a.d_first;
+		k.out.start = x->d_start;
+		k.out.slotp = a.d_slotp;
+		k.out.fkind = a.d_kind;
+		k.out.nblocks = nb;
+		k.out.nframes = uint32_t(n);
+		if (linked) {
+			x->kgrp.assign(n, 0);
+			x->ckfirst.assign(n + 1, 0);
+			const CkptArrays c = alloc_checkpoints(*x, nck, n);
+			k.out.kgrp = c.d_kgrp;
+			k.out.ckfirst = c.d_ckfirst;
+			k.out.store = c.d_store;
+			k.out.nckpt = nck;
+		}
+	}
+	k.x = x.release();
+}
+
+void comp_index_pass(CompIndexSink& k, const lz4ada_compress_job* jobs, size_t lo, size_t hi, uint32_t block_id,
+                     const CompIndexRec* rec)
+{
+	lz4ada_seek_index& x = *k.x;
+	const uint64_t blen = uint64_t(comp_block_len(block_id));
+	for (size_t f = lo; f < hi; ++f) {
+		const uint64_t n = uint64_t(jobs[f].in_len), nb = uint64_t(comp_nblocks(jobs[f].in_len, int64_t(blen)));
+		const bool taken = rec[f - lo].verdict == LZ4ADA_BATCH_OK;
+		x.reason[f] = rec[f - lo].verdict;
+		x.size[f] = taken ? n : 0;
+		x.first[f + 1] = x.first[f] + (taken ? nb : 0);
+		if (k.linked) {
+			x.kgrp[f] = taken && nb ? chain_group(k.every, chain_block_max(nb, n)) : 0;
+			x.ckfirst[f + 1] = x.ckfirst[f] + chain_checkpoints(x.kgrp[f], nb);
+			x.linked |= taken && nb > 0;
+		}
+		if (!x.kind.empty() && taken && nb)
+			x.kind[f] = uint8_t(k.kind);
+		// the places the kernels wrote by are the ones the ranged calls will read by
+		if (rec[f - lo].first != x.first[f] || (k.linked && rec[f - lo].ck != x.ckfirst[f]))
+			raise(LZ4ADA_CONSTRAINT_ERROR, "the seek index's places on the device are not the host's");
+	}
+	k.base = rec[hi - lo];
+	if (k.base.first != x.first[hi] || (k.linked && k.base.ck != x.ckfirst[hi]))
+		raise(LZ4ADA_CONSTRAINT_ERROR, "the seek index's places on the device are not the host's");
+}
+
+lz4ada_seek_index* comp_index_close(CompIndexSink& k, const lz4ada_compress_job* jobs, int64_t out_len,
+                                    lz4ada_device_frame_job* frames, hipStream_t s)
+{
+	lz4ada_seek_index& x = *k.x;
+	const size_t n = x.pos.size();
+	x.in_len = out_len;
+	const uint64_t nb = n ? x.first[n] : 0, nck = k.linked && n ? x.ckfirst[n] : 0;
+	if (n && (nb != k.out.nblocks || nck != k.out.nckpt)) {
+		// a frame fell to the lone-block rule: the arrays into blocks of the build's
+		// sizes (the passes are synchronised; this is the one more)
+		lz4ada_seek_index y;
+		y.dict = x.dict;  // (alloc_index reads whether there is a dictionary)
+		const IndexArrays a = alloc_index(y, nb, n);
+		const size_t pre_b = (size_t(nb) + n) * 8;
+		HIP_OK(hipMemcpyAsync(a.d_desc, k.out.desc, size_t(nb) * sizeof(lz4ada_block_desc), hipMemcpyDeviceToDevice, s));
+		HIP_OK(hipMemcpyAsync(a.d_first, k.out.first, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
+		HIP_OK(hipMemcpyAsync(y.d_start, k.out.start, pre_b, hipMemcpyDeviceToDevice, s));
+		HIP_OK(hipMemcpyAsync(a.d_slotp, k.out.slotp, pre_b, hipMemcpyDeviceToDevice, s));
+		if (a.d_kind)
+			HIP_OK(hipMemcpyAsync(a.d_kind, k.out.fkind, n * 8, hipMemcpyDeviceToDevice, s));
+		if (k.linked) {
+			const CkptArrays c = alloc_checkpoints(y, nck, n);
+			if (nck)
+				HIP_OK(hipMemcpyAsync(c.d_store, k.out.store, size_t(nck) * CKPT_BYTES, hipMemcpyDeviceToDevice, s));
+			HIP_OK(hipMemcpyAsync(c.d_ckfirst, k.out.ckfirst, (n + 1) * 8, hipMemcpyDeviceToDevice, s));
+			HIP_OK(hipMemcpyAsync(c.d_kgrp, k.out.kgrp, n * 8, hipMemcpyDeviceToDevice, s));
+		}
+		HIP_OK(hipStreamSynchronize(s));
+		std::swap(x.mem.p, y.mem.p);
+		std::swap(x.mem.bytes, y.mem.bytes);
+		std::swap(x.ck.p, y.ck.p);
+		std::swap(x.ck.bytes, y.ck.bytes);
+		const SeekView old = x.view;
+		x.view = y.view;
+		x.view.dict = old.dict;
+		x.view.dict_used = old.dict_used;
+		x.d_start = y.d_start;
+	}
+	for (size_t f = 0; frames && f < n; ++f) {
+		lz4ada_device_frame_job& j = frames[f];
+		j.in_off = jobs[f].out_off;
+		j.in_len = jobs[f].out_len;
+		j.out_off = j.consumed = 0;
+		j.out_len = int64_t(x.size[f]);
+		j.status = x.taken(f) ? LZ4ADA_OK : LZ4ADA_EXACT_PATH;
+		j.reason = x.reason[f];
+	}
+	lz4ada_seek_index* const r = k.x;
+	k.x = nullptr;
+	return r;
+}
+
+namespace {
 
 }  // namespace
 }  // namespace lz4ada
@@ -637,7 +830,7 @@ int seek_index_build_opt(const char* entry, const void* d_in, int64_t in_len, lz
 			misuse(entry, "opt->checkpoint_bytes is negative");
 		check_dict(entry, dict);
 		const bool linked = opt && (opt->flags & LZ4ADA_SEEK_LINKED);
-		const uint64_t every = opt && opt->checkpoint_bytes ? uint64_t(opt->checkpoint_bytes) : SEEK_CHECKPOINT_BYTES;
+		const uint64_t every = seek_checkpoint_every(opt ? opt->checkpoint_bytes : 0);
 		build_index(entry, d_in, in_len, jobs, njobs, linked, every, dict && dict->dict_len > 0 ? dict : nullptr, idx,
 		            static_cast<hipStream_t>(stream));
 	});
@@ -834,6 +1027,21 @@ int lz4ada_seek_index_debug(const lz4ada_seek_index* idx, int64_t job, int32_t* 
 		if (start_cap < int64_t(nb) + 1)
 			raise(LZ4ADA_CONSTRAINT_ERROR, "start capacity exceeded");
 		d2h(start, idx->d_start + idx->first[k] + k, (size_t(nb) + 1) * 8, static_cast<hipStream_t>(stream));
+	});
+}
+
+int lz4ada_seek_index_store_debug(const lz4ada_seek_index* idx, void* store, int64_t store_cap, int64_t* nckpt,
+                                  void* stream)
+{
+	return guarded(nullptr, [&] {
+		if (!idx || !nckpt)
+			misuse("lz4ada_seek_index_store_debug", "idx or nckpt is NULL");
+		*nckpt = int64_t(idx->view.nckpt);
+		if (!store || idx->view.nckpt == 0)
+			return;
+		if (store_cap < int64_t(idx->view.nckpt * CKPT_BYTES))
+			raise(LZ4ADA_CONSTRAINT_ERROR, "store capacity exceeded");
+		d2h(store, idx->view.store, size_t(idx->view.nckpt * CKPT_BYTES), static_cast<hipStream_t>(stream));
 	});
 }
 

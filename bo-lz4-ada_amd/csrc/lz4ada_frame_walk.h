@@ -122,6 +122,17 @@ LZ4ADA_HD inline uint32_t walk_slot_cap(uint32_t in_len, bool stored, int64_t bm
 	return uint32_t(grown < uint64_t(bmax) ? grown : uint64_t(bmax));
 }
 
+// The lone-block rule over a frame of nb blocks whose largest payload is max_in
+// (the numbers above), as the walk below ends with it; stated here for the
+// compressor's own index (lz4ada_compress_index.h), which knows its blocks
+// without walking them.  tests/test_compress_index_cpu.py pins the two to
+// each other.
+LZ4ADA_HD inline bool walk_lone(bool no_lone, int64_t nb, uint32_t max_in)
+{
+	return !no_lone && nb >= 1 && nb <= WALK_LONE_BLOCKS && max_in >= WALK_LONE_MIN_IN &&
+	       int64_t(max_in) <= WALK_LONE_MAX_IN;
+}
+
 // The frame at [p, p + len) under Single_Frame semantics (the frame and
 // whatever follows it).  Returns LZ4ADA_BATCH_OK for exactly the frames that
 // pass index_frame and leave classify as LZ4ADA_BATCH_OK (skippable ones

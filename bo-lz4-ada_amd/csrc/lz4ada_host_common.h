@@ -569,6 +569,35 @@ void fill_pass(const FramesIndex& ix, size_t lo, size_t hi, const uint8_t* d_in,
 void lay_dict_pass(PassArrays& m, const FramesIndex& ix, size_t lo, size_t hi, uint64_t total, uint64_t in_len,
                    const DictCtx& dc, uint64_t* h_kind, hipStream_t stream);
 
+// The seek index a compress call writes while it compresses (DESIGN.md §22;
+// bodies and comments in lz4ada_bulk_ranges.cpp, the caller is
+// lz4ada_bulk_compress.cpp).  comp_index_open: the index's two device blocks,
+// sized for every frame taken, and the dictionary's image queued on s; n may be
+// 0 (no device call).  A pass queues launch_compress_index with `out`, `base`
+// and its settings and hands its records (hi - lo + 1) to comp_index_pass after
+// its synchronisation.  comp_index_close: in_len, the frames' report (frames may
+// be null) and the index, which the sink owns until then.
+struct CompIndexSink {
+	lz4ada_seek_index* x = nullptr;
+	CompIndexOut out{};
+	CompIndexRec base{};  // the totals after the passes so far
+	bool linked = false, no_lone = false;
+	uint64_t every = 0;  // decoded bytes between checkpoints
+	uint32_t kind = 0;   // the CHAIN_KIND_* of a taken frame with blocks
+	CompIndexSink() = default;
+	CompIndexSink(const CompIndexSink&) = delete;
+	CompIndexSink& operator=(const CompIndexSink&) = delete;
+	~CompIndexSink();
+};
+// checkpoint_bytes of lz4ada_seek_options as decoded bytes between checkpoints (0: the default).
+uint64_t seek_checkpoint_every(int64_t checkpoint_bytes);
+void comp_index_open(CompIndexSink& k, const lz4ada_compress_job* jobs, size_t n, uint32_t block_id, bool linked,
+                     int64_t checkpoint_bytes, const lz4ada_compress_dict* cdict, hipStream_t s);
+void comp_index_pass(CompIndexSink& k, const lz4ada_compress_job* jobs, size_t lo, size_t hi, uint32_t block_id,
+                     const CompIndexRec* rec);
+lz4ada_seek_index* comp_index_close(CompIndexSink& k, const lz4ada_compress_job* jobs, int64_t out_len,
+                                    lz4ada_device_frame_job* frames, hipStream_t s);
+
 // A C-ABI call: the reference's exception as the status code, its text in
 // *err (the context's) and in the thread's last error.
 template <class F>

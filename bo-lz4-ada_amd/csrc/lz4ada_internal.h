@@ -661,4 +661,41 @@ hipError_t launch_compress_frames(const CompJob* d_jobs, uint32_t njobs, const u
                                   uint32_t dict_id, uint32_t linked, uint64_t base, const FrameRec* d_frec,
                                   uint8_t* d_out, CompJobRec* d_rec, hipStream_t stream);
 
+// ---- the seek index a compress call writes (lz4ada_compress_index.hip) ----
+// The index's device arrays as the pass's kernels fill them (SeekView's, writable)
+// and what the host sized them by: nblocks descriptors, nckpt checkpoints in
+// store, nframes frames.  kgrp / ckfirst / store: null unless the call is
+// linked; fkind: null without a dictionary.
+struct CompIndexOut {
+	lz4ada_block_desc* desc;
+	uint64_t *first, *start, *slotp;
+	uint64_t *kgrp, *ckfirst;
+	uint8_t* store;
+	uint64_t* fkind;
+	uint64_t nblocks, nckpt;
+	uint32_t nframes;
+};
+// What k_compress_index_frames says about job j of a pass: its first
+// descriptor, its first block's nominal slot and its first checkpoint among the
+// index's, and the rule's verdict (LZ4ADA_BATCH_*; a frame not taken holds
+// nothing).  Entry njobs: the totals after the pass, the next pass's `base`.
+struct CompIndexRec {
+	uint64_t first, out_base, ck;
+	int32_t verdict;
+	uint32_t pad;
+};
+// The three kernels of a pass over d_jobs[0 .. njobs) / d_blk[0 .. nblocks), the
+// call's jobs f_lo .. f_lo + njobs, once launch_compress_emit (d_emitted: its
+// descriptors) and the block checksums (d_st; null without them) are queued.
+// kind: the CHAIN_KIND_* of a taken frame with blocks (NONE without a
+// dictionary).  ckpts: the pass holds a continuation block of a linked call, so
+// k_ckpt_from_records runs: it reads d_in inside the jobs' records alone and
+// writes checkpoints [base.ck, d_rec[njobs].ck).  d_rec: njobs + 1 records.
+hipError_t launch_compress_index(const uint8_t* d_in, uint64_t in_len, const CompBlock* d_blk, const CompJob* d_jobs,
+                                 uint32_t nblocks, uint32_t njobs, const uint32_t* d_csize,
+                                 const lz4ada_block_desc* d_emitted, const lz4ada_block_status* d_st,
+                                 uint32_t block_id, uint32_t flags, bool linked, bool ckpts, uint64_t every,
+                                 bool no_lone, uint32_t kind, uint32_t f_lo, const CompIndexRec& base,
+                                 const CompIndexOut& o, CompIndexRec* d_rec, hipStream_t stream);
+
 }  // namespace lz4ada

@@ -236,6 +236,13 @@ class CompressDict(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class CompressIndexOptions(ctypes.Structure):
+    """lz4ada_compress_index_options: flags (COMP_INDEX_LINKED), reserved (0),
+    checkpoint_bytes (as SeekOptions')."""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("checkpoint_bytes", ctypes.c_int64)]
+
+
+COMP_INDEX_LINKED = 1  # CompressIndexOptions.flags: frames of linked blocks
 COMP_BLOCK_CHECKSUM, COMP_CONTENT_CHECKSUM, COMP_CONTENT_SIZE = 1, 2, 4
 COMP_DICT_WRITE_ID = 1
 _COMP_BLOCK_ID = {65536: 4, 262144: 5, 1 << 20: 6, 4 << 20: 7}
@@ -317,6 +324,12 @@ _sig = {
     "lz4ada_compress_frames_device_linked": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
     "lz4ada_compress_frame_linked_host": ([_vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _i64],
                                           _i64),
+    "lz4ada_compress_frames_device_indexed": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _pi64, _vp,
+                                               ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_compress_index_host": ([_vp, _i64, _i64, _vp, ctypes.c_uint32, ctypes.c_uint32, _i64, ctypes.c_uint64,
+                                    ctypes.c_uint64, _vp, _vp, _i64, _pi64, ctypes.POINTER(ctypes.c_int32), _pi64,
+                                    _pi64], ctypes.c_int),
+    "lz4ada_seek_index_store_debug": ([_vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
     "lz4ada_compress_frame_dict_host": ([_vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _i64],
                                         _i64),
     "lz4ada_abi_version": ([], ctypes.c_int),
@@ -896,7 +909,7 @@ def compress_frames_bound(lens, block=65536, block_checksum=False, content_check
 
 def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: int, stream: int = 0, block=65536,
                            block_checksum=False, content_checksum=False, content_size=False, dict=None,
-                           dict_id=None, linked=False):
+                           dict_id=None, linked=False, index=False, checkpoint_bytes=0):
     """Compress the records at spans [(in_off, in_len)] of the device buffer
     d_in into LZ4 frames laid back to back into the device buffer d_out (raw
     pointers) -> (bytes written, the CompressJob array: out_off, out_len,
@@ -908,11 +921,28 @@ def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: i
     it, None writes none.  linked: frames of linked blocks
     (lz4ada_compress_frames_device_linked): a block after a
     record's first is compressed against the 65,536 bytes in front of it;
-    decode_frames_device(linked=True) reads the frames."""
+    decode_frames_device(linked=True) reads the frames.  index: the call
+    also writes the frames' seek index (lz4ada_compress_frames_device_indexed,
+    DESIGN.md §22) and returns it as a third value, a SeekIndex over (d_out,
+    bytes written) whose .jobs is the call's report of the frames;
+    checkpoint_bytes: as SeekIndex.build's, for linked frames."""
     opt = _compress_options(block, block_checksum, content_checksum, content_size)
     jobs = _compress_jobs(spans)
     n = _i64()
     cd = _compress_dict(dict, dict_id)
+    if index:
+        xopt = CompressIndexOptions(COMP_INDEX_LINKED if linked else 0, 0, checkpoint_bytes)
+        frames = (DeviceFrameJob * max(len(spans), 1))()
+        ptr = _vp()
+        st = _lib.lz4ada_compress_frames_device_indexed(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
+                                                        None if cd is None else ctypes.byref(cd),
+                                                        ctypes.byref(xopt), d_out, out_cap, ctypes.byref(n), frames,
+                                                        ctypes.byref(ptr), stream)
+        if st:
+            exc = _ERRORS.get(st, LZ4AdaError)(_thread_error())
+            exc.bound = n.value
+            raise exc
+        return n.value, jobs, SeekIndex(ptr.value, frames, len(spans), n.value)
     if linked:
         st = _lib.lz4ada_compress_frames_device_linked(d_in, in_len, jobs, len(spans), ctypes.byref(opt),
                                                        None if cd is None else ctypes.byref(cd), d_out, out_cap,
@@ -931,14 +961,17 @@ def compress_frames_device(d_in: int, in_len: int, spans, d_out: int, out_cap: i
 
 
 def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False, content_checksum=False,
-                           content_size=False, dict=None, dict_id=None, linked=False):
+                           content_size=False, dict=None, dict_id=None, linked=False, index=False,
+                           checkpoint_bytes=0):
     """compress_frames_device for a CUDA torch.uint8 tensor holding the
     records, on torch's current stream -> (the frames as a uint8 tensor on the
     same device, [(off, len)] of every record's frame inside it).  out: a uint8
     tensor there to write into; by default one of compress_frames_bound bytes
     is allocated.  dict: a CUDA uint8 tensor on the same device holding the
     dictionary every frame shares; dict_id: when given, written into every
-    header.  linked: frames of linked blocks, as compress_frames_device's."""
+    header.  linked: frames of linked blocks, as compress_frames_device's.
+    index, checkpoint_bytes: as compress_frames_device's; the SeekIndex over the
+    returned tensor comes as a third value."""
     if torch is None:
         raise RuntimeError("compress_frames_tensor needs torch")
     if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
@@ -955,9 +988,12 @@ def compress_frames_tensor(t, spans, out=None, block=65536, block_checksum=False
                               device=t.device)
         elif not (out.is_cuda and out.device == t.device and out.dtype == torch.uint8 and out.is_contiguous()):
             raise ValueError("out must be a contiguous CUDA uint8 tensor on the records' device")
-        n, jobs = compress_frames_device(t.data_ptr() if t.numel() else None, t.numel(), spans, out.data_ptr(),
-                                         out.numel(), torch.cuda.current_stream().cuda_stream, linked=linked, **kw)
-    return out[:n], [(jobs[i].out_off, jobs[i].out_len) for i in range(len(spans))]
+        got = compress_frames_device(t.data_ptr() if t.numel() else None, t.numel(), spans, out.data_ptr(),
+                                     out.numel(), torch.cuda.current_stream().cuda_stream, linked=linked,
+                                     index=index, checkpoint_bytes=checkpoint_bytes, **kw)
+    n, jobs = got[0], got[1]
+    frames = [(jobs[i].out_off, jobs[i].out_len) for i in range(len(spans))]
+    return (out[:n], frames, got[2]) if index else (out[:n], frames)
 
 
 def compress_block_host(data, cap=None, dict=b"") -> bytes:
@@ -1223,6 +1259,34 @@ def seek_index_debug(idx: SeekIndex, stream: int = 0):
                                             nb.value + 1, stream), _thread_error())
         res.append((reason.value, list(start)))
     return res
+
+
+def compress_index_host(frame, record_len, block=65536, block_checksum=False, content_checksum=False,
+                        content_size=False, dict_id=None, linked=False, checkpoint_bytes=0, frame_off=0, out_base=0):
+    """Test-only: the rule of the indexed compress call over one frame that
+    compress_frame_host wrote with the same keywords (no GPU involved) ->
+    (verdict, [BlockDesc], [decoded size], K, checkpoints)."""
+    frame = bytes(frame)
+    opt = _compress_options(block, block_checksum, content_checksum, content_size)
+    cap = record_len // 65536 + 2
+    descs, sizes = (BlockDesc * cap)(), (ctypes.c_uint32 * cap)()
+    nb, verdict, group, ck = _i64(), ctypes.c_int32(), _i64(), _i64()
+    st = _lib.lz4ada_compress_index_host(_addr(frame), len(frame), record_len, ctypes.byref(opt),
+                                         0 if dict_id is None else COMP_DICT_WRITE_ID, 1 if linked else 0,
+                                         checkpoint_bytes, frame_off, out_base, descs, sizes, cap, ctypes.byref(nb),
+                                         ctypes.byref(verdict), ctypes.byref(group), ctypes.byref(ck))
+    _check(st, "lz4ada_compress_index_host: the frame is not the record's, or an argument is out of range")
+    return verdict.value, [descs[i] for i in range(nb.value)], list(sizes[:nb.value]), group.value, ck.value
+
+
+def seek_index_store_debug(idx: SeekIndex, stream: int = 0) -> bytes:
+    """Test-only: the checkpoint store of an index, 65,536 bytes per checkpoint."""
+    n = _i64()
+    _check(_lib.lz4ada_seek_index_store_debug(idx._ptr, None, 0, ctypes.byref(n), stream), _thread_error())
+    buf = ctypes.create_string_buffer(max(n.value * 65536, 1))
+    _check(_lib.lz4ada_seek_index_store_debug(idx._ptr, buf, n.value * 65536, ctypes.byref(n), stream),
+           _thread_error())
+    return buf.raw[:n.value * 65536]
 
 
 def ranges_select_debug(idx: SeekIndex, ranges, stream: int = 0):

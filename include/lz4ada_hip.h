@@ -1138,6 +1138,102 @@ int64_t lz4ada_compress_frame_linked_host(const uint8_t *src, int64_t n,
                                           int64_t dict_len, uint32_t dict_id, uint32_t dict_flags,
                                           uint8_t *dst, int64_t cap);
 
+/* ------------- records compressed into frames, with the frames' seek index */
+/*
+ * lz4ada_compress_frames_device, _dict or _linked -- by dict and by
+ * LZ4ADA_COMP_INDEX_LINKED in xopt->flags -- that also writes the seek index
+ * of the frames it writes, so that a caller who wants
+ * byte ranges of them (lz4ada_decode_ranges_device) needs no
+ * lz4ada_seek_index_build* over what the compressor already knew: where every
+ * block lies, what it decodes to, and, for a linked frame, the 65,536 record
+ * bytes in front of every checkpointed block, which lay in d_in.
+ *
+ * Frames.  d_out, *out_len and jobs[] come out byte for byte as that existing
+ * call gives them; the bound, LZ4ADA_TOO_LITTLE_MEMORY and every misuse of it
+ * behave the same, and on those outcomes *idx is NULL and nothing is
+ * allocated.  Misuse of this entry alone -- idx NULL, unknown bits in
+ * xopt->flags, xopt->reserved != 0, xopt->checkpoint_bytes < 0 -- is
+ * LZ4ADA_ASSERTION_ERROR before any device call.  xopt NULL is {0, 0, 0}.
+ *
+ * Index.  On success *idx is an index over the input (d_out, *out_len); job k
+ * is the frame at jobs[k].out_off.  lz4ada_decode_ranges_device,
+ * lz4ada_seek_index_bytes, _free, _debug and lz4ada_ranges_select_debug take
+ * it as they take a built one.  It holds what
+ *   lz4ada_seek_index_build_dict(d_out, *out_len, frames, njobs,
+ *       {linked ? LZ4ADA_SEEK_LINKED : 0, 0, checkpoint_bytes},
+ *       {dict->d_dict, dict->dict_len, dict->dict_id, 0}, ...)
+ * would hold -- descriptors, block starts, tight slots, frame kinds, its own
+ * copy of the dictionary (any dict_len > 0; the caller's may be freed after the
+ * call), checkpoint groups and the checkpoint store -- and
+ * lz4ada_seek_index_bytes is that build's figure, with two deliberate
+ * differences:
+ *  1. The verdicts are those of the build's index stage alone: frame_walk's
+ *     rule over the written sizes, which for these frames can only say
+ *     LZ4ADA_BATCH_BIG_BLOCK (the lone-block rule: a frame of at most 24 blocks
+ *     with a payload of 512 KiB or more, so only with 1 MiB and 4 MiB blocks,
+ *     and never under LZ4ADA_NO_LONE).  LZ4ADA_BATCH_OVER_BUDGET is not judged
+ *     (the ranged call judges a range's own blocks against LZ4ADA_BATCH_BYTES).
+ *     Nothing is decoded, so there is no LZ4ADA_DEVFRAME_BLOCK from a block the
+ *     index decoder declines or, in a linked frame without a dictionary, from
+ *     quirk D1's round state at build time; such a block fails its ranges at
+ *     range time with LZ4ADA_EXACT_PATH / LZ4ADA_DEVFRAME_BLOCK, as in a
+ *     dictionary index today (the ranged decode has the specification's
+ *     semantics).
+ *  2. lz4ada_batch_linked_max() is not applied: a linked frame of any length
+ *     is taken, with its checkpoints.  The limit belongs to passes that put one
+ *     wave on a whole frame; a range decodes chains of at most K blocks.
+ * njobs == 0 gives an empty index and makes no device call.
+ *
+ * frames, when given (njobs entries), is filled as the build would report it:
+ * in_off / in_len the frame's place in d_out, out_len the record's length (0
+ * for a frame the index did not take), status (LZ4ADA_OK or LZ4ADA_EXACT_PATH)
+ * and reason; out_off and consumed 0.
+ *
+ * Synchronous on `stream`.  Host synchronisations: the compress passes' own
+ * (one per pass, one more for a content checksum over LZ4ADA_BATCH_HASH_MAX
+ * bytes) and no other -- the index's kernels of a pass are queued in front of
+ * that pass's synchronisation -- unless the lone-block rule turned a frame
+ * down: then one more, after which the index's arrays lie in memory of exactly
+ * the build's size.  The index's device memory is allocated before the first
+ * pass, for every frame taken.
+ */
+#define LZ4ADA_COMP_INDEX_LINKED 1u /* frames of linked blocks (the _linked call's frames) */
+typedef struct {
+	uint32_t flags;           /* LZ4ADA_COMP_INDEX_* */
+	uint32_t reserved;        /* must be 0 */
+	int64_t checkpoint_bytes; /* as lz4ada_seek_options; 0: the default; < 0: misuse */
+} lz4ada_compress_index_options;
+int lz4ada_compress_frames_device_indexed(const void *d_in, int64_t in_len,
+                                          lz4ada_compress_job *jobs, int64_t njobs,
+                                          const lz4ada_compress_options *opt,
+                                          const lz4ada_compress_dict *dict,
+                                          const lz4ada_compress_index_options *xopt, void *d_out,
+                                          int64_t out_cap, int64_t *out_len,
+                                          lz4ada_device_frame_job *frames,
+                                          lz4ada_seek_index **idx, void *stream);
+/* Test-only.  The rule the indexed call's kernels run (lz4ada_compress_index.h)
+ * over one frame that lz4ada_compress_frame_host, _dict_host or _linked_host
+ * wrote from a record of record_len bytes under opt and dict_flags: the written
+ * sizes are read from the frame's size words, nothing else of it but the block
+ * checksums.  descs / sizes (cap entries each; fewer blocks are written when
+ * the frame holds more): every block's descriptor as the walk emits it for a
+ * pass -- in_off = frame_off + its place in the frame, out_off from out_base in
+ * steps of the slot capacity rounded up to 256, out_cap the slot capacity -- and
+ * its decoded size.  *verdict: LZ4ADA_BATCH_OK or _BIG_BLOCK; *group and
+ * *checkpoints: K and the checkpoint count of a linked frame (`linked`) with a
+ * checkpoint every checkpoint_bytes (0: the default), else 0.  A frame that is
+ * not the record's is LZ4ADA_ASSERTION_ERROR.  Host only, no HIP call. */
+int lz4ada_compress_index_host(const uint8_t *frame, int64_t frame_len, int64_t record_len,
+                               const lz4ada_compress_options *opt, uint32_t dict_flags,
+                               uint32_t linked, int64_t checkpoint_bytes, uint64_t frame_off,
+                               uint64_t out_base, lz4ada_block_desc *descs, uint32_t *sizes,
+                               int64_t cap, int64_t *nblocks, int32_t *verdict, int64_t *group,
+                               int64_t *checkpoints);
+/* Test-only.  The checkpoint store of an index, copied to the host: *nckpt
+ * entries of 65,536 bytes (store may be NULL to ask for the count alone). */
+int lz4ada_seek_index_store_debug(const lz4ada_seek_index *idx, void *store, int64_t store_cap,
+                                  int64_t *nckpt, void *stream);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
