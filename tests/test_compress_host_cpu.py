@@ -17,6 +17,7 @@ import _oracle as O
 import lz4ada
 from _compress_cases import (BLOCK_LEN, KiB, LEN_ID5, frame_blocks, frame_bound, id4_records, noise, parse_block,
                              pseudo_text, record)
+from _compress_edge_cases import A, far_repeat, planted
 from conftest import GOLDEN
 
 FLAG_SETS = [dict(zip(("block_checksum", "content_checksum", "content_size"), bits))
@@ -132,24 +133,6 @@ def test_liblz4_reads_the_frames():
 
 # ---------------------------------------------------------------- crafted
 
-A = noise(448, 11)  # seven windows of noise: every position of it is inserted
-
-
-def differing(data, byte):
-    """data with its first byte made unequal to `byte`."""
-    return bytes([data[0] ^ 1]) + data[1:] if data[0] == byte else data
-
-
-def planted(lit, ml):
-    """Noise, a first repeat, `lit` bytes of noise, a repeat of exactly `ml`
-    bytes from an inserted place, 20 bytes of noise -> (record, its sequences)."""
-    run = differing(noise(lit, 300 + lit), A[32])  # (seeds under which no position of the run shares the source's hash)
-    tail = differing(noise(20, 200 + ml), A[64 + ml])
-    data = A + A[:32] + run + A[64:64 + ml] + tail
-    at = len(A) + 32 + lit
-    return data, [(len(A), len(A), 32), (lit, at - 64, ml), (20, 0, 0)]
-
-
 @pytest.mark.parametrize("lit", [14, 15, 16, 269, 270, 271])
 def test_literal_run_edges(lit):
     data, want = planted(lit, 40)
@@ -174,17 +157,6 @@ def test_match_length_edges(ml):
     ext = {18: b"", 19: b"\x00", 20: b"\x01", 273: b"\xfe", 274: b"\xff\x00"}[ml]
     assert comp[q:q + len(ext)] == ext
     assert comp[q + len(ext)] >> 4 == 15  # the last token: 20 literals
-
-
-def far_repeat(distance):
-    """A 32-byte repeat whose only earlier copy lies `distance` back, at
-    positions past 2^16 in a block of 256 KiB: zeros (one match: nothing inside
-    it is inserted), 64 bytes of noise holding the source at 16, zeros again,
-    the copy, 20 bytes of noise -> (record, where the copy begins)."""
-    s = differing(noise(32, 31), 0)  # (a seed under which no later inserted position shares its hash)
-    src = noise(16, 23) + s + noise(16, 24)
-    tail = differing(noise(20, 22), src[48])
-    return bytes(70000) + src + bytes(distance - 48) + s + tail, 70000 + 16 + distance
 
 
 def test_offset_65535_is_matched_and_65536_is_not():
