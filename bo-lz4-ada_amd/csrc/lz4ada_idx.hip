@@ -1228,6 +1228,28 @@ __device__ __forceinline__ void ostore(LD& L, int32_t x, u32x4 v, int32_t n)
 	}
 }
 
+// Whole-piece store: v's 16 bytes at output position x where has, else
+// nothing.  The fast layouts issue one ds_write_b128, to the piece's place
+// or to the junk bytes -- none of lds_store_bf's select network, no second
+// to fifth store; a piece wrapping the ring's end sends the wave through
+// ostore, as there.  For a dealt piece that is not its run's last: such a
+// piece lies wholly inside its own run.
+template <class LD>
+__device__ __forceinline__ void ostore16(LD& L, int32_t x, u32x4 v, bool has)
+{
+	if constexpr (lds_fast<LD>::value) {
+		const uint32_t a = uint32_t(x) & omask_of(L);
+		if (__builtin_expect(!__any(has && a + 16u > omask_of(L) + 1), 1)) {
+			__builtin_memcpy(has ? &oring_of(L)[a] : junk_of(L), &v, 16);
+			return;
+		}
+		ostore(L, x, v, has ? 16 : 0);
+	} else {
+		if (has)
+			ostore(L, x, v, 16);
+	}
+}
+
 template <class LD>
 __device__ __forceinline__ u32x4 oload16(const LD& L, int32_t x)
 {
@@ -2208,9 +2230,12 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		ISTAMP(D_WALK2);
 
 		// HBM-sourced matches: every load in flight before the first use.  A
-		// match's first GC pieces load in its own lane; the pieces beyond
-		// (long matches) of both rounds are dealt over the wave, one per
-		// lane, through the LDS match descriptors.  More than 64 is common
+		// match's last 16-byte piece, the only one that can be short, loads
+		// in its own lane; the pieces before it (long matches) of both
+		// rounds are dealt over the wave, one per lane, through the LDS
+		// match descriptors, and are stored whole (no in-batch HBM match
+		// overlaps its source: that lies more than OW back, and a batch
+		// holds at most OW bytes).  More than 64 is common
 		// where matches are long and far (over a third of the mixed class's
 		// batches, by about 7 pieces): the pieces beyond load here too, in
 		// lanes whose own slot vg[r][0] is idle because their match is not
@@ -2219,10 +2244,11 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		const int BORROW = (D1E || ZL) ? 0 : BORROW_SLOTS;
 		u32x4 vg[RMAX][GC], vr = u32x4{0u, 0u, 0u, 0u};
 		int32_t rtot[RMAX], rfirst[RMAX];  // pieces beyond GC per round; the first not dealt here
-		int32_t rpd = 0, rpn = 0;          // this lane's dealt piece
+		int32_t rpd = 0;                   // this lane's dealt piece (16 whole bytes)
+		bool rph = false;                  // ... and whether it has one
 		// a piece beyond the 64 dealt ones, loaded into this lane's idle
 		// vg[r][0]: batch-relative output position (12 bits: a batch is at
-		// most OW bytes), length << 12 (0: none)
+		// most OW bytes), its 16 bytes' length << 12 (0: none)
 		static_assert(OW <= 4096, "a borrowed piece's position takes 12 bits");
 		int32_t bpc[RMAX];
 #pragma unroll
@@ -2244,10 +2270,12 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				if (64 * r < N) {
 					const int32_t src = rdst[r] + rL[r] - roff[r];
 					const bool g = rml[r] > 0 && src < glo;
-#pragma unroll
-					for (int c = 0; c < GC; ++c)
-						if (g && 16 * c < rml[r])
-							__builtin_memcpy(&vg[r][c], ob + src + 16 * c, 16);
+					// the own piece is the match's last (1..16 bytes; the load
+					// reads up to 15 bytes past the source's end: still below
+					// the match's own destination, and never stored)
+					static_assert(GC == 1, "one own HBM piece per match: its last");
+					if (g)
+						__builtin_memcpy(&vg[r][0], ob + src + (((rml[r] - 1) >> 4) << 4), 16);
 					nc[r] = g ? max(((rml[r] + 15) >> 4) - GC, 0) : 0;
 					GCOUNT(0, __popcll(__ballot(g)));
 					GCOUNT(1, __popcll(__ballot(g)) + __popcll(__ballot(g && ((src & 127) > 112))));
@@ -2273,14 +2301,16 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				const int32_t lo = min(chunk_owner2(D, inc0, nc[0], inc1, nc[1], 0), 127);
 				const uint64_t dd = D.ldesc[lo];
 				const int32_t od = o_batch + int32_t(dd & 0xffffu);
-				const int32_t ooff = int32_t((dd >> 16) & 0xffffu), oml = int32_t((dd >> 32) & 0xffffu);
-				const int32_t k = GC + lane - int32_t(dd >> 48);
+				const int32_t ooff = int32_t((dd >> 16) & 0xffffu);
+				// (a match's dealt pieces are its pieces 0 .. K - 2, whole; its
+				// last is its own lane's)
+				const int32_t k = lane - int32_t(dd >> 48);
 				GCOUNT(0, __popcll(__ballot(lane < tot)));
 				GCOUNT(1, __popcll(__ballot(lane < tot)) +
 				              __popcll(__ballot(lane < tot && ((od - ooff + 16 * k) & 127) > 112)));
 				if (lane < tot) {
 					rpd = od + 16 * k;
-					rpn = min(16, oml - 16 * k);
+					rph = true;
 					__builtin_memcpy(&vr, ob + (od - ooff) + 16 * k, 16);
 				}
 				if (tot > 64) {
@@ -2306,9 +2336,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 						const int32_t bo = __shfl(own2, (t - 64) & 63);
 						if (idle && t < min(tot, 128)) {
 							const uint64_t bd = D.ldesc[bo];
-							const int32_t brel = int32_t(bd & 0xffffu), bml = int32_t((bd >> 32) & 0xffffu);
-							const int32_t bk = GC + t - int32_t(bd >> 48);
-							bpc[r] = (brel + 16 * bk) | (min(16, bml - 16 * bk) << 12);
+							const int32_t brel = int32_t(bd & 0xffffu);
+							const int32_t bk = t - int32_t(bd >> 48);
+							bpc[r] = (brel + 16 * bk) | (16 << 12);  // (a dealt piece: whole)
 							__builtin_memcpy(&vg[r][0], ob + (o_batch + brel - int32_t((bd >> 16) & 0xffffu)) + 16 * bk,
 							                 16);
 						}
@@ -2322,20 +2352,24 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		}
 		ISTAMP(D_TLDS);
 
-		// L: literals (input ring -> output ring).  Every run's first 16
-		// bytes in its own lane; the pieces beyond (runs over 16 bytes) of
-		// both rounds are dealt over the wave together, each piece reading
-		// its run from an LDS descriptor.  (Storing a short last piece as 16
-		// bytes that spill into its own match, rewritten in M, measured no
-		// faster.)
+		// L: literals (input ring -> output ring).  A run of K 16-byte
+		// pieces stores its last one, the only one that can be short, in
+		// its own lane with the exact-length store; the K - 1 pieces before
+		// it (runs over 16 bytes) of both rounds are dealt over the wave
+		// together, each piece reading its run from an LDS descriptor and
+		// storing 16 whole bytes that lie inside its run.  (Storing a short
+		// last piece as 16 bytes that spill into its own match, rewritten
+		// in M, measured no faster.)
 		static_assert(RMAX == 2, "literal dealing pairs two rounds");
 		{
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r)  // (rL = 0 also where a round has no sequence: n = 0)
-				ostore(D, rdst[r], ZL ? u32x4{ 0u, 0u, 0u, 0u } : fetch16(S, rL[r] > 0 ? rlit[r] : S.lo),
-				       min(16, rL[r]));
 			const int32_t nc0 = rL[0] > 16 ? (rL[0] - 1) >> 4 : 0;
 			const int32_t nc1 = rL[1] > 16 ? (rL[1] - 1) >> 4 : 0;
+#pragma unroll
+			for (int r = 0; r < RMAX; ++r) {  // (rL = 0 also where a round has no sequence: n = 0)
+				const int32_t c = 16 * (r == 0 ? nc0 : nc1);  // the last piece's place in the run
+				ostore(D, rdst[r] + c, ZL ? u32x4{ 0u, 0u, 0u, 0u } : fetch16(S, rL[r] > 0 ? rlit[r] + c : S.lo),
+				       rL[r] - c);
+			}
 			if (__any(nc0 > 0 || nc1 > 0)) {
 				const int32_t inc0 = wave_incl_scan(nc0);
 				const int32_t tot0 = wave_last(inc0);
@@ -2353,11 +2387,10 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 					const uint64_t dd = D.ldesc[lo];
 					const int32_t lit = base + int32_t(dd & 0xffffu);
 					const int32_t dst = o_batch + int32_t((dd >> 16) & 0xffffu);
-					const int32_t L = int32_t((dd >> 32) & 0xffffu);
-					const int32_t k = 1 + t - int32_t(dd >> 48);  // piece 0 went in-lane
+					const int32_t k = t - int32_t(dd >> 48);  // pieces 0 .. K - 2 (the last went in-lane)
 					const bool has = t < tot;
-					ostore(D, dst + 16 * k, ZL ? u32x4{ 0u, 0u, 0u, 0u } : fetch16(S, has ? lit + 16 * k : S.lo),
-					       has ? min(16, L - 16 * k) : 0);
+					ostore16(D, dst + 16 * k, ZL ? u32x4{ 0u, 0u, 0u, 0u } : fetch16(S, has ? lit + 16 * k : S.lo),
+					         has);
 				}
 			}
 		}
@@ -2381,9 +2414,9 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		// them makes each later reuse of its registers wait vmcnt(0) (one
 		// showed up inside the near-match loop)
 		__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-		// pieces of HBM-sourced matches beyond the first GC, dealt and
-		// loaded in P (the first 64 of the batch)
-		ostore(D, rpd, vr, rpn);  // (rpn = 0: none)
+		// pieces of HBM-sourced matches before their last, dealt and loaded
+		// in P (the first 64 of the batch): 16 whole bytes inside their match
+		ostore16(D, rpd, vr, rph);
 #pragma unroll
 		for (int r = 0; r < RMAX; ++r) {
 			mring[r] = oring[r] = lring[r] = 0;
@@ -2391,10 +2424,40 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				const int32_t mdst = rdst[r] + rL[r], off = roff[r], ml = rml[r];
 				const bool hbm = ml > 0 && mdst - off < glo;
 				static_assert(GC == 1, "one own HBM piece per match");
-				// (the slot of a match that is not HBM-sourced may hold a
-				// borrowed piece of another match instead: bpc, set in P)
-				ostore(D, hbm ? mdst : o_batch + (bpc[r] & 0xfff), vg[r][0], hbm ? min(16, ml) : bpc[r] >> 12);
+				// the match's last piece, the one that can be short, loaded in
+				// its own lane (the slot of a match that is not HBM-sourced may
+				// hold a borrowed whole piece of another match instead: bpc,
+				// set in P)
+				const int32_t mc = ((ml - 1) >> 4) << 4;
+				ostore(D, hbm ? mdst + mc : o_batch + (bpc[r] & 0xfff), vg[r][0], hbm ? ml - mc : bpc[r] >> 12);
+				// dealt pieces that found no lane in P load now and are waited
+				// for on the spot (over a third of the mixed class's batches
+				// without BORROW)
+				if (rtot[r] > rfirst[r]) {
+					ICOUNT(D_HSLOW_B, r == 0 || rtot[0] <= rfirst[0]);
+					ICOUNT(D_HSLOW_P, rtot[r] - rfirst[r]);
+					const int32_t nc = hbm ? max(((ml + 15) >> 4) - GC, 0) : 0;
+					const int32_t inc = wave_incl_scan(nc);
+					for (int32_t t0 = rfirst[r]; t0 < rtot[r]; t0 += 64) {
+						const int32_t t = t0 + lane;
+						const int32_t lo = piece_owner(inc, t);
+						const int32_t k = t - (__shfl(inc, lo) - __shfl(nc, lo));
+						const int32_t osrc = __shfl(mdst - off, lo), odst = __shfl(mdst, lo);
+						const bool has = t < rtot[r];
+						u32x4 v = u32x4{ 0u, 0u, 0u, 0u };
+						if (has)
+							__builtin_memcpy(&v, ob + osrc + 16 * k, 16);
+						ostore16(D, odst + 16 * k, v, has);
+					}
+					// settle this rare path's loads (see fetch4)
+					__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+				}
 				int32_t xoff = off, xml = (ml > 0 && !hbm) ? ml : 0;  // its ring copy, if any
+				// (after every store of this round's HBM pieces, the loop
+				// above included: the D1 bytes overwrite the start of piece 0
+				// of their match, which is a dealt piece when the match is
+				// over 16 bytes, and a wave's LDS stores take effect in the
+				// order they are issued)
 				if (d1p) {
 					// quirk D1 (d1_emulable): the match's first k1 bytes are
 					// what the last wild copy left past the frontier, from d =
@@ -2431,29 +2494,6 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 					if (fo)
 						__builtin_memcpy(&v, ob + gq, 16);
 					ostore(D, mdst, v, k1);
-				}
-				// dealt pieces that found no lane in P load now and are waited
-				// for on the spot (over a third of the mixed class's batches
-				// without BORROW)
-				if (rtot[r] > rfirst[r]) {
-					ICOUNT(D_HSLOW_B, r == 0 || rtot[0] <= rfirst[0]);
-					ICOUNT(D_HSLOW_P, rtot[r] - rfirst[r]);
-					const int32_t nc = hbm ? max(((ml + 15) >> 4) - GC, 0) : 0;
-					const int32_t inc = wave_incl_scan(nc);
-					for (int32_t t0 = rfirst[r]; t0 < rtot[r]; t0 += 64) {
-						const int32_t t = t0 + lane;
-						const int32_t lo = piece_owner(inc, t);
-						const int32_t k = GC + t - (__shfl(inc, lo) - __shfl(nc, lo));
-						const int32_t osrc = __shfl(mdst - off, lo), odst = __shfl(mdst, lo);
-						const int32_t oml = __shfl(ml, lo);
-						if (t < rtot[r]) {
-							u32x4 v;
-							__builtin_memcpy(&v, ob + osrc + 16 * k, 16);
-							ostore(D, odst + 16 * k, v, min(16, oml - 16 * k));
-						}
-					}
-					// settle this rare path's loads (see fetch4)
-					__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
 				}
 				mring[r] = mdst;
 				oring[r] = xoff;
