@@ -44,6 +44,7 @@
 
 #include "lz4ada_compress_index.h"
 #include "lz4ada_host_common.h"
+#include "lz4ada_index_merge.h"
 #include "lz4ada_range_blocks.h"
 #include "lz4ada_range_chains.h"
 
@@ -102,6 +103,9 @@ struct lz4ada_seek_index {
 	std::vector<uint64_t> size;  // decoded bytes; 0 unless accepted
 	// by sorted position, n + 1 entries: what view.first holds
 	std::vector<uint64_t> first;
+	// the nominal slots of the frames taken: where the out_off of a next frame's
+	// first block would lie (what a concat rebases a later part's out_off by)
+	uint64_t slots = 0;
 	bool taken(size_t job) const { return reason[job] == LZ4ADA_DEVFRAME_OK; }
 };
 
@@ -483,18 +487,29 @@ void decode_linked_frames(FramesIndex& ix, const lz4ada_seek_index& x, uint8_t* 
 // The index's own dictionary, queued on s: the gap every pass copies, zeros and
 // then the last `used` bytes of the caller's (an allocation: 256-aligned).  For
 // the builds and for the index a compress call writes; dict_len > 0.
-void lay_dict_image(lz4ada_seek_index& x, const void* d_dict, int64_t dict_len, hipStream_t s)
+uint8_t* alloc_dict_image(lz4ada_seek_index& x, uint32_t used)
 {
-	const uint32_t used = uint32_t(std::min<uint64_t>(uint64_t(dict_len), DICT_MAX));
 	const uint64_t gap = dict_gap(used);
 	uint8_t* const img = x.dict_mem.alloc(size_t(gap), "the seek index's dictionary");
 	x.dict = DictCtx{ img, gap, used, gap };
-	const size_t zeros = size_t(gap) - used;
+	x.view.dict = img;
+	x.view.dict_used = used;
+	return img;
+}
+void lay_dict_image(lz4ada_seek_index& x, const void* d_dict, int64_t dict_len, hipStream_t s)
+{
+	const uint32_t used = uint32_t(std::min<uint64_t>(uint64_t(dict_len), DICT_MAX));
+	uint8_t* const img = alloc_dict_image(x, used);
+	const size_t zeros = size_t(x.dict.gap) - used;
 	HIP_OK(hipMemsetAsync(img, 0, zeros, s));
 	HIP_OK(hipMemcpyAsync(img + zeros, static_cast<const uint8_t*>(d_dict) + (uint64_t(dict_len) - used), used,
 	                      hipMemcpyDeviceToDevice, s));
-	x.view.dict = img;
-	x.view.dict_used = used;
+}
+// Its sibling for a concat: the image of an index that has one, as it lies.
+void copy_dict_image(lz4ada_seek_index& x, const lz4ada_seek_index& from, hipStream_t s)
+{
+	uint8_t* const img = alloc_dict_image(x, from.dict.used);
+	HIP_OK(hipMemcpyAsync(img, from.dict_mem.p, size_t(from.dict.gap), hipMemcpyDeviceToDevice, s));
 }
 
 // What the index keeps of nb blocks in n > 0 frames, allocated and named in its
@@ -590,6 +605,7 @@ void build_index(const char* entry, const void* d_in, int64_t in_len, lz4ada_dev
 		if (linked && n && !ix.taken(k))
 			x->kgrp[k] = 0;
 		x->linked |= linked && ix.taken(k) && ix.linked(k) && ix.walk[k].nblocks > 0;
+		x->slots += ix.taken(k) ? ix.walk[k].slots : 0;
 	}
 	const uint64_t nb = x->first[n];
 	if (nb >= (uint64_t(1) << 31))
@@ -737,6 +753,7 @@ lz4ada_seek_index* comp_index_close(CompIndexSink& k, const lz4ada_compress_job*
 	lz4ada_seek_index& x = *k.x;
 	const size_t n = x.pos.size();
 	x.in_len = out_len;
+	x.slots = k.base.out_base;
 	const uint64_t nb = n ? x.first[n] : 0, nck = k.linked && n ? x.ckfirst[n] : 0;
 	if (n && (nb != k.out.nblocks || nck != k.out.nckpt)) {
 		// a frame fell to the lone-block rule: the arrays into blocks of the build's
@@ -783,7 +800,172 @@ lz4ada_seek_index* comp_index_close(CompIndexSink& k, const lz4ada_compress_job*
 	return r;
 }
 
+// ---- several indexes laid into one (lz4ada_seek_index_concat) ----
+// The rule is lz4ada_index_merge.h's: the host validates the parts and sums the
+// five prefixes with it, concatenates its own vectors by them, allocates the
+// result through the layouts above, sends one part table up and queues the
+// kernels of lz4ada_index_merge.hip; one host synchronisation ends the call and
+// brings the dictionary comparison's flag down.
 namespace {
+
+MergePart merge_shape(const lz4ada_seek_index& x)
+{
+	const size_t n = x.pos.size();
+	return MergePart{ int64_t(n), int64_t(n ? x.first[n] : 0), int64_t(x.view.nckpt), x.in_len, int64_t(x.slots) };
+}
+
+void concat_index(const char* entry, const lz4ada_seek_index* const* parts, const int64_t* in_base, int64_t nparts,
+                  int64_t in_len, lz4ada_seek_index** idx, hipStream_t s)
+{
+	if (!idx)
+		misuse(entry, "idx is NULL");
+	if (nparts > 0 && !parts)
+		misuse(entry, "parts is NULL");
+	std::vector<MergePart> shape(size_t(std::max<int64_t>(nparts, 0)));
+	for (int64_t p = 0; p < nparts; ++p) {
+		if (!parts[p])
+			misuse(entry, "part" + img(p) + " is NULL");
+		shape[size_t(p)] = merge_shape(*parts[p]);
+	}
+	int64_t at = 0;
+	switch (merge_validate(shape.data(), in_base, nparts, in_len, &at)) {
+	case MERGE_OK:
+		break;
+	case MERGE_NEGATIVE_COUNT:
+		misuse(entry, "nparts or in_len is negative");
+	case MERGE_NULL_ARRAY:
+		misuse(entry, "in_base is NULL");
+	case MERGE_NEGATIVE_BASE:
+		misuse(entry, "the base of part" + img(at) + " is negative");
+	case MERGE_BAD_PART:
+		misuse(entry, "part" + img(at) + " is not an index");
+	case MERGE_NOT_RISING:
+		misuse(entry, "part" + img(at) + " begins at" + img(in_base[at]) + ", inside or in front of the part before it");
+	case MERGE_PAST_END:
+		misuse(entry, "part" + img(at) + " ends past in_len," + img(in_len));
+	}
+	// one dictionary, or none: by its used length here, by its bytes on the device
+	const lz4ada_seek_index* ref = nullptr;  // the first part with frames
+	uint32_t ref_at = 0;
+	bool anyck = false;
+	for (int64_t p = 0; p < nparts; ++p) {
+		const lz4ada_seek_index& q = *parts[p];
+		if (q.pos.empty())
+			continue;
+		if (!ref) {
+			ref = &q;
+			ref_at = uint32_t(p);
+		}
+		if (q.dict.used != ref->dict.used)
+			misuse(entry, "part" + img(p) + " holds a dictionary of" + img(q.dict.used) + " bytes, part" + img(ref_at) +
+			                  " one of" + img(ref->dict.used) + ": one dictionary for all parts, or none");
+		anyck |= !q.kgrp.empty();
+	}
+	const size_t np = size_t(nparts), stride = np + 1;
+	std::vector<uint64_t> pre(MERGE_PREFIXES * stride);
+	if (!merge_plan(shape.data(), nparts, pre.data()))
+		raise(LZ4ADA_CONSTRAINT_ERROR, "the parts hold more jobs or blocks than a seek index takes");
+	const uint64_t *const pre_f = &pre[MERGE_FRAMES * stride], *const pre_b = &pre[MERGE_BLOCKS * stride],
+	               *const pre_c = &pre[MERGE_CKPTS * stride];
+	const size_t n = size_t(pre_f[np]);
+	const uint64_t nb = pre_b[np], nck = pre_c[np];
+	std::unique_ptr<lz4ada_seek_index> x(new lz4ada_seek_index);
+	x->in_len = in_len;
+	if (n == 0) {  // nothing to hold: no device call
+		*idx = x.release();
+		return;
+	}
+	// the host's vectors: by job, and by sorted position (a part's sorted
+	// positions are kept, shifted by the frames before it)
+	x->slots = pre[MERGE_SLOTS * stride + np];
+	x->pos.reserve(n);
+	x->reason.reserve(n);
+	x->size.reserve(n);
+	x->first.reserve(n + 1);
+	if (anyck) {
+		x->kgrp.reserve(n);
+		x->ckfirst.reserve(n + 1);
+	}
+	if (ref->dict.used)
+		x->kind.reserve(n);
+	for (size_t p = 0; p < np; ++p) {
+		const lz4ada_seek_index& q = *parts[p];
+		const size_t m = q.pos.size();
+		for (size_t j = 0; j < m; ++j)
+			x->pos.push_back(uint32_t(pre_f[p] + q.pos[j]));
+		x->reason.insert(x->reason.end(), q.reason.begin(), q.reason.end());
+		x->size.insert(x->size.end(), q.size.begin(), q.size.end());
+		for (size_t k = 0; k < m; ++k) {
+			x->first.push_back(pre_b[p] + q.first[k]);
+			if (anyck) {
+				x->kgrp.push_back(q.kgrp.empty() ? 0 : q.kgrp[k]);
+				x->ckfirst.push_back(pre_c[p] + (q.ckfirst.empty() ? 0 : q.ckfirst[k]));
+			}
+			if (ref->dict.used)
+				x->kind.push_back(q.kind.empty() ? uint8_t(CHAIN_KIND_NONE) : q.kind[k]);
+		}
+		x->linked |= q.linked;
+	}
+	x->first.push_back(nb);
+	if (anyck)
+		x->ckfirst.push_back(nck);
+	// the device's arrays, in the builds' layouts
+	device_check_or_raise();
+	if (ref->dict.used)
+		copy_dict_image(*x, *ref, s);
+	const IndexArrays a = alloc_index(*x, nb, n);
+	MergeOut o{};
+	o.desc = a.d_desc;
+	o.first = a.d_first;
+	o.start = x->d_start;
+	o.slotp = a.d_slotp;
+	o.fkind = a.d_kind;
+	o.nblocks = nb;
+	o.nframes = uint32_t(n);
+	if (anyck) {
+		const CkptArrays c = alloc_checkpoints(*x, nck, n);
+		o.kgrp = c.d_kgrp;
+		o.ckfirst = c.d_ckfirst;
+		o.store = c.d_store;
+		o.nckpt = nck;
+	}
+	// the part table, in one copy: the parts | the prefixes | the comparison's flag
+	const size_t part_b = np * sizeof(MergePartDev), pre_b8 = pre.size() * 8, tab_b = part_b + pre_b8 + 8;
+	uint8_t* const d_tab = scratch(SC_SEEK, tab_b);
+	if (!d_tab)
+		raise(LZ4ADA_DEVICE_ERROR, "no device memory for the part table");
+	PinBuf& h = scratch_cache().pin;
+	h.reserve(tab_b);
+	MergePartDev* const w = reinterpret_cast<MergePartDev*>(h.p);
+	for (size_t p = 0; p < np; ++p) {
+		const lz4ada_seek_index& q = *parts[p];
+		MergePartDev d{};
+		if (!q.pos.empty()) {
+			const SeekView& v = q.view;
+			d = MergePartDev{ v.desc, v.first, v.start, v.slotp, v.kgrp, v.ckfirst, v.fkind, v.store, v.dict,
+				          uint64_t(in_base[p]) };
+		}
+		w[p] = d;
+	}
+	memcpy(h.p + part_b, pre.data(), pre_b8);
+	memset(h.p + part_b + pre_b8, 0, 8);
+	HIP_OK(hipMemcpyAsync(d_tab, h.p, tab_b, hipMemcpyHostToDevice, s));
+	MergeTable t{};
+	t.part = reinterpret_cast<const MergePartDev*>(d_tab);
+	t.pre = reinterpret_cast<const uint64_t*>(d_tab + part_b);
+	t.nparts = uint32_t(np);
+	uint32_t* const d_flag = reinterpret_cast<uint32_t*>(d_tab + part_b + pre_b8);
+	HIP_OK(launch_index_merge(t, o, s));
+	if (ref->dict.used)
+		HIP_OK(launch_index_merge_dict_eq(t, ref_at, ref->dict.gap, d_flag, s));
+	// the call's one host synchronisation: the index is complete, and the flag
+	uint32_t* const flag = reinterpret_cast<uint32_t*>(h.p + part_b + pre_b8);
+	HIP_OK(hipMemcpyAsync(flag, d_flag, 4, hipMemcpyDeviceToHost, s));
+	HIP_OK(hipStreamSynchronize(s));
+	if (*flag)
+		misuse(entry, "the parts' dictionaries differ in their bytes: one dictionary for all parts, or none");
+	*idx = x.release();
+}
 
 }  // namespace
 }  // namespace lz4ada
@@ -1042,6 +1224,84 @@ int lz4ada_seek_index_store_debug(const lz4ada_seek_index* idx, void* store, int
 		if (store_cap < int64_t(idx->view.nckpt * CKPT_BYTES))
 			raise(LZ4ADA_CONSTRAINT_ERROR, "store capacity exceeded");
 		d2h(store, idx->view.store, size_t(idx->view.nckpt * CKPT_BYTES), static_cast<hipStream_t>(stream));
+	});
+}
+
+int lz4ada_seek_index_concat(const lz4ada_seek_index* const* parts, const int64_t* in_base, int64_t nparts,
+                             int64_t in_len, lz4ada_seek_index** idx, void* stream)
+{
+	if (idx)
+		*idx = nullptr;
+	batch_stats() = lz4ada_batch_stats{};
+	return guarded(nullptr, [&] {
+		if (nparts >= (int64_t(1) << 31))
+			raise(LZ4ADA_CONSTRAINT_ERROR, "lz4ada_seek_index_concat: more parts than a seek index takes jobs");
+		concat_index("lz4ada_seek_index_concat", parts, in_base, nparts, in_len, idx, static_cast<hipStream_t>(stream));
+	});
+}
+
+int lz4ada_index_merge_plan_host(const int64_t* n, const int64_t* nb, const int64_t* nck, const int64_t* part_len,
+                                 const int64_t* slots, const int64_t* in_base, int64_t nparts, int64_t in_len,
+                                 uint64_t* prefix, const int64_t* kind, const int64_t* elem, int64_t nq,
+                                 int64_t* part_of)
+{
+	if (nparts < 0 || nparts >= (int64_t(1) << 31) || nq < 0 || !prefix ||
+	    (nparts > 0 && (!n || !nb || !nck || !part_len || !slots || !in_base)) ||
+	    (nq > 0 && (!kind || !elem || !part_of)))
+		return LZ4ADA_ASSERTION_ERROR;
+	std::vector<MergePart> shape(static_cast<size_t>(nparts));
+	for (int64_t p = 0; p < nparts; ++p)
+		shape[size_t(p)] = MergePart{ n[p], nb[p], nck[p], part_len[p], slots[p] };
+	int64_t at = 0;
+	if (merge_validate(shape.data(), in_base, nparts, in_len, &at) != MERGE_OK)
+		return LZ4ADA_ASSERTION_ERROR;
+	if (!merge_plan(shape.data(), nparts, prefix))
+		return LZ4ADA_CONSTRAINT_ERROR;
+	const uint64_t stride = uint64_t(nparts) + 1;
+	for (int64_t q = 0; q < nq; ++q) {
+		if (kind[q] < 0 || kind[q] >= MERGE_PREFIXES || elem[q] < 0)
+			return LZ4ADA_ASSERTION_ERROR;
+		const uint64_t* const pre = prefix + uint64_t(kind[q]) * stride;
+		if (uint64_t(elem[q]) >= pre[nparts])
+			return LZ4ADA_ASSERTION_ERROR;
+		part_of[q] = int64_t(merge_part_of(pre, uint64_t(nparts), uint64_t(elem[q])));
+	}
+	return LZ4ADA_OK;
+}
+
+int lz4ada_seek_index_arrays_debug(const lz4ada_seek_index* idx, int64_t* nframes, int64_t* nblocks, int64_t* nckpt,
+                                   int32_t* has_ckpt, int32_t* has_kind, lz4ada_block_desc* desc, uint64_t* first,
+                                   uint64_t* start, uint64_t* slotp, uint64_t* kgrp, uint64_t* ckfirst,
+                                   uint64_t* fkind, void* stream)
+{
+	return guarded(nullptr, [&] {
+		if (!idx || !nframes || !nblocks || !nckpt || !has_ckpt || !has_kind)
+			misuse("lz4ada_seek_index_arrays_debug", "idx or a count is NULL");
+		const size_t n = idx->pos.size();
+		const uint64_t nb = n ? idx->first[n] : 0;
+		const SeekView& v = idx->view;
+		*nframes = int64_t(n);
+		*nblocks = int64_t(nb);
+		*nckpt = int64_t(v.nckpt);
+		*has_ckpt = v.kgrp != nullptr;
+		*has_kind = v.fkind != nullptr;
+		if (n == 0)
+			return;
+		hipStream_t s = static_cast<hipStream_t>(stream);
+		if (desc && nb)
+			d2h(desc, v.desc, size_t(nb) * sizeof(lz4ada_block_desc), s);
+		if (first)
+			d2h(first, v.first, (n + 1) * 8, s);
+		if (start)
+			d2h(start, v.start, (size_t(nb) + n) * 8, s);
+		if (slotp)
+			d2h(slotp, v.slotp, (size_t(nb) + n) * 8, s);
+		if (kgrp && v.kgrp)
+			d2h(kgrp, v.kgrp, n * 8, s);
+		if (ckfirst && v.ckfirst)
+			d2h(ckfirst, v.ckfirst, (n + 1) * 8, s);
+		if (fkind && v.fkind)
+			d2h(fkind, v.fkind, n * 8, s);
 	});
 }
 

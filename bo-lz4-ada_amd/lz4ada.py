@@ -330,6 +330,12 @@ _sig = {
                                     ctypes.c_uint64, _vp, _vp, _i64, _pi64, ctypes.POINTER(ctypes.c_int32), _pi64,
                                     _pi64], ctypes.c_int),
     "lz4ada_seek_index_store_debug": ([_vp, _vp, _i64, _pi64, _vp], ctypes.c_int),
+    "lz4ada_seek_index_concat": ([_vp, _vp, _i64, _i64, ctypes.POINTER(_vp), _vp], ctypes.c_int),
+    "lz4ada_index_merge_plan_host": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp],
+                                     ctypes.c_int),
+    "lz4ada_seek_index_arrays_debug": ([_vp, _pi64, _pi64, _pi64, ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_int32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                                       ctypes.c_int),
     "lz4ada_compress_frame_dict_host": ([_vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _i64],
                                         _i64),
     "lz4ada_abi_version": ([], ctypes.c_int),
@@ -1106,6 +1112,32 @@ class SeekIndex:
             return cls.build(t.data_ptr(), t.numel(), spans, torch.cuda.current_stream().cuda_stream,
                              linked=linked, checkpoint_bytes=checkpoint_bytes, dict=dd)
 
+    @classmethod
+    def concat(cls, parts, bases, in_len: int, stream: int = 0):
+        """The indexes `parts` (SeekIndex objects, e.g. one per compress call)
+        laid into one index over an input of in_len bytes in which the input
+        of parts[p] lies at bases[p] (lz4ada_seek_index_concat, DESIGN.md
+        §23).  Job j of parts[p] is job (jobs of the parts before) + j of the
+        result; .jobs is the parts' reports in that order with in_off grown by
+        the base.  The parts stay as they are and may be freed at once."""
+        parts, bases = list(parts), list(bases)
+        if len(parts) != len(bases):
+            raise ValueError("one base per part")
+        arr = (_vp * max(len(parts), 1))(*[p._ptr for p in parts])
+        base = (_i64 * max(len(parts), 1))(*bases)
+        ptr = _vp()
+        _check(_lib.lz4ada_seek_index_concat(arr, base, len(parts), in_len, ctypes.byref(ptr), stream),
+               _thread_error())
+        njobs = sum(p.njobs for p in parts)
+        jobs = (DeviceFrameJob * max(njobs, 1))()
+        at = 0
+        for p, b in zip(parts, bases):
+            for i in range(p.njobs):
+                ctypes.memmove(ctypes.byref(jobs[at]), ctypes.byref(p.jobs[i]), ctypes.sizeof(DeviceFrameJob))
+                jobs[at].in_off += b
+                at += 1
+        return cls(ptr.value, jobs, njobs, in_len)
+
     @property
     def device_bytes(self) -> int:
         return int(_lib.lz4ada_seek_index_bytes(self._ptr))
@@ -1287,6 +1319,62 @@ def seek_index_store_debug(idx: SeekIndex, stream: int = 0) -> bytes:
     _check(_lib.lz4ada_seek_index_store_debug(idx._ptr, buf, n.value * 65536, ctypes.byref(n), stream),
            _thread_error())
     return buf.raw[:n.value * 65536]
+
+
+def seek_index_arrays_debug(idx: SeekIndex, stream: int = 0):
+    """Test-only: the index's device arrays copied to the host -> a dict:
+    nframes, nblocks, nckpt, desc (a tuple of its six fields per block), first,
+    start, slotp, and kgrp, ckfirst / fkind as lists, or None where the index
+    holds none."""
+    n, nb, nck = _i64(), _i64(), _i64()
+    has_ck, has_kind = ctypes.c_int32(), ctypes.c_int32()
+
+    def call(*arrays):
+        _check(_lib.lz4ada_seek_index_arrays_debug(idx._ptr, ctypes.byref(n), ctypes.byref(nb), ctypes.byref(nck),
+                                                   ctypes.byref(has_ck), ctypes.byref(has_kind), *arrays, stream),
+               _thread_error())
+    call(*[None] * 7)
+    u64 = ctypes.c_uint64
+    desc = (BlockDesc * max(nb.value, 1))()
+    first, ckfirst = (u64 * (n.value + 1))(), (u64 * (n.value + 1))()
+    start, slotp = (u64 * max(nb.value + n.value, 1))(), (u64 * max(nb.value + n.value, 1))()
+    kgrp, fkind = (u64 * max(n.value, 1))(), (u64 * max(n.value, 1))()
+    call(desc, first, start, slotp, kgrp, ckfirst, fkind)
+    held = n.value > 0
+    return _dict(nframes=n.value, nblocks=nb.value, nckpt=nck.value,
+                 desc=[(d.in_off, d.in_len, d.flags, d.out_off, d.out_cap, d.cksum) for d in desc[:nb.value]],
+                 first=list(first) if held else None,
+                 start=list(start[:nb.value + n.value]) if held else None,
+                 slotp=list(slotp[:nb.value + n.value]) if held else None,
+                 kgrp=list(kgrp[:n.value]) if has_ck.value else None,
+                 ckfirst=list(ckfirst) if has_ck.value else None,
+                 fkind=list(fkind[:n.value]) if has_kind.value else None)
+
+
+MERGE_PREFIX_NAMES = ("frames", "blocks", "words", "checkpoints", "slots")
+
+
+def index_merge_plan_host(parts, bases, in_len: int, queries=()):
+    """Test-only: the merge rule on the host (lz4ada_index_merge.h, no GPU
+    involved).  parts: [(jobs, blocks, checkpoints, input length, nominal
+    slots)]; bases: where each part's input lies in an input of in_len bytes;
+    queries: [(prefix 0..4, merged element)] -> (the five exclusive prefixes as
+    lists of len(parts) + 1, in MERGE_PREFIX_NAMES' order; the part of every
+    query).  AssertionFailure for what lz4ada_seek_index_concat calls misuse,
+    ConstraintError from 2^31 jobs or blocks."""
+    parts, bases, queries = list(parts), list(bases), list(queries)
+    if len(parts) != len(bases):
+        raise ValueError("one base per part")
+    m, nq = len(parts), len(queries)
+    cols = [(_i64 * max(m, 1))(*[p[k] for p in parts]) for k in range(5)]
+    base = (_i64 * max(m, 1))(*bases)
+    prefix = (ctypes.c_uint64 * (5 * (m + 1)))()
+    kind = (_i64 * max(nq, 1))(*[q[0] for q in queries])
+    elem = (_i64 * max(nq, 1))(*[q[1] for q in queries])
+    part_of = (_i64 * max(nq, 1))()
+    _check(_lib.lz4ada_index_merge_plan_host(*cols, base, m, in_len, prefix, kind, elem, nq, part_of),
+           "lz4ada_index_merge_plan_host: parts that do not rise inside in_len, a query out of range, or too many jobs")
+    return [list(prefix[k * (m + 1):(k + 1) * (m + 1)]) for k in range(5)], list(part_of[:nq])
 
 
 def ranges_select_debug(idx: SeekIndex, ranges, stream: int = 0):

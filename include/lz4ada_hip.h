@@ -1234,6 +1234,88 @@ int lz4ada_compress_index_host(const uint8_t *frame, int64_t frame_len, int64_t 
 int lz4ada_seek_index_store_debug(const lz4ada_seek_index *idx, void *store, int64_t store_cap,
                                   int64_t *nckpt, void *stream);
 
+/* ------------------------------- the indexes of several calls, laid into one */
+/*
+ * A record store grows batch by batch, and every compress call (or build)
+ * returns an index of its own, while a ranged call takes one index over one
+ * input.  lz4ada_seek_index_concat makes that one index
+ * without reading a frame byte or decoding anything: every piece an index holds
+ * is relative to its frame or is an offset that one constant per part rebases.
+ *
+ * On success *idx is a new index over an input of in_len bytes in which the
+ * input that part p was made over lies at [in_base[p], in_base[p] + its
+ * in_len).  Job j of part p is job (jobs of parts 0 .. p-1) + j of the result.
+ * The result holds what one index over the whole input would hold, array for
+ * array -- when the parts come from compress calls over consecutive groups of
+ * records, the index one call over all the records writes -- and is an
+ * ordinary index: lz4ada_decode_ranges_device (which demands the new in_len),
+ * lz4ada_seek_index_bytes, _free, _debug, _store_debug and
+ * lz4ada_ranges_select_debug take it, and it may be a part of a later concat.
+ * lz4ada_seek_index_bytes is the formulas above over the sums: nb, n and C
+ * summed over the parts, the LZ4ADA_SEEK_LINKED line when any part has it, the
+ * dictionary line once.
+ *
+ * Parts are not modified and not consumed; a part may serve ranged calls on
+ * other threads meanwhile, and may be freed as soon as the call returns: the
+ * result owns copies of everything, the dictionary image and the checkpoints
+ * included.  A part's jobs need not lie in rising in_off (a built index): its
+ * sorted positions are kept, shifted by the frames before it.  Linked and
+ * unlinked parts may be mixed: if any part holds checkpoint arrays the result
+ * does, and the frames of parts without them get K = 0 and no checkpoint, as
+ * an LZ4ADA_SEEK_LINKED build gives independent frames.  A part with no job
+ * contributes nothing; if all are such, or nparts == 0, the result is an empty
+ * index over in_len and no device call is made.  The same part may be named
+ * twice (two copies of its frames in the input).
+ *
+ * Dictionaries: either no part with jobs holds one or every one does, and then
+ * all hold the same -- the same dict_used and the same image bytes.  A mix, or
+ * another dict_used, is LZ4ADA_ASSERTION_ERROR before any device call.  Other
+ * bytes are found by a comparison on the device whose flag the host reads at
+ * the call's one synchronisation: LZ4ADA_ASSERTION_ERROR then too, after the
+ * kernels ran, with *idx NULL and the parts as they were.
+ *
+ * Misuse, LZ4ADA_ASSERTION_ERROR before any device call with *idx NULL: a NULL
+ * idx; NULL parts or in_base with nparts > 0; a NULL part; nparts < 0;
+ * in_len < 0; a negative base; in_base[p] < in_base[p-1] + the in_len of part
+ * p-1 (parts rise and stay apart; touching and gaps are fine); a part that
+ * ends past in_len.  2^31 jobs or blocks in all, or more:
+ * LZ4ADA_CONSTRAINT_ERROR, as the builds.
+ *
+ * Synchronous on stream.  One copy takes the part table up, a fixed number of
+ * launches follows whatever nparts is, and the call makes exactly one host
+ * synchronisation, at its end, after which the index never changes.
+ * lz4ada_last_batch_stats() is all zero.
+ */
+int lz4ada_seek_index_concat(const lz4ada_seek_index *const *parts, const int64_t *in_base,
+                             int64_t nparts, int64_t in_len, lz4ada_seek_index **idx,
+                             void *stream);
+/* Test-only.  The merge rule on the host (lz4ada_index_merge.h, what the concat
+ * validates and sums by and its kernels look parts up with): parts given by
+ * their jobs n[], blocks nb[], checkpoints nck[], input lengths part_len[] and
+ * nominal slots slots[], at in_base[] of an input of in_len bytes.  prefix (5 *
+ * (nparts + 1) entries) gets the exclusive prefixes of frames, blocks, blocks +
+ * frames, checkpoints and nominal slots, one after the other.  part_of[q]: the
+ * part that merged element elem[q] of prefix kind[q] (0 .. 4) belongs to.
+ * LZ4ADA_ASSERTION_ERROR for what the concat calls misuse and for a query
+ * outside its prefix's total, LZ4ADA_CONSTRAINT_ERROR from 2^31 jobs or blocks.
+ * Host only, no HIP call. */
+int lz4ada_index_merge_plan_host(const int64_t *n, const int64_t *nb, const int64_t *nck,
+                                 const int64_t *part_len, const int64_t *slots,
+                                 const int64_t *in_base, int64_t nparts, int64_t in_len,
+                                 uint64_t *prefix, const int64_t *kind, const int64_t *elem,
+                                 int64_t nq, int64_t *part_of);
+/* Test-only.  An index's device arrays copied to the host.  *nframes, *nblocks,
+ * *nckpt: its counts; *has_ckpt / *has_kind: whether it holds kgrp and ckfirst
+ * / fkind.  Each array may be NULL (call once for the counts); the caller gives
+ * room for nblocks descriptors, nframes + 1 entries of first and ckfirst,
+ * nblocks + nframes of start and slotp, nframes of kgrp and fkind.  An index
+ * without jobs holds no array. */
+int lz4ada_seek_index_arrays_debug(const lz4ada_seek_index *idx, int64_t *nframes,
+                                   int64_t *nblocks, int64_t *nckpt, int32_t *has_ckpt,
+                                   int32_t *has_kind, lz4ada_block_desc *desc, uint64_t *first,
+                                   uint64_t *start, uint64_t *slotp, uint64_t *kgrp,
+                                   uint64_t *ckfirst, uint64_t *fkind, void *stream);
+
 /* The bulk path keeps its large device scratch (output slots, linked-frame
  * decode copies) per thread between calls; this frees the calling thread's,
  * and empties the process-wide device / pinned memory pools and the stream
