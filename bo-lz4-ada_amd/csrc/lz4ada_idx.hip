@@ -35,6 +35,13 @@
 // before the block start, an oversize block) are redone by k_decode_pc,
 // which produces the exact statuses; so this pair never changes a result,
 // only the speed.
+//
+// One translation unit in parts, included below in order:
+// lz4ada_idx_input.inc (input access, sequence parsing), lz4ada_idx_pass1.inc
+// (pass 1), lz4ada_idx_window.inc (pass 2's LDS output window and
+// ring-sourced matches) and lz4ada_idx_pair.inc (k_decode_pp2).  This file
+// keeps the straight-to-HBM path, the stages both block decoders share,
+// decode_block, decode_chain, the k_decode_idx* kernels and the launchers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -140,746 +147,8 @@ __device__ unsigned long long g_idx_gathers[4];  // loads, line touches, batches
 #define GCOUNT(i, v)
 #endif
 
-// ---------------------------------------------------------------- byte access
-// Block-relative byte p comes from LDS when [p, p+8) lies in the staged
-// window [lo, hi), else from global memory (guarded by the frame end).
-struct Src {
-	const uint8_t* lds;  // LDS array; block-relative p at lds[(p + mis) & mask]
-	uint32_t mask;       // LDS array size - 1 (power of two; a 16-byte mirror follows)
-	int32_t mis;
-	int32_t lo, hi;
-	cg8* in;
-	uintptr_t lim;
-};
-
-__device__ __forceinline__ uint32_t fetch4(const Src& S, int32_t p)
-{
-	if (p >= S.lo && p + 8 <= S.hi) {
-		const uint32_t a = uint32_t(p + S.mis) & S.mask;
-		const uint32_t* w = reinterpret_cast<const uint32_t*>(S.lds + (a & ~3u));
-		const uint32_t w0 = w[0], w1 = w[1];  // w[1] may be in the mirror
-		return __builtin_amdgcn_alignbyte(w1, w0, a & 3u);
-	}
-	const uintptr_t g = reinterpret_cast<uintptr_t>(S.in) + uintptr_t(intptr_t(p));
-	uint32_t v = 0;
-#pragma unroll
-	for (int i = 0; i < 4; ++i)
-		if (g + i < S.lim)
-			v |= uint32_t(*reinterpret_cast<cg8*>(g + i)) << (8 * i);
-	// settle this rare path's loads here: left pending, they make every
-	// merge after it (the walk loops' heads) wait for all memory, the
-	// in-flight next-chunk prefetch included
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-	return v;
-}
-
-// 16 bytes at byte a of a power-of-two LDS ring (mask = size - 1): three
-// 8-byte-aligned ds_read_b64 (each wrapped on its own), a one-bit dword
-// select and four v_alignbyte -- ld16u's select network costs ~4x the VALU.
-__device__ __forceinline__ u32x4 ring16(const uint8_t* base, uint32_t a, uint32_t mask)
-{
-	const uint32_t a8 = a & ~7u;
-	const uint64_t q0 = *reinterpret_cast<const uint64_t*>(base + (a8 & mask));
-	const uint64_t q1 = *reinterpret_cast<const uint64_t*>(base + ((a8 + 8) & mask));
-	const uint64_t q2 = *reinterpret_cast<const uint64_t*>(base + ((a8 + 16) & mask));
-	const uint32_t w0 = uint32_t(q0), w1 = uint32_t(q0 >> 32), w2 = uint32_t(q1),
-	               w3 = uint32_t(q1 >> 32), w4 = uint32_t(q2), w5 = uint32_t(q2 >> 32);
-	const bool s1 = (a & 4u) != 0;
-	const uint32_t d0 = s1 ? w1 : w0, d1 = s1 ? w2 : w1, d2 = s1 ? w3 : w2, d3 = s1 ? w4 : w3,
-	               d4 = s1 ? w5 : w4;
-	const uint32_t sh = a & 3u;
-	u32x4 v;
-	v.x = __builtin_amdgcn_alignbyte(d1, d0, sh);
-	v.y = __builtin_amdgcn_alignbyte(d2, d1, sh);
-	v.z = __builtin_amdgcn_alignbyte(d3, d2, sh);
-	v.w = __builtin_amdgcn_alignbyte(d4, d3, sh);
-	return v;
-}
-
-// 16 bytes at block-relative p (literal source): LDS or global.
-__device__ __forceinline__ u32x4 fetch16(const Src& S, int32_t p)
-{
-	if (p >= S.lo && p + 16 <= S.hi)
-		return ring16(S.lds, uint32_t(p + S.mis) & S.mask, S.mask);
-	const uintptr_t g = reinterpret_cast<uintptr_t>(S.in) + uintptr_t(intptr_t(p));
-	u32x4 v;
-	if (g + 16 <= S.lim) {
-		__builtin_memcpy(&v, reinterpret_cast<cg8*>(g), 16);
-	} else {
-		uint8_t t[16];
-		for (int i = 0; i < 16; ++i)
-			t[i] = (g + i < S.lim) ? *reinterpret_cast<cg8*>(g + i) : 0;
-		__builtin_memcpy(&v, t, 16);
-	}
-	// settle the rare global read here (see fetch4): otherwise every use of
-	// the LDS path's result waits for all memory -- the batch's in-flight
-	// HBM match loads and flush stores included
-	__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-	return v;
-}
-
-struct Seq {
-	int32_t lit, L, off, ml, next;  // ml = 0: literal-only last sequence
-};
-
-// One sequence at block-relative p < n (Decompress_Sequence,
-// lz4ada.adb:737-777, with the end-of-block rule of :748-764).  False on
-// any malformed shape; the caller then declines the block.
-__device__ __forceinline__ bool parse_seq(const Src& S, int32_t p, int32_t n, Seq& q)
-{
-	const uint32_t w = fetch4(S, p);
-	const int32_t tk = int32_t(w & 0xffu);
-	int32_t L = tk >> 4, M = tk & 15, x = p + 1;
-	if (L == 15) {
-		uint32_t e, k = 1, ww = w;
-		do {
-			if (x >= n || L > n)
-				return false;
-			if (k > 3) {
-				ww = fetch4(S, x);
-				k = 0;
-			}
-			e = (ww >> (8 * k)) & 0xffu;
-			++k;
-			++x;
-			L += int32_t(e);
-		} while (e == 255u);
-	}
-	q.lit = x;
-	q.L = L;
-	x += L;
-	if (x >= n) {
-		if (x > n || M != 0)
-			return false;
-		q.off = 0;
-		q.ml = 0;
-		q.next = n;
-		return true;
-	}
-	if (x + 1 >= n)
-		return false;
-	uint32_t w2 = fetch4(S, x);
-	q.off = int32_t(w2 & 0xffffu);
-	if (q.off == 0)
-		return false;
-	x += 2;
-	if (M == 15) {
-		uint32_t e, k = 2;
-		do {
-			if (x >= n || M > MAX_RUN)
-				return false;
-			if (k > 3) {
-				w2 = fetch4(S, x);
-				k = 0;
-			}
-			e = (w2 >> (8 * k)) & 0xffu;
-			++k;
-			++x;
-			M += int32_t(e);
-		} while (e == 255u);
-	}
-	q.ml = M + 4;
-	q.next = x;
-	return true;
-}
-
-// parse_seq for the common shape, without branches: both length
-// extensions at most one byte, every byte read in the LDS window, the
-// sequence well before the block end.  Anything else (and malformed data)
-// takes parse_seq; the result is the same.
-__device__ __forceinline__ bool parse_fast(const Src& S, int32_t p, int32_t n, Seq& q)
-{
-	const uint32_t a = uint32_t(p + S.mis) & S.mask;
-	const uint32_t* wa = reinterpret_cast<const uint32_t*>(S.lds + (a & ~3u));
-	const uint32_t w = __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
-	const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
-	const bool x1 = tk >= 0xf0u, x2 = (tk & 15u) == 15u;
-	const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
-	const int32_t lit = p + 1 + (x1 ? 1 : 0);
-	const int32_t x = lit + L;
-	const uint32_t b = uint32_t(x + S.mis) & S.mask;
-	const uint32_t* wb = reinterpret_cast<const uint32_t*>(S.lds + (b & ~3u));
-	const uint32_t w2 = __builtin_amdgcn_alignbyte(wb[1], wb[0], b & 3u);
-	const uint32_t e2 = (w2 >> 16) & 0xffu;
-	q.lit = lit;
-	q.L = L;
-	q.off = int32_t(w2 & 0xffffu);
-	q.ml = int32_t(tk & 15u) + 4 + (x2 ? int32_t(e2) : 0);
-	q.next = x + 2 + (x2 ? 1 : 0);
-	const bool ok = p >= S.lo && x + 8 <= S.hi && x + 8 <= n && !(x1 && e1 == 255u) &&
-	                !(x2 && e2 == 255u) && q.off != 0;
-	if (__builtin_expect(ok, 1))
-		return true;
-	return parse_seq(S, p, n, q);
-}
-
-// parse_fast's branch-free form alone: false where it does not apply (the
-// caller then runs parse_seq for that sequence; q is a placeholder)
-__device__ __forceinline__ bool parse_fast_try(const Src& S, int32_t p, int32_t n, Seq& q)
-{
-	const uint32_t a = uint32_t(p + S.mis) & S.mask;
-	const uint32_t* wa = reinterpret_cast<const uint32_t*>(S.lds + (a & ~3u));
-	const uint32_t w = __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
-	const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
-	const bool x1 = tk >= 0xf0u, x2 = (tk & 15u) == 15u;
-	const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
-	const int32_t lit = p + 1 + (x1 ? 1 : 0);
-	const int32_t x = lit + L;
-	const uint32_t b = uint32_t(x + S.mis) & S.mask;
-	const uint32_t* wb = reinterpret_cast<const uint32_t*>(S.lds + (b & ~3u));
-	const uint32_t w2 = __builtin_amdgcn_alignbyte(wb[1], wb[0], b & 3u);
-	const uint32_t e2 = (w2 >> 16) & 0xffu;
-	q.lit = lit;
-	q.L = L;
-	q.off = int32_t(w2 & 0xffffu);
-	q.ml = int32_t(tk & 15u) + 4 + (x2 ? int32_t(e2) : 0);
-	q.next = x + 2 + (x2 ? 1 : 0);
-	return p >= S.lo && x + 8 <= S.hi && x + 8 <= n && !(x1 && e1 == 255u) && !(x2 && e2 == 255u) &&
-	       q.off != 0;
-}
-
-
-// 16 bytes from global memory at byte address a, never reading at or past lim.
-__device__ __forceinline__ u32x4 gload16(uintptr_t a, uintptr_t lim)
-{
-	u32x4 v;
-	if (a + 16 <= lim) {
-		__builtin_memcpy(&v, reinterpret_cast<cg8*>(a), 16);
-	} else {
-		uint8_t t[16];
-		for (int i = 0; i < 16; ++i)
-			t[i] = (a + i < lim) ? *reinterpret_cast<cg8*>(a + i) : 0;
-		__builtin_memcpy(&v, t, 16);
-	}
-	return v;
-}
-
-// Exact-length store of n (0..16) bytes to global memory.
-__device__ __forceinline__ void gstore_n(g8* dst, u32x4 v, int32_t n)
-{
-	if (n >= 16) {
-		__builtin_memcpy(dst, &v, 16);
-		return;
-	}
-	uint64_t lo = uint64_t(v.x) | (uint64_t(v.y) << 32);
-	const uint64_t hi = uint64_t(v.z) | (uint64_t(v.w) << 32);
-	if (n & 8) {
-		__builtin_memcpy(dst, &lo, 8);
-		dst += 8;
-		lo = hi;
-	}
-	if (n & 4) {
-		const uint32_t x = uint32_t(lo);
-		__builtin_memcpy(dst, &x, 4);
-		dst += 4;
-		lo >>= 32;
-	}
-	if (n & 2) {
-		const uint16_t x = uint16_t(lo);
-		__builtin_memcpy(dst, &x, 2);
-		dst += 2;
-		lo >>= 16;
-	}
-	if (n & 1)
-		*dst = uint8_t(lo);
-}
-
-// ------------------------------------------------------------------ pass 1
-
-// the 16-bit output counts of a lane's records: two to a dword, so the
-// first walk can add into one with a 32-bit LDS add; read and written as
-// halves everywhere else
-typedef uint16_t __attribute__((may_alias)) cnt16;
-typedef uint32_t __attribute__((may_alias)) cnt32;
-
-// Pass 1 runs on the W waves of a block's workgroup (1: k_index and
-// k_decode_idx; 2: k_decode_pp2): 64 * W lanes share each staged chunk.
-template <int W>
-struct Pass1 {
-	static_assert(W == 1 || W == 2, "one or two waves per block");
-	static constexpr int SEG = CHUNK / (64 * W);  // segment per lane
-	static constexpr int NSUB = SEG / SUB;        // index records per segment
-	static constexpr int STRIDE = 16 * 64 * W;    // bytes one 16-byte load per thread covers
-	static constexpr int PF = CHUNK / STRIDE;     // 16-byte loads per thread per chunk
-};
-
-template <int W>
-struct alignas(16) IdxLds {
-	uint8_t buf[CHUNK + 16];                     // staged chunk; + mirror of its first 16 bytes
-	uint32_t rbm[64 * W][Pass1<W>::NSUB + 1];    // each lane's records from its latest walk: start
-	cnt32 rcnt[64 * W][Pass1<W>::NSUB / 2 + 1];  // bitmaps and output bytes (>= 0xFFFF: in HBM)
-	// the exchange words of two waves (no bytes with one)
-	int32_t xa[W - 1];        // wave 0's largest exit (wave 1's lane-0 entry)
-	int32_t xs[W - 1][2][4];  // per wave: largest exit, sequence starts, bad, used sub-segments
-};
-static_assert(sizeof(IdxLds<1>) <= 20480, "8 waves per CU: at most 20 KiB of LDS per wave");
-
-// a lane's counts as halves (record k: half k)
-template <int N>
-__device__ __forceinline__ cnt16* halves(cnt32 (&row)[N])
-{
-	return reinterpret_cast<cnt16*>(row);
-}
-template <int N>
-__device__ __forceinline__ const cnt16* halves(const cnt32 (&row)[N])
-{
-	return reinterpret_cast<const cnt16*>(row);
-}
-
-// Walk the chain from e (an entry at or after this lane's segment start s)
-// over the sequences starting before seg_end; returns the exit (first
-// chain position >= seg_end, or n).  A malformed sequence sets err (epos:
-// its position) and returns seg_end as a guess: from a wrong (speculative)
-// entry that is just a dead chain, and a -1 would poison every lane after
-// it one iteration at a time.
-//
-// Every walk rewrites the segment's NS records (sub-segment k = bytes
-// [s + 32k, s + 32k + 32)) in LDS: rb[k] bit j = a sequence starts at byte
-// j, rc[k] = the output bytes (literals + match) of the sequences starting
-// there.  The lane's last walk -- from the true entry -- leaves the exact
-// records; k_index writes them to HBM once per chunk.  An output count that
-// does not fit 16 bits goes straight to its record's high word in HBM
-// (ghi[2k]; long RLE runs).
-//
-// Re-walk (may_stop: the lane's previous walk, exit y_old, had no error):
-// chains are deterministic, so once this walk reaches a position the
-// previous walk started a sequence at, the rest is the previous walk.  It
-// finishes that sub-segment (its count mixes both walks' sequences) and
-// stops: later records and the exit are the previous walk's.  Chains from a
-// wrong entry merge within ~14 sequences, so a re-walk costs a fraction of
-// a segment.
-template <int NS>
-__device__ __forceinline__ int32_t walk_segment(const Src& S, int32_t e, int32_t s, int32_t seg_end,
-                                                int32_t n, uint32_t* rb, cnt16* rc, uint32_t* ghi,
-                                                bool& err, int32_t& epos, int32_t y_old,
-                                                bool may_stop, int32_t& nst)
-{
-	nst = 0;  // sequence steps (diagnostic counts; dead in the product)
-	err = false;
-	epos = INT32_MAX;
-	auto put = [&](int32_t k, uint32_t b, uint32_t c) {
-		rb[k] = b;
-		rc[k] = uint16_t(min(c, 0xFFFFu));
-		if (c >= 0xFFFFu)
-			ghi[2 * k] = c;
-	};
-	// the dword pair at pos, shifted to pos (LDS; a position outside the
-	// staged window reads garbage, which parse_fast's window test rejects)
-	auto pair_at = [&](int32_t pos) -> uint32_t {
-		const uint32_t a = uint32_t(pos + S.mis) & S.mask;
-		const uint32_t* wa = reinterpret_cast<const uint32_t*>(S.lds + (a & ~3u));
-		return __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
-	};
-	int32_t p = e;
-	int32_t kc = -1, nxt = 0;  // sub-segment being counted; next record to write
-	uint32_t bm = 0, cnt = 0;
-	bool merged = false;
-	uint32_t w = p < seg_end ? pair_at(p) : 0u;  // token pair of the sequence at p
-	while (p < seg_end) {
-		const int32_t k = (p - s) >> 5;
-		if (k != kc) {
-			if (kc >= 0)
-				put(kc, bm, cnt);
-			if (merged)
-				return y_old;
-			for (; nxt < k; ++nxt)
-				if (nxt != kc)
-					put(nxt, 0, 0);
-			nxt = k + 1;
-			kc = k;
-			bm = cnt = 0;
-		}
-		const uint32_t bit = 1u << ((p - s) & 31);
-		if (may_stop && (rb[k] & bit))
-			merged = true;  // rb[k] is still the previous walk's record
-		bm |= bit;
-		++nst;
-		// parse_fast from the token pair in hand; the offset pair at x and
-		// the next sequence's token pair load together (the next position
-		// needs only this token), so a step waits for one LDS round trip
-		const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
-		const bool x1 = tk >= 0xf0u, x2 = (tk & 15u) == 15u;
-		const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
-		const int32_t x = p + 1 + (x1 ? 1 : 0) + L;
-		const int32_t np = x + 2 + (x2 ? 1 : 0);
-		const uint32_t w2 = pair_at(x), wn = pair_at(np);
-		const uint32_t e2 = (w2 >> 16) & 0xffu;
-		Seq q;
-		q.L = L;
-		q.ml = int32_t(tk & 15u) + 4 + (x2 ? int32_t(e2) : 0);
-		q.next = np;
-		const bool ok = p >= S.lo && x + 8 <= S.hi && x + 8 <= n && !(x1 && e1 == 255u) &&
-		                !(x2 && e2 == 255u) && (w2 & 0xffffu) != 0;
-		if (!ok) {  // rare shapes (and malformed data): the exact parse
-			if (!parse_seq(S, p, n, q)) {
-				err = true;
-				epos = p;
-				return seg_end;
-			}
-		}
-		cnt += uint32_t(q.L + q.ml);
-		p = q.next;
-		w = ok ? wn : pair_at(p);
-	}
-	if (kc >= 0)
-		put(kc, bm, cnt);
-	if (!merged)
-		for (; nxt < NS; ++nxt)
-			put(nxt, 0, 0);
-	return p;
-}
-
-// A lane's first walk of a chunk: walk_segment(may_stop = false) from an
-// entry e >= s, leaving exactly the records it would, with the per-step
-// bookkeeping (the sub-segment transition, the zero fill, the merge tests)
-// replaced by two LDS read-modify-writes into rows zeroed up front: the
-// start bit is OR-ed into rb[k], L + ml added to the 16-bit half k of rc
-// (no other lane touches the row, and a wave's LDS operations execute in
-// order).  Positions are buffer offsets (the staged chunk is linear here:
-// byte p at buf[p - S.lo]), so no read wraps; one past the staged bytes
-// returns other LDS contents, which the window test rejects.
-//
-// A sub-segment starts at most 11 sequences the branch-free parse accepts
-// (3 bytes or more each, L <= 269, ml <= 273), so their sum cannot carry
-// out of its half.  The first sequence it rejects (a longer length extension, bytes
-// past the staged window, the block's last sequences, malformed data) ends
-// the adds for its sub-segment: the rest of that sub-segment goes through
-// parse_seq with an exact 32-bit count, stored saturated with the exact
-// value in HBM as walk_segment's put() does.
-template <int NS>
-__device__ __forceinline__ int32_t walk_first(const Src& S, int32_t e, int32_t s, int32_t seg_end,
-                                              int32_t n, uint32_t* rb, cnt32* rc, uint32_t* ghi,
-                                              bool& err, int32_t& epos, int32_t& nst)
-{
-	static_assert(NS % 2 == 0, "two counts to a dword");
-	nst = 0;
-	err = false;
-	epos = INT32_MAX;
-#pragma unroll
-	for (int k = 0; k < NS; ++k)
-		rb[k] = 0;
-#pragma unroll
-	for (int k = 0; k < NS / 2; ++k)
-		rc[k] = 0;
-	const uint8_t* buf = S.lds;
-	auto pair_at = [&](int32_t P) -> uint32_t {
-		const uint32_t a = uint32_t(P);
-		const uint32_t* wa = reinterpret_cast<const uint32_t*>(buf + (a & ~3u));
-		return __builtin_amdgcn_alignbyte(wa[1], wa[0], a & 3u);
-	};
-	const int32_t B = S.lo;
-	const int32_t S0 = s - B, END = seg_end - B;
-	const int32_t LIM8 = min(S.hi, n) - 8 - B;  // the latest x with 8 staged bytes inside the block
-	int32_t P = e - B;                          // e >= s >= S.lo
-	uint32_t w = P < END ? pair_at(P) : 0u;
-	while (P < END) {
-		const uint32_t d = uint32_t(P - S0);
-		const uint32_t k = d >> 5, bit = 1u << (d & 31u);
-		++nst;
-		const uint32_t tk = w & 0xffu, e1 = (w >> 8) & 0xffu;
-		const bool x1 = tk >= 0xf0u, x2 = (tk & 15u) == 15u;
-		const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
-		const int32_t x = P + 1 + (x1 ? 1 : 0) + L;
-		const int32_t np = x + 2 + (x2 ? 1 : 0);
-		// the offset pair at x and the next token pair load together, before
-		// the branch below (left to the compiler, the second read sinks past
-		// it and a step waits for two LDS round trips)
-		const uint32_t w2 = pair_at(x), wn = pair_at(np);
-		asm volatile("" ::"v"(wn));
-		const uint32_t e2 = (w2 >> 16) & 0xffu;
-		const uint32_t c =uint32_t(L) + (tk & 15u) + 4u + (x2 ? e2 : 0u);
-		const bool ok = x <= LIM8 && !(x1 && e1 == 255u) && !(x2 && e2 == 255u) && (w2 & 0xffffu) != 0;
-		if (__builtin_expect(!ok, 0)) {
-			const uint32_t sh = (k & 1u) * 16u;
-			const uint32_t old = (__hip_atomic_load(&rc[k >> 1], __ATOMIC_RELAXED,
-			                                        __HIP_MEMORY_SCOPE_WAVEFRONT) >> sh) & 0xffffu;
-			uint32_t bm = 0, cnt = old;
-			int32_t p = P + B;
-			do {
-				Seq q;
-				if (!parse_seq(S, p, n, q)) {
-					err = true;
-					epos = p;
-					return seg_end;
-				}
-				bm |= 1u << (uint32_t(p - s) & 31u);
-				cnt += uint32_t(q.L + q.ml);
-				p = q.next;
-				if (p < seg_end && uint32_t(p - s) >> 5 == k)
-					++nst;
-				else
-					break;
-			} while (true);
-			__hip_atomic_fetch_or(&rb[k], bm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-			__hip_atomic_fetch_add(&rc[k >> 1], (min(cnt, 0xFFFFu) - old) << sh, __ATOMIC_RELAXED,
-			                       __HIP_MEMORY_SCOPE_WAVEFRONT);
-			if (cnt >= 0xFFFFu)
-				ghi[2 * k] = cnt;
-			P = p - B;
-			w = P < END ? pair_at(P) : 0u;
-			continue;
-		}
-		__hip_atomic_fetch_or(&rb[k], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-		__hip_atomic_fetch_add(&rc[k >> 1], c << ((k & 1u) * 16u), __ATOMIC_RELAXED,
-		                       __HIP_MEMORY_SCOPE_WAVEFRONT);
-		P = np;
-		w = wn;
-	}
-	return P + B;
-}
-
-// The chain position after the sequence at buffer offset P (the staged
-// chunk is linear: byte p at buf[p - S.lo]), for the lead-in walk: only a
-// guess, so no checks, and every length extension taken as one byte (a
-// longer one just makes a wrong guess, which the re-walks fix) -- then the
-// token and the byte after it are all a step reads, with no address
-// arithmetic: the lead-in keeps P itself.
-__device__ __forceinline__ int32_t skip_seq(const uint8_t* buf, int32_t P)
-{
-	const uint32_t tk = buf[P], e1 = buf[P + 1];
-	const int32_t x1 = tk >= 0xf0u ? 1 : 0;
-	const int32_t L = int32_t(tk >> 4) + (x1 ? int32_t(e1) : 0);
-	return P + 3 + x1 + L + ((tk & 15u) == 15u ? 1 : 0);
-}
-
-// The lead-in of a lane whose segment starts at s > C: from `lead` bytes
-// before s (inside the staged chunk), the first guessed chain position >= s.
-__device__ __forceinline__ int32_t lead_in_walk(const Src& S, int32_t C, int32_t s, int32_t lead)
-{
-	const int32_t S0 = s - S.lo;
-	int32_t P = max(s - lead, C) - S.lo;
-	while (P < S0)
-		P = skip_seq(S.lds, P);
-	return P + S.lo;
-}
-
-__device__ __forceinline__ int32_t lead_in_bytes(int32_t starts)
-{
-	const int32_t l = LEAD_SEQ * (CHUNK / max(starts, 1));
-	return __builtin_amdgcn_readfirstlane(min(max(l, LEAD_MIN), LEAD_MAX));
-}
-
-// Pass 1 of block b by the W waves of its workgroup (the body of k_index;
-// the fused kernels run it before pass 2 of the same block: k_decode_idx
-// with one wave, k_decode_pp2 with two).  With two waves, 128 lanes walk
-// each chunk, 128 bytes each: wave 0's lane 0 enters at the exact chain
-// position, wave 1's lane 0 at its lead-in guess until wave 0's exit is
-// known (one LDS exchange per chunk), and the chunk's totals are combined
-// through LDS; one wave keeps everything in registers.
-template <int W>
-__device__ __forceinline__ void index_block(IdxLds<W>& X, const uint8_t* __restrict__ frame,
-                                            uint64_t frame_len,
-                                            const lz4ada_block_desc* __restrict__ desc, uint32_t b,
-                                            uint8_t* __restrict__ tab_all,
-                                            lz4ada_block_status* __restrict__ status)
-{
-	constexpr int SEG = Pass1<W>::SEG, NSUB = Pass1<W>::NSUB, PF = Pass1<W>::PF, STRIDE = Pass1<W>::STRIDE;
-	const int32_t tid = int32_t(threadIdx.x) & (64 * W - 1);  // thread of the block's workgroup
-	const int32_t w = tid >> 6, lane = tid & 63;               // its wave, its lane
-	const lz4ada_block_desc d = desc[b];
-	if (d.flags & LZ4ADA_BLOCK_STORED) {
-		if (tid == 0)
-			status[b].code = DS_OK;
-		return;
-	}
-	if (d.in_len >= RLE_MIN_IN && uint64_t(d.in_len) * RLE_RATIO < uint64_t(d.out_cap)) {
-		if (tid == 0)
-			status[b].code = DS_SPARSE;
-		return;
-	}
-	cg8* in = gptr(frame) + d.in_off;
-	const int32_t n = int32_t(d.in_len);
-	const uintptr_t lim = reinterpret_cast<uintptr_t>(frame) + frame_len;
-	const int32_t mis = int32_t(reinterpret_cast<uintptr_t>(in) & 15u);
-	uint64_t* tab = reinterpret_cast<uint64_t*>(tab_all) + (((d.in_off >> 8) + b) << 3);
-
-	Src S;
-	S.lds = X.buf;
-	S.mask = CHUNK - 1;
-	S.mis = mis;
-	S.in = in;
-	S.lim = lim;
-
-	// 16 KiB chunk at aligned address a (threads: PF x 16 bytes each), the
-	// next one loaded while the current one is walked
-	auto load16k = [&](uintptr_t a, u32x4 (&v)[PF]) {
-		if (a + CHUNK <= lim) {
-#pragma unroll
-			for (int r = 0; r < PF; ++r)
-				__builtin_memcpy(&v[r], reinterpret_cast<cg8*>(a + uintptr_t(STRIDE * r + 16 * tid)), 16);
-		} else {
-#pragma unroll
-			for (int r = 0; r < PF; ++r)
-				v[r] = gload16(a + uintptr_t(STRIDE * r + 16 * tid), lim);
-		}
-	};
-	const uintptr_t abase = reinterpret_cast<uintptr_t>(in) - uintptr_t(mis);
-	u32x4 pf[PF];
-	if (n > 0)
-		load16k(abase, pf);
-
-	ISTAMP_DECL;
-	int32_t E = 0;  // exact chain entry of the current chunk
-	int32_t lead = LEAD_IN0;  // lead-in bytes (from the previous chunk's density)
-	bool bad = false;
-	bool sparse = false;  // declined as literal-heavy (k_decode_sparse takes it)
-	for (int32_t C = 0; C < n && !bad; C += CHUNK) {
-		// stage block-relative [C - mis, C - mis + CHUNK) (16-byte aligned addresses)
-#pragma unroll
-		for (int r = 0; r < PF; ++r)
-			*reinterpret_cast<u32x4*>(&X.buf[STRIDE * r + 16 * tid]) = pf[r];
-		if (tid == 0)
-			*reinterpret_cast<u32x4*>(&X.buf[CHUNK]) = pf[0];
-		__syncthreads();
-		if (C + CHUNK < n)
-			load16k(abase + uintptr_t(C + CHUNK), pf);
-		S.lo = C - mis;
-		S.hi = C - mis + CHUNK;
-		ISTAMP(I_STAGE);
-		ICOUNT(I_CHUNKS, 1);
-
-		const int32_t s = C + SEG * tid;
-		const int32_t seg_end = min(s + SEG, n);
-		// Entry of lane i = max exit of lanes < i (lane 0: the exact entry E).
-		// True exits never decrease along the chunk, so the fixed point is
-		// the true chain, and a run of segments a long sequence jumps over
-		// is crossed in one step instead of one iteration per segment.
-		int32_t ein = (tid == 0) ? E : s;
-		if (tid > 0 && s < n) {
-			// Lead-in: walk from OV bytes before the segment to find a
-			// likelier entry than s itself -- chains from a wrong start merge
-			// with the true one within ~14 sequences, so by s this one mostly
-			// has, and the re-walk rounds below (most of pass 1's time) are
-			// rarely needed.
-			ein = lead_in_walk(S, C, s, lead);
-		}
-		ISTAMP(I_LEAD);
-		uint32_t* ghi = reinterpret_cast<uint32_t*>(tab + (C >> 5) + NSUB * tid) + 1;
-		int32_t epos = INT32_MAX;
-		bool err = false;
-		int32_t nst = 0;
-		int32_t y = (s < n) ? walk_first<NSUB>(S, ein, s, seg_end, n, X.rbm[tid], X.rcnt[tid], ghi, err,
-		                                       epos, nst)
-		                    : ein;
-		ISTAMP(I_WALK0);
-		ICOUNT(I_STEPS, wave_last(wave_incl_scan(nst)));
-		ICOUNT(I_MAXST, wave_last(wave_incl_max(nst)));
-		// this wave's lane-0 entry: the exact one, but for wave 1 its lead-in
-		// guess until wave 0's largest exit is known
-		int32_t e0 = E;
-		if constexpr (W == 2)
-			e0 = __shfl(ein, 0);
-		auto converge = [&]() {
-			for (int it = 0; it < 64; ++it) {
-				int32_t prev = __shfl_up(wave_incl_max(y), 1);
-				if (lane == 0)
-					prev = e0;
-				const bool changed = prev != ein;
-				if (!__any(changed))
-					break;
-				ICOUNT(I_ITERS, 1);
-				nst = 0;
-				if (changed) {
-					ein = prev;
-					if (s < n) {
-						y = walk_segment<NSUB>(S, ein, s, seg_end, n, X.rbm[tid], halves(X.rcnt[tid]), ghi,
-						                       err, epos, y, !err, nst);
-					} else {
-						y = ein;
-						err = false;
-					}
-				}
-				ICOUNT(I_STEPS, wave_last(wave_incl_scan(nst)));
-				ICOUNT(I_MAXST, wave_last(wave_incl_max(nst)));
-			}
-		};
-		converge();
-		if constexpr (W == 2) {
-			const int32_t mx = wave_last(wave_incl_max(y));
-			if (tid == 0)
-				X.xa[0] = mx;
-			__syncthreads();
-			if (w == 1) {
-				const int32_t ea = X.xa[0];
-				if (ea != e0) {  // the guess missed: the lanes it reached walk again
-					e0 = ea;
-					converge();
-				}
-			}
-		}
-		ISTAMP(I_ITER);
-		// converged: every entry is the true chain position, and every
-		// lane's records are those of its last walk: to HBM, coalesced
-		bad = __any(s < n && err);
-		wave_lds_fence();
-		int32_t starts = 0;  // sequence starts in this chunk (sizes the next lead-in)
-#pragma unroll
-		for (int i = 0; i < NSUB; ++i) {
-			// this wave's record q (segment sg, sub-segment sb), the chunk's record r
-			const int32_t q = 64 * i + lane, sg = 64 * w + q / NSUB, sb = q & (NSUB - 1);
-			const int32_t r = W == 2 ? q + 256 * w : q;
-			if (C + SEG * sg < n) {
-				const uint32_t bmv = X.rbm[sg][sb], c16 = halves(X.rcnt[sg])[sb];
-				starts += __popc(bmv);
-				if (c16 != 0xFFFFu)
-					tab[(C >> 5) + r] = uint64_t(bmv) | (uint64_t(c16) << 32);
-				else  // the exact count is in the high word already
-					*reinterpret_cast<uint32_t*>(tab + (C >> 5) + r) = bmv;
-			}
-		}
-		// Sparse chains (over 64 input bytes per sequence: long literal
-		// runs) defeat the speculative walks -- every segment's guess
-		// misses and the entries crawl one lane per iteration -- and are
-		// the one-wave scalar parse's best case: decline the block (large
-		// blocks only: a short one costs a few chunks either way).
-		const bool sparse_test = C == 0 && n >= 4 * CHUNK;
-		int32_t used = 0;  // sub-segments holding a sequence start
-		E = wave_last(wave_incl_max(y));
-		starts = wave_last(wave_incl_scan(starts));
-		if (sparse_test) {
-			if (s < n)
-				for (int k = 0; k < NSUB; ++k)
-					used += X.rbm[tid][k] ? 1 : 0;
-			used = wave_last(wave_incl_scan(used));
-		}
-		if constexpr (W == 2) {  // the chunk's totals over both waves
-			if (lane == 0) {
-				X.xs[0][w][0] = E;
-				X.xs[0][w][1] = starts;
-				X.xs[0][w][2] = bad ? 1 : 0;
-				X.xs[0][w][3] = used;
-			}
-			__syncthreads();  // also: every read of this chunk's staging is done
-			E = max(X.xs[0][0][0], X.xs[0][1][0]);
-			starts = X.xs[0][0][1] + X.xs[0][1][1];
-			bad = (X.xs[0][0][2] | X.xs[0][1][2]) != 0;
-			used = X.xs[0][0][3] + X.xs[0][1][3];
-		}
-		lead = lead_in_bytes(starts);
-		if (sparse_test && !bad && used < CHUNK / SUB / 4)
-			bad = sparse = true;
-		if constexpr (W == 1)
-			__syncthreads();  // the next chunk overwrites the staging buffer
-	}
-	if (E != n)
-		bad = true;
-	if (tid == 0)
-		status[b].code = bad ? (sparse ? DS_SPARSE : DS_RETRY) : DS_OK;
-	ISTAMP_FLUSH();
-}
-
-// Pass 1 alone, 64 * W threads per block.  The product launches W = 1;
-// W = 2 puts k_decode_pp2's pass 1 under the table test.
-template <int W>
-__global__ __launch_bounds__(64 * W) void k_index(const uint8_t* __restrict__ frame, uint64_t frame_len,
-                                                   const lz4ada_block_desc* __restrict__ desc,
-                                                   uint32_t nblocks, uint8_t* __restrict__ tab_all,
-                                                   lz4ada_block_status* __restrict__ status)
-{
-	__shared__ IdxLds<W> X;
-	if (blockIdx.x < nblocks)
-		index_block<W>(X, frame, frame_len, desc, blockIdx.x, tab_all, status);
-}
+#include "lz4ada_idx_input.inc"   // Src, fetch4 / fetch16 / ring16, Seq, parse_*, gload16, gstore_n
+#include "lz4ada_idx_pass1.inc"   // Pass1, IdxLds, walk_segment, walk_first, the lead-in, index_block, k_index
 
 // ------------------------------------------------------------------ pass 2
 
@@ -1113,724 +382,7 @@ __device__ __forceinline__ bool batch_global(const Src& S, g8* ob, uintptr_t oli
 	return true;
 }
 
-// ------------------------------------------------------ LDS output window
-// A batch whose output fits in OW bytes is assembled in an LDS ring that
-// also keeps the 2+ KiB of output before it, then flushed to HBM with
-// aligned 16-byte stores (the partial last 16 bytes go with the next batch).
-constexpr int OW = 4080;        // max batch output assembled in LDS (see glo below)
-constexpr int ORING = 8192;     // LDS output ring (batch + history)
-constexpr int OMASK = ORING - 1;
-constexpr int MAXSEQ = 128;     // sequences per batch (2 rounds: 192 VGPRs; 256 took 254 and spilled)
-constexpr int RMAX = MAXSEQ / 64;  // rounds of 64 sequences per batch
-constexpr int GC = 1;           // 16-byte pieces an HBM-sourced match loads in its own lane (1: fewest registers; the rest are dealt)
-constexpr int FLUSH_ST = (OW + 15) / 16 / 64 + 1;  // store instructions per flush (fixed)
-static_assert(2 * OW + 16 <= ORING, "batch + its HBM threshold must fit the ring");
-// batch cut limits (experiments: a smaller cut with the same ring and HBM threshold)
-#ifndef LZ4ADA_OW_CUT
-#define LZ4ADA_OW_CUT OW
-#endif
-#ifndef LZ4ADA_SEQ_CUT
-#define LZ4ADA_SEQ_CUT MAXSEQ
-#endif
-
-struct alignas(16) DecLds {
-	uint8_t ring[RING + 16];      // staged input: 4 chunks of 2 KiB (+ mirror)
-	uint8_t oring[ORING];         // output window
-	uint16_t cst[MAXSEQ];         // the batch's sequence starts, in order
-	uint8_t own[256];             // piece -> owning lane (dealt HBM pieces)
-	uint64_t rrec[4 * 64];        // pass-1 records of the staged chunks' sub-segments
-	uint64_t ldesc[2 * 64];       // literal runs of both rounds (dealt literal pieces)
-	uint32_t plut[16 * 4];        // v_perm selectors of the period-off patterns (pattern_lut_init)
-	uint8_t junk[16];             // target of the stores a lane does not need (lds_store_bf)
-};
-static_assert(sizeof(DecLds) <= 20480, "8 waves per CU: at most 20 KiB of LDS per wave");
-
-// The output window and per-wave scratch of an LDS layout: DecLds (one
-// wave per block) holds them directly; a k_decode_pp2 wave's view (WP2,
-// below) picks its wave's scratch.
-__device__ __forceinline__ uint8_t* oring_of(DecLds& D) { return D.oring; }
-__device__ __forceinline__ const uint8_t* oring_of(const DecLds& D) { return D.oring; }
-__device__ __forceinline__ uint8_t* own_of(DecLds& D) { return D.own; }
-__device__ __forceinline__ uint64_t* ldesc_of(DecLds& D) { return D.ldesc; }
-// Layouts with junk bytes and the pattern selectors (the one-wave decoder):
-// branch-free exact stores (lds_store_bf) and period patterns by v_perm
-// (pattern_perm); the two-wave layout keeps the branching forms.
-template <class LD>
-struct lds_fast {
-	static constexpr bool value = false;
-};
-template <>
-struct lds_fast<DecLds> {
-	static constexpr bool value = true;
-};
-__device__ __forceinline__ uint8_t* junk_of(DecLds& D) { return D.junk; }
-__device__ __forceinline__ const uint32_t* plut_of(const DecLds& D) { return D.plut; }
-template <class LD>
-__device__ __forceinline__ uint8_t* junk_of(LD&) { return nullptr; }
-template <class LD>
-__device__ __forceinline__ const uint32_t* plut_of(const LD&) { return nullptr; }
-// the window's size - 1 (a power of two) for a layout: ORING unless the
-// layout says otherwise (the pipelined pair's 16 KiB window)
-template <class LD>
-constexpr uint32_t omask_v = OMASK;
-template <class LD>
-__device__ __forceinline__ constexpr uint32_t omask_of(const LD&) { return omask_v<LD>; }
-
-// Exact store of n (0..16) bytes of v at p, without branches: each of the
-// five stores (16, 8, 4, 2, 1 bytes) goes to its place or, when n does not
-// take it, to the 16 junk bytes, so every lane runs the same five ds_write
-// instructions (lds_store_n's four divergent branches cost a wave whose
-// lanes disagree on n all of them, with their exec-mask bookkeeping).
-__device__ __forceinline__ void lds_store_bf(uint8_t* p, uint8_t* junk, u32x4 v, uint32_t n)
-{
-	const uint64_t lo = uint64_t(v.x) | (uint64_t(v.y) << 32);
-	const uint64_t hi = uint64_t(v.z) | (uint64_t(v.w) << 32);
-	__builtin_memcpy(n >= 16u ? p : junk, &v, 16);
-	__builtin_memcpy((n & 8u) ? p : junk, &lo, 8);
-	const uint64_t r8 = (n & 8u) ? hi : lo;
-	uint8_t* const p4 = p + (n & 8u);
-	const uint32_t w4 = uint32_t(r8);
-	__builtin_memcpy((n & 4u) ? p4 : junk, &w4, 4);
-	const uint32_t r4 = (n & 4u) ? uint32_t(r8 >> 32) : w4;
-	uint8_t* const p2 = p4 + (n & 4u);
-	const uint16_t w2 = uint16_t(r4);
-	__builtin_memcpy((n & 2u) ? p2 : junk, &w2, 2);
-	*((n & 1u) ? p2 + (n & 2u) : junk) = uint8_t((n & 2u) ? (r4 >> 16) : r4);
-}
-
-// Exact-length store of n bytes (fast layouts: 0..16; else 1..16) at
-// output position x into the ring.
-template <class LD>
-__device__ __forceinline__ void ostore(LD& L, int32_t x, u32x4 v, int32_t n)
-{
-	const uint32_t a = uint32_t(x) & omask_of(L);
-	if constexpr (lds_fast<LD>::value) {
-		// a store wrapping the ring's end (one piece every 8 KiB of output)
-		// takes the byte loop below, the wave's other lanes with it
-		if (__builtin_expect(!__any(a + uint32_t(n) > omask_of(L) + 1), 1)) {
-			lds_store_bf(&oring_of(L)[a], junk_of(L), v, uint32_t(n));
-			return;
-		}
-	}
-	if (a + uint32_t(n) <= omask_of(L) + 1) {
-		// one ds_write_b128 even when misaligned: 256 cycles against 1579
-		// for four ds_write_b32 (each misaligned one is split too) and 384
-		// for 16 ds_write_b8 (tools/lds_bench.hip, dependent chain)
-		lds_store_n(&oring_of(L)[a], v, n);
-		return;
-	}
-	const uint64_t lo = uint64_t(v.x) | (uint64_t(v.y) << 32);
-	const uint64_t hi = uint64_t(v.z) | (uint64_t(v.w) << 32);
-#pragma clang loop vectorize(disable) unroll(disable)
-	for (int32_t i = 0; i < n; ++i) {
-		const uint64_t w = i < 8 ? lo : hi;
-		oring_of(L)[(a + uint32_t(i)) & omask_of(L)] = uint8_t(w >> (8 * (i & 7)));
-	}
-}
-
-// Whole-piece store: v's 16 bytes at output position x where has, else
-// nothing.  The fast layouts issue one ds_write_b128, to the piece's place
-// or to the junk bytes -- none of lds_store_bf's select network, no second
-// to fifth store; a piece wrapping the ring's end sends the wave through
-// ostore, as there.  For a dealt piece that is not its run's last: such a
-// piece lies wholly inside its own run.
-template <class LD>
-__device__ __forceinline__ void ostore16(LD& L, int32_t x, u32x4 v, bool has)
-{
-	if constexpr (lds_fast<LD>::value) {
-		const uint32_t a = uint32_t(x) & omask_of(L);
-		if (__builtin_expect(!__any(has && a + 16u > omask_of(L) + 1), 1)) {
-			__builtin_memcpy(has ? &oring_of(L)[a] : junk_of(L), &v, 16);
-			return;
-		}
-		ostore(L, x, v, has ? 16 : 0);
-	} else {
-		if (has)
-			ostore(L, x, v, 16);
-	}
-}
-
-template <class LD>
-__device__ __forceinline__ u32x4 oload16(const LD& L, int32_t x)
-{
-	return ring16(oring_of(L), uint32_t(x) & omask_of(L), omask_of(L));
-}
-
-// Store steps and phases of period-off patterns without integer division:
-// bits 5(o-1).. = o * (16 / o), bits 40 + 2(o-1).. = 8 mod o, for o = 1..8.
-constexpr uint64_t pattern_lut()
-{
-	uint64_t v = 0;
-	for (int o = 1; o <= 8; ++o)
-		v |= (uint64_t(o * (16 / o)) << (5 * (o - 1))) | (uint64_t(8 % o) << (40 + 2 * (o - 1)));
-	return v;
-}
-constexpr uint64_t PAT_LUT = pattern_lut();
-
-// 16 bytes of the period-off (1..15) sequence whose first off bytes are
-// s0|s1's, and the largest multiple of off <= 16: storing it every stp
-// bytes keeps the phase.
-__device__ __forceinline__ void make_pattern16(uint64_t s0, uint64_t s1, int32_t off, u32x4& pv,
-                                               int32_t& stp)
-{
-	uint64_t x, hi;
-	if (off <= 8) {
-		x = off == 8 ? s0 : (s0 & ((uint64_t(1) << (8 * off)) - 1));
-		// doubling x |= x << 8w for w = off, 2 off, 4 off while w < 8, with
-		// selects instead of a lane-divergent loop
-#pragma unroll
-		for (int i = 0; i < 3; ++i) {
-			const int32_t w = off << i;
-			x |= w < 8 ? x << (8 * w) : 0;
-		}
-		const uint32_t sh = uint32_t(off - 1);
-		stp = int32_t((PAT_LUT >> (5 * sh)) & 31u);
-		const int32_t r = int32_t((PAT_LUT >> (40 + 2 * sh)) & 3u);
-		// bytes 8..15: x[r..7], then x from 8 - off on (x is off-periodic)
-		hi = r == 0 ? x : (x >> (8 * r)) | ((x >> (8 * (8 - off))) << (8 * (8 - r)));
-	} else {
-		const int32_t r = off - 8;
-		x = s0;
-		hi = (s1 & ((uint64_t(1) << (8 * r)) - 1)) | (s0 << (8 * r));
-		stp = off;
-	}
-	pv.x = uint32_t(x);
-	pv.y = uint32_t(x >> 32);
-	pv.z = uint32_t(hi);
-	pv.w = uint32_t(hi >> 32);
-}
-
-// a's bytes j < c, b's from c on (c = 1..15)
-__device__ __forceinline__ u32x4 merge_at(u32x4 a, u32x4 b, int32_t c)
-{
-	auto m = [c](int32_t d) -> uint32_t {
-		const int32_t t = c - 4 * d;
-		return t >= 4 ? ~0u : (t <= 0 ? 0u : (1u << (8 * t)) - 1u);
-	};
-	u32x4 v;
-	v.x = (a.x & m(0)) | (b.x & ~m(0));
-	v.y = (a.y & m(1)) | (b.y & ~m(1));
-	v.z = (a.z & m(2)) | (b.z & ~m(2));
-	v.w = (a.w & m(3)) | (b.w & ~m(3));
-	return v;
-}
-
-// Store step of a period-off pattern match (make_pattern16's stp).
-__device__ __forceinline__ int32_t pattern_step(int32_t off)
-{
-	return off <= 8 ? int32_t((PAT_LUT >> (5 * (off - 1))) & 31u) : off;
-}
-
-// v_perm_b32 selectors of the period-off patterns, off = 1..15 (entry off,
-// dword d; entry 0 unused): byte t of output dword d is source byte
-// (4d + t) mod off, taken from v.y:v.x (off <= 8, and dwords 0-1 -- v.x and
-// v.y themselves -- of every off), v.z:v.x (dword 2, off >= 9) or
-// v.w:v.x / v.y:v.x (dword 3, off >= 12 / 9..11): pattern_perm.  Written
-// once per block by its wave (lane l: entry l / 4, dword l % 4).
-__device__ __forceinline__ void pattern_lut_init(uint32_t* plut)
-{
-	const uint32_t l = lane_id(), off = l >> 2, d = l & 3u;
-	uint32_t sel = 0;
-	if (off > 0)
-		for (uint32_t t = 0; t < 4; ++t) {
-			const uint32_t idx = (4 * d + t) % off;
-			uint32_t x = idx;
-			if (off > 8 && d == 2 && idx >= 8)
-				x = idx - 4;  // v.z byte idx - 8 (v_perm's src0 bytes are 4..7)
-			if (off >= 12 && d == 3 && idx >= 12)
-				x = idx - 8;  // v.w byte idx - 12
-			sel |= x << (8 * t);
-		}
-	plut[l] = sel;
-}
-
-// The phase-0 period-off (1..15) pattern of the 16 source bytes v (the
-// first off of them valid): make_pattern16's value in one LDS read, two
-// selects and four v_perm_b32 instead of its 64-bit shift network.
-// (pattern_sel is the LDS read: it needs off alone, so a caller issues it
-// beside the source read and applies it once both have arrived)
-__device__ __forceinline__ u32x4 pattern_sel(int32_t off, const uint32_t* plut)
-{
-	return *reinterpret_cast<const u32x4*>(plut + 4 * off);
-}
-
-__device__ __forceinline__ u32x4 pattern_perm(u32x4 v, int32_t off, u32x4 sel)
-{
-	const uint32_t h2 = off <= 8 ? v.y : v.z, h3 = off <= 11 ? v.y : v.w;
-	u32x4 o;
-	o.x = __builtin_amdgcn_perm(v.y, v.x, sel.x);
-	o.y = __builtin_amdgcn_perm(v.y, v.x, sel.y);
-	o.z = __builtin_amdgcn_perm(h2, v.x, sel.z);
-	o.w = __builtin_amdgcn_perm(h3, v.x, sel.w);
-	return o;
-}
-
-// Match with a final source entirely inside the ring (Output_With_History,
-// lz4ada.adb:845-904).  Match byte i is source byte i mod off (the overlap
-// rule), so no unit reads this match's own output: an off < 16 overlap
-// stores a 16-byte period pattern every stp bytes, any other match 16
-// source bytes per unit (a unit that wraps the period merges two reads).
-// One loop for both forms: a wave runs max(units) over its lanes, not the
-// two loops one after the other.
-template <class LD>
-__device__ __forceinline__ void ring_match(LD& L, int32_t dst, int32_t off, int32_t len)
-{
-	const int32_t src = dst - off;
-	u32x4 pv = oload16(L, src);
-	int32_t stp = 16;
-	const bool pat = off < 16 && off < len;
-	if (pat) {
-		if constexpr (lds_fast<LD>::value) {
-			pv = pattern_perm(pv, off, pattern_sel(off, plut_of(L)));
-			stp = pattern_step(off);
-		} else {
-			make_pattern16(uint64_t(pv.x) | (uint64_t(pv.y) << 32), uint64_t(pv.z) | (uint64_t(pv.w) << 32),
-			               off, pv, stp);
-		}
-	}
-	ostore(L, dst, pv, min(16, len));
-	int32_t start = 0;  // unit x of the wide form begins at source byte x mod off
-	for (int32_t x = stp; x < len; x += stp) {
-		u32x4 v = pv;
-		if (!pat) {
-			start += 16;
-			if (start >= off)
-				start -= off;
-			v = oload16(L, src + start);
-			if (off - start < 16)
-				v = merge_at(v, oload16(L, src + start - off), off - start);
-		}
-		ostore(L, dst + x, v, min(16, len - x));
-	}
-}
-
-// q = t / d and r = t mod d for 0 <= t < 2^22, 1 <= d < 2^16: float
-// reciprocal (error < 1 in q) and one correction step.
-__device__ __forceinline__ int32_t div_small(int32_t t, int32_t d, int32_t& r)
-{
-	int32_t q = int32_t(float(t) * __builtin_amdgcn_rcpf(float(d)));
-	r = t - q * d;
-	if (r < 0) {
-		--q;
-		r += d;
-	}
-	if (r >= d) {
-		++q;
-		r -= d;
-	}
-	return q;
-}
-
-
-__device__ __forceinline__ int32_t piece_owner(int32_t inc, int32_t t);
-
-// Owner lane of piece t0 + lane, lane i holding pieces [inc_i - np_i,
-// inc_i) (inc: inclusive prefix sum, monotone): each lane marks its first
-// piece's slot of the 64-piece chunk in LDS, a prefix maximum fills the
-// slots in between, and the chunk's first slot is seeded with the owner of
-// piece t0 (the lanes with inc <= t0, counted from a ballot).  Two LDS
-// round trips instead of six dependent shuffles of a binary search.
-template <class LD>
-__device__ __forceinline__ int32_t chunk_owner(LD& D, int32_t inc, int32_t np, int32_t t0)
-{
-	const int32_t lane = int32_t(lane_id());
-	const int32_t seed = __popcll(__ballot(inc <= t0));
-	uint8_t* own = own_of(D);
-	own[lane] = uint8_t(lane == 0 ? seed : 0);
-	const int32_t excl = inc - np;
-	if (np > 0 && excl >= t0 && excl < t0 + 64)
-		own[excl - t0] = uint8_t(lane);
-	wave_lds_fence();
-	const int32_t v = own[lane];
-	wave_lds_fence();  // own[] is marked again for the next chunk
-	return wave_incl_max(v);
-}
-
-// chunk_owner over two rounds' entries (round 0's lanes, then round 1's),
-// from each entry's first piece e and whether it has any (nz): entry
-// 64 r + lane holds pieces [e_r, e_r + its count), owner 0..127; seed is the
-// owner of piece t0.
-template <class LD>
-__device__ __forceinline__ int32_t chunk_owner_marks(LD& D, int32_t seed, int32_t e0, bool nz0, int32_t e1,
-                                                     bool nz1, int32_t t0)
-{
-	const int32_t lane = int32_t(lane_id());
-	uint8_t* own = own_of(D);
-	own[lane] = uint8_t(lane == 0 ? seed : 0);
-	if (nz0 && e0 >= t0 && e0 < t0 + 64)
-		own[e0 - t0] = uint8_t(lane);
-	if (nz1 && e1 >= t0 && e1 < t0 + 64)
-		own[e1 - t0] = uint8_t(64 + lane);
-	wave_lds_fence();
-	const int32_t v = own[lane];
-	wave_lds_fence();  // own[] is marked again for the next chunk
-	return wave_incl_max(v);
-}
-
-// ... from the inclusive prefix sums and the counts (entry 64 r + lane holds
-// pieces [inc_r - np_r, inc_r))
-template <class LD>
-__device__ __forceinline__ int32_t chunk_owner2(LD& D, int32_t inc0, int32_t np0, int32_t inc1,
-                                                int32_t np1, int32_t t0)
-{
-	const int32_t seed = __popcll(__ballot(inc0 <= t0)) + __popcll(__ballot(inc1 <= t0));
-	return chunk_owner_marks(D, seed, inc0 - np0, np0 > 0, inc1 - np1, np1 > 0, t0);
-}
-
-// Every lane's match (dst, off, ml; ml = 0: none) with a source in the LDS
-// ring, cut into units of which ring_pieces deals two per piece over the
-// wave: 16 output bytes each, or stp bytes of a period-off pattern (off <
-// 16 < ml would overlap: match byte i is source byte i mod off, so a unit
-// never reads its own match's output).  Pieces are in output order; one
-// reading output of a lower lane of its chunk waits until that lane has
-// stored (ballot per step).
-// Units of one match: 16 bytes each, or stp-byte steps of a period-off
-// pattern (off < 16 < ml overlaps).
-__device__ __forceinline__ int32_t match_pieces(int32_t off, int32_t ml)
-{
-	if (ml <= 0)
-		return 0;
-	if (!(off < 16 && off < ml))
-		return (ml + 15) >> 4;
-	const int32_t stp = pattern_step(off);
-	int32_t rr;
-	return stp == 16 ? (ml + 15) >> 4 : div_small(ml + stp - 1, stp, rr);
-}
-
-// Rounds whose idle own-piece slots take dealt HBM pieces beyond the 64th
-// (decode_block's P; 0: none, every such piece loads in M)
-#ifndef LZ4ADA_BORROW_SLOTS
-#define LZ4ADA_BORROW_SLOTS 2
-#endif
-constexpr int BORROW_SLOTS = LZ4ADA_BORROW_SLOTS;
-static_assert(BORROW_SLOTS >= 0 && BORROW_SLOTS <= 2, "round 0's slots, or both rounds'");
-
-#ifndef LZ4ADA_FWD_ROUNDS
-#define LZ4ADA_FWD_ROUNDS 5
-#endif
-constexpr int FWD_ROUNDS = LZ4ADA_FWD_ROUNDS;  // forwarding rounds of ring_lanes (0: none)
-// (forwarding over ring_pieces' dealt pieces was measured and is gone: mixed
-// 13.17 -> 13.41 ms with it, dense 37.07 -> 37.38; profiles/r06i_ab.txt)
-
-// Dealt pieces of a ring-sourced match: two of match_pieces' units each
-// (32 output bytes, or two steps of a period-off pattern), so a batch of
-// mixed data deals ~48 pieces instead of ~71 and nearly always fits one
-// 64-piece chunk (ring_pieces' set-up runs once per chunk).
-__device__ __forceinline__ int32_t ring_piece_count(int32_t off, int32_t ml)
-{
-	return (match_pieces(off, ml) + 1) >> 1;
-}
-
-// chunk_owner2 from the entries' first pieces alone (e: exclusive prefix sum
-// of the piece counts, 16 bits per round in ee; nz: the entry has pieces):
-// the entries with inc <= t0 are those after the first with e <= t0 (entry
-// 0's e is 0, and piece t0 exists).
-template <class LD>
-__device__ __forceinline__ int32_t chunk_owner_e(LD& D, uint32_t ee, bool nz0, bool nz1, int32_t t0)
-{
-	const int32_t e0 = int32_t(ee & 0xffffu), e1 = int32_t(ee >> 16);
-	const int32_t seed = __popcll(__ballot(e0 <= t0)) + __popcll(__ballot(e1 <= t0)) - 1;
-	return chunk_owner_marks(D, seed, e0, nz0, e1, nz1, t0);
-}
-
-// Marks two registers as changed (no instruction): what is computed from
-// them after this point stays after it, instead of being hoisted out of the
-// loop around it and held in registers across it.
-__device__ __forceinline__ void step_state(uint32_t& a, uint32_t& b) { asm volatile("" : "+v"(a), "+v"(b)); }
-
-// Both rounds' ring-sourced matches (round r: mdst[r], off[r], ml[r]; ml 0:
-// none), dealt together in output order; a piece finds its match in an LDS
-// descriptor (D.ldesc, free after the literals) instead of by shuffles.
-// Piece k of a match is its units 2k and 2k + 1 (match_pieces' units: 16
-// output bytes, or stp bytes' step of a period-off pattern).  With more
-// than 16 bytes left at its start it stores 16 whole bytes there and an
-// exact-length second unit ostp further on; else one exact-length unit.
-// Neither unit reads its own match's output (ring_match's rule), so a
-// piece waits only for the lower pieces of its chunk that write into the
-// source of either unit.
-template <class LD>
-__device__ __forceinline__ int32_t ring_pieces(LD& D, const int32_t (&mdst)[RMAX],
-                                               const int32_t (&off)[RMAX], const int32_t (&ml)[RMAX],
-                                               int32_t o_batch)
-{
-	int32_t steps = 0;  // store steps (diagnostic count)
-	const int32_t lane = int32_t(lane_id());
-	const bool nz0 = ml[0] > 0, nz1 = ml[1] > 0;
-	int32_t tot;
-	uint32_t ee;  // the entries' first pieces, both rounds (inc* / np* end here)
-	{
-		const int32_t np0 = ring_piece_count(off[0], ml[0]), np1 = ring_piece_count(off[1], ml[1]);
-		const int32_t inc0 = wave_incl_scan(np0);
-		const int32_t tot0 = wave_last(inc0);
-		const int32_t inc1 = tot0 + wave_incl_scan(np1);
-		tot = wave_last(inc1);
-		auto pack = [&](int32_t md, int32_t of, int32_t m, int32_t excl) -> uint64_t {
-			return uint64_t(uint16_t(md - o_batch)) | (uint64_t(uint16_t(of)) << 16) |
-			       (uint64_t(uint16_t(m)) << 32) | (uint64_t(uint16_t(excl)) << 48);
-		};
-		uint64_t* ldesc = ldesc_of(D);
-		ldesc[lane] = pack(mdst[0], off[0], ml[0], inc0 - np0);
-		ldesc[64 + lane] = pack(mdst[1], off[1], ml[1], inc1 - np1);
-		ee = uint32_t(inc0 - np0) | (uint32_t(inc1 - np1) << 16);
-	}
-	for (int32_t t0 = 0; t0 < tot; t0 += 64) {
-		const int32_t t = t0 + lane;
-		const bool act = t < tot;
-		const int32_t lo = min(chunk_owner_e(D, ee, nz0, nz1, t0), 127);
-		const uint64_t dd = ldesc_of(D)[lo];
-		const int32_t od = o_batch + int32_t(dd & 0xffffu);
-		const int32_t ooff = int32_t((dd >> 16) & 0xffffu), oml = int32_t((dd >> 32) & 0xffffu);
-		const int32_t k = t - int32_t(dd >> 48);
-		const bool opat = ooff < 16 && ooff < oml;
-		const int32_t ostp = opat ? pattern_step(ooff) : 16;
-		const bool wide = !opat && oml > ooff;  // overlap with off >= 16
-		const int32_t base = 2 * k * ostp;       // the piece's first output byte in its match
-		const int32_t pd = od + base;
-		const int32_t left = oml - base;
-		const bool two = left > 16;
-		// the exact-length store: the second unit's bytes, or the whole piece
-		const int32_t pd2 = two ? pd + ostp : pd;
-		const int32_t n2 = two ? min(16, left - ostp) : left;
-		const int32_t pe_ = pd2 + n2;  // the piece writes [pd, pe_)
-		// source bytes read: the whole period for patterns and overlaps
-		const int32_t s_lo = (opat || wide) ? od - ooff : od - ooff + base;
-		const int32_t s_hi = (opat || wide) ? od : s_lo + (pe_ - pd);
-		// lanes of this chunk whose piece [pd, pe_) meets [s_lo, s_hi):
-		// pd is monotone over the lanes, so two binary searches -- skipped
-		// when every source ends before the chunk's first piece
-		// (a piece's real end, not pd + 32: a short last piece must not hold
-		// back a source that only starts after it)
-		const int32_t pe = act ? pe_ : INT32_MAX, ps = act ? pd : INT32_MAX;
-		int32_t fj1 = 64, fj2 = -1;  // the chunk's pieces that write this one's source (none)
-		if (!__all(!act || s_hi <= wave_get(ps, 0))) {
-			// the first probe's source is lane 31 in every lane: a readlane, not
-			// an LDS shuffle.  wave_get's conditions hold: 31 is a constant, and
-			// every lane computed pe and ps above (the chunk loop and this
-			// branch are wave-uniform)
-			int32_t j1 = wave_get(pe, 31) <= s_lo ? 32 : 0, c2 = wave_get(ps, 31) < s_hi ? 32 : 0;
-#pragma unroll
-			for (int st = 16; st >= 1; st >>= 1) {
-				if (__shfl(pe, j1 + st - 1) <= s_lo)
-					j1 += st;
-				if (__shfl(ps, c2 + st - 1) < s_hi)
-					c2 += st;
-			}
-			fj1 = j1;
-			fj2 = min(c2 - 1, lane - 1);
-		}
-		uint64_t dep = 0;
-		if (act && fj1 <= fj2)
-			dep = (fj2 == 63 ? ~uint64_t(0) : ((uint64_t(2) << fj2) - 1)) & ~((uint64_t(1) << fj1) - 1);
-		// the piece's reads, fixed before the steps: per unit 16 bytes at a
-		// and, for an overlap with off >= 16 whose unit wraps the period, the
-		// bytes from cut on at a - off.  The second unit begins 16 bytes on
-		// in the period: at a1 + 16, or off before that once past its end.
-		// The step loop is the kernel's register peak, and every address,
-		// select and mask the loads and stores derive from these values
-		// would be hoisted out of it, so they cross it packed in two
-		// registers the compiler must take as changing (step_state): a step
-		// unpacks what it needs.
-		//   sa: a1 (ring address, 14 bits) | pd (ring address) << 14 | (ostp - 1) << 28
-		//   sb: off | cut1 << 16 | cut2 << 21 | n2 << 26 | (the second unit wraps) << 31
-		static_assert(omask_v<LD> < (1u << 14), "ring addresses pack into 14 bits");
-		uint32_t sa, sb;
-		{
-			int32_t rem = 0;
-			if (wide)
-				div_small(base, ooff, rem);
-			const int32_t a1 = opat ? od - ooff : (wide ? od - ooff + rem : s_lo);
-			const int32_t cut1 = (wide && ooff - rem < 16) ? ooff - rem : 16;
-			const bool wrap2 = wide && rem + 16 >= ooff;
-			const int32_t rem2 = rem + 16 - (wrap2 ? ooff : 0);
-			const int32_t cut2 = (wide && ooff - rem2 < 16) ? ooff - rem2 : 16;
-			sa = (uint32_t(a1) & omask_of(D)) | ((uint32_t(pd) & omask_of(D)) << 14) | (uint32_t(ostp - 1) << 28);
-			sb = uint32_t(ooff) | (uint32_t(cut1) << 16) | (uint32_t(cut2) << 21) | (uint32_t(max(n2, 0)) << 26) |
-			     (uint32_t(wrap2) << 31);
-		}
-		const bool ld2 = two && !opat;  // a pattern's second unit is its first
-		bool pend = act;
-		for (;;) {
-			const uint64_t pm = __ballot(pend);
-			if (pm == 0)
-				break;
-			const bool ready = pend && (dep & pm) == 0;
-			step_state(sa, sb);
-			const int32_t xa1 = int32_t(sa & 0x3fffu), xpd = int32_t((sa >> 14) & 0x3fffu);
-			const int32_t xoff = int32_t(sb & 0xffffu), xcut1 = int32_t((sb >> 16) & 31u);
-			const int32_t xcut2 = int32_t((sb >> 21) & 31u), xn2 = int32_t((sb >> 26) & 31u);
-			const int32_t xa2 = xa1 + 16 - (int32_t(sb) < 0 ? xoff : 0);
-			const int32_t xpd2 = two ? xpd + int32_t(sa >> 28) + 1 : xpd;
-			// Reads first.  Unit 1's read, unit 2's and the pattern selectors'
-			// (their address needs only xoff) are issued here, before the
-			// step's first store, and consumed below, so they are in flight
-			// together and each use waits for its own (a counted lgkmcnt)
-			// instead of paying a round trip of its own behind the store
-			// before it.  The rule that makes it valid: no read of a ready
-			// lane meets a store of this step.  Not its own piece's --
-			// neither unit reads its own match's output (ring_match's rule)
-			// -- and not another ready lane's: dep covers the sources of both
-			// units, so two lanes ready in one step never read each other's
-			// stores of that step.  The compiler cannot prove that two oring
-			// addresses differ and would keep unit 2's read behind unit 1's
-			// store; hence the order here.  (The wrap-merge reads of an
-			// overlap stay where they are used: issued up here under their
-			// predicates they measured slower, and so did unit 2's early
-			// read in the branching form below, which keeps the plain
-			// order)
-			if constexpr (lds_fast<LD>::value) {
-				// every lane loads and stores (a lane not ready stores
-				// nothing: its stores go to the junk bytes)
-				u32x4 v = oload16(D, xa1);
-				u32x4 w = oload16(D, xa2);
-				const u32x4 sel = pattern_sel(opat ? xoff : 0, plut_of(D));
-				if (ready && xcut1 < 16)
-					v = merge_at(v, oload16(D, xa1 - xoff), xcut1);
-				if (ready && opat)
-					v = pattern_perm(v, xoff, sel);
-				// unit 2's bytes are assembled before unit 1's store is issued:
-				// placed after it, their wait would count the store as well
-				asm volatile("" : "+v"(w.x), "+v"(w.y), "+v"(w.z), "+v"(w.w)::"memory");
-				// the first unit of two: 16 whole bytes in one store (one wrapping
-				// the ring's end takes ostore's byte loop)
-				if (__builtin_expect(!__any(ready && two && uint32_t(xpd) + 16u > omask_of(D) + 1), 1))
-					__builtin_memcpy((ready && two) ? &oring_of(D)[xpd] : junk_of(D), &v, 16);
-				else
-					ostore(D, xpd, v, (ready && two) ? 16 : 0);
-				if (ready && ld2 && xcut2 < 16)
-					w = merge_at(w, oload16(D, xa2 - xoff), xcut2);
-				if (ld2)
-					v = w;
-				ostore(D, xpd2, v, ready ? xn2 : 0);
-			} else if (ready) {
-				u32x4 v = oload16(D, xa1);
-				if (xcut1 < 16)
-					v = merge_at(v, oload16(D, xa1 - xoff), xcut1);
-				if (opat) {
-					int32_t sstp;
-					make_pattern16(uint64_t(v.x) | (uint64_t(v.y) << 32),
-					               uint64_t(v.z) | (uint64_t(v.w) << 32), xoff, v, sstp);
-				}
-				if (two)
-					ostore(D, xpd, v, 16);
-				if (ld2) {
-					v = oload16(D, xa2);
-					if (xcut2 < 16)
-						v = merge_at(v, oload16(D, xa2 - xoff), xcut2);
-				}
-				ostore(D, xpd2, v, xn2);
-			}
-			pend = pend && !ready;
-			wave_lds_fence();
-			++steps;
-		}
-	}
-	return steps;
-}
-
-// Ring-sourced matches of a round of short matches, one lane each: those
-// whose source is final before the round (or lies in their own literals)
-// at once, a near match -- reading this round's match output -- once every
-// lane whose output it reads is done (a 64-bit mask from two binary
-// searches over the round's monotone match positions, one AND against a
-// ballot per step).  rbeg: the round's first output position; L: this
-// lane's literal length.
-#ifndef LZ4ADA_RING_LANE_MAX
-#define LZ4ADA_RING_LANE_MAX 32
-#endif
-constexpr int RING_LANE_MAX = LZ4ADA_RING_LANE_MAX;
-template <class LD>
-__device__ __forceinline__ int32_t ring_lanes(LD& D, int32_t mdst, int32_t off, int32_t ml,
-                                           int32_t rbeg, int32_t L, int32_t glo = INT32_MIN)
-{
-	const int32_t lane = int32_t(lane_id());
-	const int32_t src = mdst - off;
-	const int32_t dep_end = src + min(off, ml);
-	const bool far = ml > 0 && (dep_end <= rbeg || off <= L);
-	int32_t steps = 0;  // store steps (diagnostic count)
-	if (!__any(ml > 0 && !far)) {
-		if (far)
-			ring_match(D, mdst, off, ml);
-		wave_lds_fence();
-		return 0;
-	}
-	// with near matches, the far ones run in the first step with the near
-	// ones that are ready (their sources are final: no producers), not in
-	// a step of their own
-	bool near = ml > 0;
-	const int32_t mend = mdst + ml;
-	// the first probe by readlane (lane 31 in every lane).  wave_get's
-	// conditions hold: every lane holds its mdst and mend -- the caller
-	// computes them for all 64 lanes, in wave-uniform control flow
-	int32_t j1 = wave_get(mend, 31) <= src ? 32 : 0, c2 = wave_get(mdst, 31) < dep_end ? 32 : 0;
-#pragma unroll
-	for (int st = 16; st >= 1; st >>= 1) {
-		if (__shfl(mend, j1 + st - 1) <= src)
-			j1 += st;
-		if (__shfl(mdst, c2 + st - 1) < dep_end)
-			c2 += st;
-	}
-	int32_t fj1 = far ? 64 : j1, fj2 = far ? -1 : min(c2 - 1, lane - 1);
-	// Forwarding (pointer jumping over the round's near matches): a plain
-	// match (off >= ml) whose source lies inside ONE earlier near match P of
-	// the round, P itself a plain copy, reads P's source instead -- byte x of
-	// it is byte x - off - off_P -- and waits for P's producers instead of
-	// for P.  Each round composes every lane's forwarding with its producer's
-	// current one, so a chain of k dependent matches (text: matches copying
-	// recent matches, ~17 in a row) takes ~log2 k rounds instead of k store
-	// steps.  A source forwarded past glo (below the window's kept bytes)
-	// stops there.
-	int32_t fo = off;
-	{
-		const int32_t pm = __shfl(mdst, fj1), pe = __shfl(mend, fj1), po = __shfl(off, fj1);
-		const bool pn = __shfl(int32_t(near), fj1) != 0;
-		bool fw = FWD_ROUNDS > 0 && glo != INT32_MIN && near && off >= ml && fj1 == fj2 && pm <= src &&
-		          dep_end <= pe && pn && po >= pe - pm;
-		// (the producer's state is read before any lane updates its own:
-		// synchronous rounds; P's identity out[y] = out[y - fo_P] holds for
-		// whatever forwarding P has reached)
-		for (int r = 0; r < FWD_ROUNDS && __any(fw); ++r) {
-			const int32_t p = fj1;
-			const int32_t qo = __shfl(fo, p), q1 = __shfl(fj1, p), q2 = __shfl(fj2, p);
-			const bool qf = __shfl(int32_t(fw), p) != 0;
-			if (fw && mdst - fo - qo >= glo) {
-				fo += qo;
-				fj1 = q1;  // P's producers (none: q1 > q2, the source is final)
-				fj2 = q2;
-				fw = qf;
-			} else {
-				fw = false;
-			}
-		}
-	}
-	uint64_t dep = 0;
-	if (near && fj1 <= fj2)
-		dep = (fj2 == 63 ? ~uint64_t(0) : ((uint64_t(2) << fj2) - 1)) & ~((uint64_t(1) << fj1) - 1);
-	for (;;) {
-		const uint64_t pending = __ballot(near);
-		if (pending == 0)
-			break;
-		const bool ready = near && (dep & pending) == 0;
-		if (ready) {
-			ring_match(D, mdst, fo, ml);
-			near = false;
-		}
-		wave_lds_fence();
-		++steps;
-	}
-	return steps;
-}
-
-// Owner of piece t when lane i holds pieces [inc_i - cnt_i, inc_i) (inc: the
-// wave's inclusive prefix sum of piece counts): the first lane with inc > t.
-__device__ __forceinline__ int32_t piece_owner(int32_t inc, int32_t t)
-{
-	int32_t lo = 0;
-#pragma unroll
-	for (int st = 32; st >= 1; st >>= 1)
-		if (__shfl(inc, lo + st - 1) <= t)
-			lo += st;
-	return lo;
-}
+#include "lz4ada_idx_window.inc"  // DecLds and its accessors, ostore*, oload16, patterns, owner searches, ring_*
 
 // 2 KiB input chunk c (aligned address abase + c*BATCH), 32 bytes per lane
 __device__ __forceinline__ void load_chunk2(uintptr_t abase, int32_t c, uintptr_t lim, u32x4& v0,
@@ -1918,6 +470,129 @@ __device__ __forceinline__ lz4ada_block_desc wave_desc(const lz4ada_block_desc* 
 	return d;
 }
 
+// ------------------------------------------------ pass 2's shared stages
+// The steps of a batch that decode_block (one wave per block) and
+// decode_block_pp2 (the pipelined pair) both take, each stated once over
+// the LDS layout: DecLds, or a pair wave's view WP2.  What the decoders do
+// differently stays in them: the pair's token and done[] hand-offs, its
+// split of a match at the HBM threshold (hml) and its glo from the other
+// wave's flush; quirk D1, the zero plane and the borrowed slots in
+// decode_block.
+//
+// Left in both decoders, because as a function the same text compiled to
+// other machine code for the k_decode_idx family or for k_decode_pp2 in
+// every form tried (bench.kernel_code_hash): the
+// two-round parse, the fill of the sequence starts into cst, the chunk
+// loads ahead of staging (decode_block's own, beside stage_chunk, where
+// the pair has pp_load_chunk), and the [&] lambdas through which
+// decode_block reaches deal_pack.  The window reload after an oversized
+// batch is two statements on purpose: decode_block's reaches back into the
+// history in front of the block (hb) with cached loads, the pair's has no
+// history, reads past the L1 (nontemporal) and checks each piece against
+// cap -- one function would take a flag that says which decoder calls.
+
+// Staging: input chunk c (2 KiB, 32 bytes per lane: v0, v1) into the input
+// ring (four chunks; the ring's first 16 bytes mirrored past its end) and
+// the pass-1 records of its 64 sub-segments into rrec.
+template <class LD>
+__device__ __forceinline__ void stage_chunk(LD& L, int32_t c, const u32x4& v0, const u32x4& v1, uint64_t r)
+{
+	const uint32_t lane = lane_id();
+	const uint32_t a = uint32_t(c * BATCH) & (RING - 1);
+	*reinterpret_cast<u32x4*>(&ring_of(L)[a + 16 * lane]) = v0;
+	*reinterpret_cast<u32x4*>(&ring_of(L)[a + 1024 + 16 * lane]) = v1;
+	if (a == 0 && lane == 0)
+		*reinterpret_cast<u32x4*>(&ring_of(L)[RING]) = v0;
+	rrec_of(L)[64 * (c & 3) + lane] = r;
+}
+
+// The batch cut, from the staged records of the 64 sub-segments from k0, one
+// per lane: lanes [0, m) form a batch of at most `ow` output bytes and at
+// most `seqs` sequences (OW and MAXSEQ; decode_block's experiment macros
+// pass a smaller cut).  m == 0: the first sub-segment alone exceeds a limit
+// -- an oversized batch, the 64 sub-segments go straight to HBM.
+struct BatchCut {
+	uint32_t bm;           // this lane's sequence starts (pass 1's bitmap of its sub-segment)
+	int32_t cnt, nseq;     // its output bytes (at most 2^24: above any cap, which the caller checks) and sequences
+	int32_t incl, incl_s;  // their inclusive sums over the wave
+	int32_t m;
+};
+template <class LD>
+__device__ __forceinline__ BatchCut batch_cut(LD& L, int32_t k0, int32_t nsub, int32_t ow, int32_t seqs)
+{
+	const int32_t k = k0 + int32_t(lane_id());
+	const uint64_t rec = (k < nsub) ? rrec_of(L)[k & 255] : 0;
+	BatchCut c;
+	c.bm = uint32_t(rec);
+	c.cnt = int32_t(min(uint32_t(rec >> 32), 1u << 24));
+	c.nseq = __popc(c.bm);
+	c.incl = wave_incl_scan(c.cnt);
+	c.incl_s = wave_incl_scan(c.nseq);
+	c.m = __popcll(__ballot(c.incl <= ow && c.incl_s <= seqs));
+	return c;
+}
+
+// The flush: whole 16-byte units of output bytes [from, to) from the window
+// to HBM (the first may start before `from`: those bytes are in the window
+// too; a partial last unit goes with the next batch).  Always FLUSH_ST store
+// instructions, so that a later vmcnt wait can count them.
+__device__ __forceinline__ void flush_units(g8* ob, const uint8_t* window, uint32_t mask, int32_t from, int32_t to)
+{
+	const int32_t lane = int32_t(lane_id());
+	const int32_t u0 = from >> 4, u1 = to >> 4;
+#pragma unroll
+	for (int i = 0; i < FLUSH_ST; ++i) {
+		const int32_t u = u0 + lane + 64 * i;
+		if (u < u1)
+			*reinterpret_cast<GLOBAL u32x4*>(ob + (u << 4)) =
+			    *reinterpret_cast<const u32x4*>(&window[(u << 4) & mask]);
+	}
+}
+
+// The window's unflushed tail, the partial unit below output position o, to
+// HBM by one lane: before an oversized batch, and at the block's end.
+template <class LD>
+__device__ __forceinline__ void flush_tail(LD& L, g8* ob, int32_t o)
+{
+	const int32_t a0 = o & ~15;
+	if (lane_id() == 0 && o > a0)
+		gstore_n(ob + a0, *reinterpret_cast<const u32x4*>(&oring_of(L)[uint32_t(a0) & omask_of(L)]), o - a0);
+}
+
+// Dealing two rounds' pieces over the wave (HBM-sourced match pieces,
+// literal pieces): lane i has nc0 pieces in round 0 and nc1 in round 1; the
+// batch's pieces are numbered round 0's first, in lane order.
+struct Deal2 {
+	int32_t inc0, tot0;  // round 0: inclusive sum, total
+	int32_t inc1, tot;   // both rounds: tot0 + round 1's inclusive sum, total
+};
+__device__ __forceinline__ Deal2 deal2(int32_t nc0, int32_t nc1)
+{
+	Deal2 d;
+	d.inc0 = wave_incl_scan(nc0);
+	d.tot0 = wave_last(d.inc0);
+	d.inc1 = d.tot0 + wave_incl_scan(nc1);
+	d.tot = wave_last(d.inc1);
+	return d;
+}
+// A run's descriptor, which its dealt pieces read from ldesc (lane i writes
+// round 0's at [i] and round 1's at [64 + i]): 4 x 16 bits.
+struct DealRun {
+	int32_t src;   // a match: its batch-relative destination; literals: their input position in the batch
+	int32_t aux;   // a match: its offset; literals: their batch-relative destination
+	int32_t len;   // the run's bytes
+	int32_t excl;  // the batch's pieces before the run's first
+};
+__device__ __forceinline__ uint64_t deal_pack(int32_t src, int32_t aux, int32_t len, int32_t excl)
+{
+	return uint64_t(uint16_t(src)) | (uint64_t(uint16_t(aux)) << 16) | (uint64_t(uint16_t(len)) << 32) |
+	       (uint64_t(uint16_t(excl)) << 48);
+}
+__device__ __forceinline__ DealRun deal_unpack(uint64_t dd)
+{
+	return DealRun{ int32_t(dd & 0xffffu), int32_t((dd >> 16) & 0xffffu), int32_t((dd >> 32) & 0xffffu),
+	                int32_t(dd >> 48) };
+}
 // One block.  hist: output bytes right before this block's slot that its
 // matches may read -- 0 for independent blocks; in a linked frame, the
 // earlier blocks' output, contiguous when every one of them is full.
@@ -2038,12 +713,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		if (hi < cf + 3) {
 			staged = true;
 			auto stage_one = [&]() {
-				const uint32_t a = uint32_t(hi * BATCH) & (RING - 1);
-				*reinterpret_cast<u32x4*>(&D.ring[a + 16 * lane]) = pf0;
-				*reinterpret_cast<u32x4*>(&D.ring[a + 1024 + 16 * lane]) = pf1;
-				if (a == 0 && lane == 0)
-					*reinterpret_cast<u32x4*>(&D.ring[RING]) = pf0;
-				D.rrec[64 * (hi & 3) + lane] = pr;
+				stage_chunk(D, hi, pf0, pf1, pr);
 				++hi;
 				load_chunk2(abase, hi, lim, pf0, pf1);
 				pr = load_rec(hi);
@@ -2061,20 +731,12 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 
 		ISTAMP(D_STAGE);
 		ICOUNT(D_BATCHES, 1);
-		const int32_t k = k0 + lane;  // this lane's sub-segment
-		const int32_t sub_s = k * SUB;
+		const int32_t sub_s = (k0 + lane) * SUB;  // this lane's sub-segment
 		const int32_t sub_end = min(sub_s + SUB, n);
-		// this lane's sequence starts and output bytes, from pass 1's record
-		const uint64_t rec = (k < nsub) ? D.rrec[k & 255] : 0;
-		uint32_t bm = uint32_t(rec);
-		const int32_t cnt = int32_t(min(uint32_t(rec >> 32), 1u << 24));  // > cap: rejected below
-		const int32_t nseq = __popc(bm);
-		const int32_t p0 = bm ? sub_s + __builtin_ctz(bm) : n;
-		const int32_t incl = wave_incl_scan(cnt);
-		const int32_t incl_s = wave_incl_scan(nseq);
-		const int32_t o_lane = o_batch + incl - cnt;
-		const bool fit = incl <= LZ4ADA_OW_CUT && incl_s <= LZ4ADA_SEQ_CUT;
-		const int32_t m = __popcll(__ballot(fit));  // lanes [0, m) form an LDS batch
+		const BatchCut c = batch_cut(D, k0, nsub, LZ4ADA_OW_CUT, LZ4ADA_SEQ_CUT);
+		const int32_t m = c.m;  // lanes [0, m) form an LDS batch
+		const int32_t p0 = c.bm ? sub_s + __builtin_ctz(c.bm) : n;
+		const int32_t o_lane = o_batch + c.incl - c.cnt;
 		ISTAMP(D_WALK1);
 
 		if (m == 0) {
@@ -2083,14 +745,12 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				break;
 			}
 			// oversized: all 64 sub-segments straight to HBM
-			const int32_t total = wave_last(incl);
+			const int32_t total = wave_last(c.incl);
 			if (o_batch + total > cap) {
 				bad = true;
 				break;
 			}
-			const int32_t a0 = o_batch & ~15;
-			if (lane == 0 && o_batch > a0)  // the ring's unflushed tail
-				gstore_n(ob + a0, *reinterpret_cast<const u32x4*>(&D.oring[a0 & OMASK]), o_batch - a0);
+			flush_tail(D, ob, o_batch);
 			vm_wait();
 			if (!batch_global(S, ob, olim, p0, sub_end, n, o_lane, o_batch, hb)) {
 				bad = true;
@@ -2111,7 +771,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			continue;
 		}
 
-		const int32_t o_end = o_batch + wave_get(incl, m - 1);
+		const int32_t o_end = o_batch + wave_get(c.incl, m - 1);
 		if (o_end > cap) {
 			bad = true;
 			break;
@@ -2119,13 +779,13 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		// the batch's sequence starts, in output order
 		const int32_t base = k0 * SUB;
 		if (lane < m) {
-			int32_t e = incl_s - nseq;
+			int32_t e = c.incl_s - c.nseq;
 			const uint16_t rel = uint16_t(sub_s - base);
-			for (; bm; bm &= bm - 1)
+			for (uint32_t bm = c.bm; bm; bm &= bm - 1)
 				D.cst[e++] = uint16_t(rel + __builtin_ctz(bm));
 		}
 		wave_lds_fence();
-		const int32_t N = wave_get(incl_s, m - 1);
+		const int32_t N = wave_get(c.incl_s, m - 1);
 		// HBM holds every byte below align_down(o_batch, 16) (earlier
 		// flushes); a match reading below glo reads HBM (its source ends
 		// before o_batch - 16), anything newer is in the ring
@@ -2284,46 +944,41 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 			GCOUNT(2, 1);
 			static_assert(RMAX == 2, "HBM piece dealing pairs two rounds");
 			if (__any(nc[0] > 0 || nc[1] > 0)) {
-				const int32_t inc0 = wave_incl_scan(nc[0]);
-				const int32_t tot0 = wave_last(inc0);
-				const int32_t inc1 = tot0 + wave_incl_scan(nc[1]);
-				const int32_t tot = wave_last(inc1);
-				rtot[0] = tot0;
-				rtot[1] = tot - tot0;
+				const Deal2 dl = deal2(nc[0], nc[1]);
+				rtot[0] = dl.tot0;
+				rtot[1] = dl.tot - dl.tot0;
 				rfirst[0] = 64;
-				rfirst[1] = max(64 - tot0, 0);
+				rfirst[1] = max(64 - dl.tot0, 0);
 				auto pack = [&](int32_t md, int32_t of, int32_t m, int32_t excl) -> uint64_t {
-					return uint64_t(uint16_t(md - o_batch)) | (uint64_t(uint16_t(of)) << 16) |
-					       (uint64_t(uint16_t(m)) << 32) | (uint64_t(uint16_t(excl)) << 48);
+					return deal_pack(md - o_batch, of, m, excl);
 				};
-				D.ldesc[lane] = pack(rdst[0] + rL[0], roff[0], rml[0], inc0 - nc[0]);
-				D.ldesc[64 + lane] = pack(rdst[1] + rL[1], roff[1], rml[1], inc1 - nc[1]);
-				const int32_t lo = min(chunk_owner2(D, inc0, nc[0], inc1, nc[1], 0), 127);
-				const uint64_t dd = D.ldesc[lo];
-				const int32_t od = o_batch + int32_t(dd & 0xffffu);
-				const int32_t ooff = int32_t((dd >> 16) & 0xffffu);
+				D.ldesc[lane] = pack(rdst[0] + rL[0], roff[0], rml[0], dl.inc0 - nc[0]);
+				D.ldesc[64 + lane] = pack(rdst[1] + rL[1], roff[1], rml[1], dl.inc1 - nc[1]);
+				const int32_t lo = min(chunk_owner2(D, dl.inc0, nc[0], dl.inc1, nc[1], 0), 127);
+				const DealRun u = deal_unpack(D.ldesc[lo]);
+				const int32_t od = o_batch + u.src, ooff = u.aux;
 				// (a match's dealt pieces are its pieces 0 .. K - 2, whole; its
 				// last is its own lane's)
-				const int32_t k = lane - int32_t(dd >> 48);
-				GCOUNT(0, __popcll(__ballot(lane < tot)));
-				GCOUNT(1, __popcll(__ballot(lane < tot)) +
-				              __popcll(__ballot(lane < tot && ((od - ooff + 16 * k) & 127) > 112)));
-				if (lane < tot) {
+				const int32_t k = lane - u.excl;
+				GCOUNT(0, __popcll(__ballot(lane < dl.tot)));
+				GCOUNT(1, __popcll(__ballot(lane < dl.tot)) +
+				              __popcll(__ballot(lane < dl.tot && ((od - ooff + 16 * k) & 127) > 112)));
+				if (lane < dl.tot) {
 					rpd = od + 16 * k;
 					rph = true;
 					__builtin_memcpy(&vr, ob + (od - ooff) + 16 * k, 16);
 				}
-				if (tot > 64) {
+				if (dl.tot > 64) {
 					ICOUNT(D_HOVF_B, 1);
-					ICOUNT(D_HOVF_P, tot - 64);
+					ICOUNT(D_HOVF_P, dl.tot - 64);
 				}
-				if (BORROW && tot > 64) {
+				if (BORROW && dl.tot > 64) {
 					// pieces 64 ..: one each to the lanes whose own-piece slot
 					// vg[r][0] is idle (the round's match is not HBM-sourced),
 					// round 0's idle lanes first, in lane order.  The idle lane
 					// of rank i takes piece first + i; its owner is entry i -
 					// 64 + first of the second chunk's owners.
-					const int32_t own2 = min(chunk_owner2(D, inc0, nc[0], inc1, nc[1], 64), 127);
+					const int32_t own2 = min(chunk_owner2(D, dl.inc0, nc[0], dl.inc1, nc[1], 64), 127);
 					int32_t first = 64;
 #pragma unroll
 					for (int r = 0; r < RMAX; ++r) {
@@ -2334,18 +989,16 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 						const int32_t t = first + int32_t(__builtin_amdgcn_mbcnt_hi(
 						                              uint32_t(im >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(im), 0u)));
 						const int32_t bo = __shfl(own2, (t - 64) & 63);
-						if (idle && t < min(tot, 128)) {
-							const uint64_t bd = D.ldesc[bo];
-							const int32_t brel = int32_t(bd & 0xffffu);
-							const int32_t bk = t - int32_t(bd >> 48);
-							bpc[r] = (brel + 16 * bk) | (16 << 12);  // (a dealt piece: whole)
-							__builtin_memcpy(&vg[r][0], ob + (o_batch + brel - int32_t((bd >> 16) & 0xffffu)) + 16 * bk,
-							                 16);
+						if (idle && t < min(dl.tot, 128)) {
+							const DealRun bu = deal_unpack(D.ldesc[bo]);
+							const int32_t bk = t - bu.excl;
+							bpc[r] = (bu.src + 16 * bk) | (16 << 12);  // (a dealt piece: whole)
+							__builtin_memcpy(&vg[r][0], ob + (o_batch + bu.src - bu.aux) + 16 * bk, 16);
 						}
-						first = min(first + __popcll(im), min(tot, 128));
+						first = min(first + __popcll(im), min(dl.tot, 128));
 					}
 					rfirst[0] = first;
-					rfirst[1] = max(first - tot0, 0);
+					rfirst[1] = max(first - dl.tot0, 0);
 				}
 				wave_lds_fence();  // ldesc / own[] are written again later
 			}
@@ -2371,24 +1024,19 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 				       rL[r] - c);
 			}
 			if (__any(nc0 > 0 || nc1 > 0)) {
-				const int32_t inc0 = wave_incl_scan(nc0);
-				const int32_t tot0 = wave_last(inc0);
-				const int32_t inc1 = tot0 + wave_incl_scan(nc1);
-				const int32_t tot = wave_last(inc1);
+				const Deal2 dl = deal2(nc0, nc1);
 				auto pack = [&](int32_t lit, int32_t dst, int32_t L, int32_t excl) -> uint64_t {
-					return uint64_t(uint16_t(lit - base)) | (uint64_t(uint16_t(dst - o_batch)) << 16) |
-					       (uint64_t(uint16_t(L)) << 32) | (uint64_t(uint16_t(excl)) << 48);
+					return deal_pack(lit - base, dst - o_batch, L, excl);
 				};
-				D.ldesc[lane] = pack(rlit[0], rdst[0], rL[0], inc0 - nc0);
-				D.ldesc[64 + lane] = pack(rlit[1], rdst[1], rL[1], inc1 - nc1);
-				for (int32_t t0 = 0; t0 < tot; t0 += 64) {
+				D.ldesc[lane] = pack(rlit[0], rdst[0], rL[0], dl.inc0 - nc0);
+				D.ldesc[64 + lane] = pack(rlit[1], rdst[1], rL[1], dl.inc1 - nc1);
+				for (int32_t t0 = 0; t0 < dl.tot; t0 += 64) {
 					const int32_t t = t0 + lane;
-					const int32_t lo = min(chunk_owner2(D, inc0, nc0, inc1, nc1, t0), 127);
-					const uint64_t dd = D.ldesc[lo];
-					const int32_t lit = base + int32_t(dd & 0xffffu);
-					const int32_t dst = o_batch + int32_t((dd >> 16) & 0xffffu);
-					const int32_t k = t - int32_t(dd >> 48);  // pieces 0 .. K - 2 (the last went in-lane)
-					const bool has = t < tot;
+					const int32_t lo = min(chunk_owner2(D, dl.inc0, nc0, dl.inc1, nc1, t0), 127);
+					const DealRun u = deal_unpack(D.ldesc[lo]);
+					const int32_t lit = base + u.src, dst = o_batch + u.aux;
+					const int32_t k = t - u.excl;  // pieces 0 .. K - 2 (the last went in-lane)
+					const bool has = t < dl.tot;
 					ostore16(D, dst + 16 * k, ZL ? u32x4{ 0u, 0u, 0u, 0u } : fetch16(S, has ? lit + 16 * k : S.lo),
 					         has);
 				}
@@ -2537,19 +1185,7 @@ __device__ __forceinline__ int32_t decode_block(DecLds& D, const uint8_t* __rest
 		}
 		ISTAMP(D_NEAR);
 
-		// flush whole 16-byte units of [o_batch, o_end) (the first may start
-		// before o_batch: those bytes are in the ring too); always FLUSH_ST
-		// store instructions, so the wait above can count them
-		{
-			const int32_t u0 = o_batch >> 4, u1 = o_end >> 4;
-#pragma unroll
-			for (int i = 0; i < FLUSH_ST; ++i) {
-				const int32_t u = u0 + lane + 64 * i;
-				if (u < u1)
-					*reinterpret_cast<GLOBAL u32x4*>(ob + (u << 4)) =
-					    *reinterpret_cast<const u32x4*>(&D.oring[(u << 4) & OMASK]);
-			}
-		}
+		flush_units(ob, D.oring, OMASK, o_batch, o_end);  // (P's vmcnt wait counts its stores)
 		o_batch = o_end;
 		k0 += m;
 		ISTAMP(D_FLUSH);
@@ -2850,619 +1486,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 	                    int64_t(h0));
 }
 
-// ============================================================ pipelined pair
-// k_decode_pp2 (round 5): two waves per block that pipeline consecutive
-// batches instead of splitting each one (k_decode_idx2), for launches of at
-// most one block per SIMD -- a configs[3] shard at N = 8 (1,024 blocks) --
-// where a block has the LDS (~30 KiB) and the VGPRs (two waves per SIMD at
-// <= 256) for two-round batches of up to 128 sequences in each wave.  Each
-// block's chain is latency-bound: wave w takes batches j = w,
-// w + 2, ...; batch j's staging, cut, parse, HBM-sourced loads, literals and
-// HBM-sourced stores run while the other wave is still inside batch j - 1,
-// and only the ring-sourced matches (which may read batch j - 1's output)
-// wait for batch j - 1's to be stored -- an LDS token, no barrier in the
-// batch loop.  Both waves compute every cut from the staged pass-1 records
-// (each its own batch and the next), so they agree on the batch sequence,
-// on who stages which input chunk and on the HBM threshold; spin waits on
-// LDS counters carry the hand-offs, each bounded (a hand-off that never
-// comes declines the block instead of hanging the grid).
-//
-// Window discipline (16 KiB output window, batches of <= OW bytes): while
-// batch j runs its ring-sourced matches, batch j + 1 may write its literals
-// and HBM-sourced bytes, so the window keeps [o_j - RFLOOR2, o_j + OW)
-// intact.  A match reads HBM for its source bytes below glo_j =
-// align16(o_{j-1}) rounded down to a 128-byte line (written by the flushes
-// of batches <= j - 2, whose completion each wave publishes after its own
-// vmcnt wait; a CU's L1 never gets a line holding bytes not yet flushed) in
-// whole 16-byte pieces, and the window for the rest (a match straddling the
-// threshold is split in two).  A first try with one-round batches and four
-// waves per SIMD at 2,048 blocks (k_decode_pp, commit dd280ab) ran 15.6 ms
-// against k_decode_idx's 13.3: 64-sequence batches cost ~0.7 of a
-// 128-sequence one (tools/time_decode.py, LZ4ADA_SEQ_CUT=64), and four
-// waves per SIMD slow each one ~1.3x.
-
-constexpr int ORING2 = 16384;                 // output window of the pipelined pair
-constexpr int32_t RFLOOR2 = ORING2 - 2 * OW;  // window bytes kept below a batch through its ring phase
-static_assert(OW + 16 + 128 + 16 < RFLOOR2, "the HBM threshold must lie inside the kept window");
-
-struct alignas(16) PpLds2 {
-	uint8_t ring[RING + 16];   // staged input: 4 chunks of 2 KiB (+ mirror), shared
-	uint8_t oring[ORING2];     // output window, shared
-	uint64_t rrec[4 * 64];     // pass-1 records of the staged chunks
-	uint64_t ldesc[2][2 * 64]; // per wave: run / match descriptors of both rounds
-	uint16_t cst[2][MAXSEQ];   // per wave: its batch's sequence starts
-	uint8_t own[2][256];       // per wave: piece owners
-	int32_t tok;               // last batch whose ring-sourced matches are stored
-	int32_t staged;            // input chunks staged so far
-	int32_t abort_;            // a wave declined the block
-	int32_t pad;
-	int32_t done[2];           // per wave: last own batch whose flush has completed
-};
-
-struct WP2 {
-	PpLds2& L;
-	int32_t w;
-};
-__device__ __forceinline__ uint8_t* oring_of(WP2& V) { return V.L.oring; }
-__device__ __forceinline__ const uint8_t* oring_of(const WP2& V) { return V.L.oring; }
-__device__ __forceinline__ uint8_t* own_of(WP2& V) { return V.L.own[V.w]; }
-__device__ __forceinline__ uint64_t* ldesc_of(WP2& V) { return V.L.ldesc[V.w]; }
-template <>
-constexpr uint32_t omask_v<WP2> = ORING2 - 1;
-
-__device__ __forceinline__ int32_t lds_peek(const int32_t* p)
-{
-	return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile int32_t*>(p));
-}
-
-// Publish v at p after every LDS write of this wave so far (the other wave
-// reads those once it sees v): lgkmcnt(0) only, the flush stores in flight
-// are not waited for.
-__device__ __forceinline__ void lds_publish(int32_t* p, int32_t v)
-{
-	asm volatile("" ::: "memory");
-	__builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0), vmcnt/expcnt untouched
-	*reinterpret_cast<volatile int32_t*>(p) = v;
-	asm volatile("" ::: "memory");
-}
-
-// Wait until *p >= want; false if the block was aborted meanwhile -- or
-// after ~2^24 polls (~0.5 s): a hand-off that never comes declines the
-// block (DS_RETRY: k_decode_pc redoes it) instead of hanging the grid.
-__device__ __forceinline__ bool lds_wait_ge(int32_t* abort_flag, const int32_t* p, int32_t want)
-{
-	for (uint32_t it = 0; lds_peek(p) < want; ++it) {
-		if (lds_peek(abort_flag))
-			return false;
-		if (it >= (1u << 24)) {
-			lds_publish(abort_flag, 1);
-			return false;
-		}
-		__builtin_amdgcn_s_sleep(1);
-	}
-	asm volatile("" ::: "memory");
-	return true;
-}
-
-// One batch cut from the staged records (decode_block's rule: <= OW output
-// bytes, <= MAXSEQ sequences): sub-segments [k0, k0 + m).  over: the first
-// sub-segment alone exceeds a limit -- the 64 from k0 go straight to HBM.
-struct PpCut {
-	int32_t m, bytes;
-	bool over;
-};
-__device__ __forceinline__ PpCut pp_cut(const PpLds2& L, int32_t k0, int32_t nsub)
-{
-	const int32_t k = k0 + int32_t(lane_id());
-	const uint64_t rec = k < nsub ? L.rrec[k & 255] : 0;
-	const int32_t cnt = int32_t(min(uint32_t(rec >> 32), 1u << 24));
-	const int32_t incl = wave_incl_scan(cnt);
-	const int32_t incl_s = wave_incl_scan(__popc(uint32_t(rec)));
-	PpCut c;
-	c.m = __popcll(__ballot(incl <= OW && incl_s <= MAXSEQ));
-	c.over = c.m == 0;
-	c.m = c.over ? 64 : c.m;
-	c.bytes = wave_get(incl, c.m - 1);
-	return c;
-}
-
-__device__ __forceinline__ void pp_load_chunk(uintptr_t abase, int32_t c, uintptr_t lim, const uint64_t* tab,
-                                              int32_t nsub, u32x4& v0, u32x4& v1, uint64_t& r)
-{
-	load_chunk2(abase, c, lim, v0, v1);
-	const int32_t k = 64 * c + int32_t(lane_id());
-	r = k < nsub ? __builtin_nontemporal_load(tab + k) : 0;
-}
-
-__device__ __forceinline__ void pp_stage_chunk(PpLds2& L, int32_t c, const u32x4& v0, const u32x4& v1,
-                                               uint64_t r)
-{
-	const uint32_t lane = lane_id();
-	const uint32_t a = uint32_t(c * BATCH) & (RING - 1);
-	*reinterpret_cast<u32x4*>(&L.ring[a + 16 * lane]) = v0;
-	*reinterpret_cast<u32x4*>(&L.ring[a + 1024 + 16 * lane]) = v1;
-	if (a == 0 && lane == 0)
-		*reinterpret_cast<u32x4*>(&L.ring[RING]) = v0;
-	L.rrec[64 * (c & 3) + lane] = r;
-}
-
-// Pass 2 of block b (independent; pass 1's verdict DS_OK) by both waves.
-// Returns the output length, or -1 when the block is declined.
-__device__ __forceinline__ int32_t decode_block_pp2(PpLds2& L, const uint8_t* __restrict__ frame,
-                                                    uint64_t frame_len,
-                                                    const lz4ada_block_desc* __restrict__ desc, uint32_t b,
-                                                    const uint8_t* __restrict__ tab_all,
-                                                    uint8_t* __restrict__ out)
-{
-	const int32_t tid = int32_t(threadIdx.x), w = tid >> 6, lane = tid & 63;
-	WP2 V{ L, w };
-	const lz4ada_block_desc d = wave_desc(desc, b);
-	cg8* in = gptr(frame) + d.in_off;
-	g8* ob = gptr(out) + d.out_off;
-	const int32_t n = int32_t(d.in_len);
-	const int32_t cap = int32_t(d.out_cap);
-	const uintptr_t lim = reinterpret_cast<uintptr_t>(frame) + frame_len;
-	const uintptr_t olim = reinterpret_cast<uintptr_t>(ob) + uintptr_t(cap);
-	const int32_t mis = int32_t(reinterpret_cast<uintptr_t>(in) & 15u);
-	const uint64_t* tab = reinterpret_cast<const uint64_t*>(tab_all) + (((d.in_off >> 8) + b) << 3);
-	const int32_t nsub = (n + SUB - 1) / SUB;
-	const uintptr_t abase = reinterpret_cast<uintptr_t>(in) - uintptr_t(mis);
-	constexpr uint32_t WMASK = ORING2 - 1;
-	int32_t* const abort_flag = &L.abort_;
-
-	Src S;
-	S.lds = L.ring;
-	S.mask = RING - 1;
-	S.mis = mis;
-	S.in = in;
-	S.lim = lim;
-
-	// The cut cursor: the next batch to cut is j, at sub-segment k0 and
-	// output byte o; hi = input chunks staged once the batches cut so far
-	// have staged theirs (the owner of batch j stages [hi_before, cf_j + 3)).
-	// o_prev / over_prev: batch j - 1's output start and whether it went
-	// straight to HBM.  Each wave cuts its own batch and the next one.
-	int32_t j = 0, k0 = 0, o = 0, hi = 0, o_prev = 0;
-	bool over_prev = false;
-	auto advance = [&](PpCut& c) {
-		c = pp_cut(L, k0, nsub);
-		o_prev = o;
-		over_prev = c.over;
-		o += c.bytes;
-		k0 += c.m;
-		++j;
-	};
-	auto chunk_of = [&](int32_t k) { return (k * SUB + mis) / BATCH; };
-	u32x4 pf0 = u32x4{ 0u, 0u, 0u, 0u }, pf1 = pf0;  // this wave's prefetched chunk pfc
-	uint64_t pr = 0;
-	int32_t pfc = -1;
-	bool bad = false;
-	if (w == 1 && k0 < nsub) {  // batch 0 is wave 0's: cut it once staged
-		hi = chunk_of(0) + 3;
-		PpCut c0;
-		if (lds_wait_ge(abort_flag, &L.staged, hi))
-			advance(c0);
-		else
-			bad = true;
-	}
-
-	while (!bad && k0 < nsub) {
-		// ---- batch j is this wave's
-		const int32_t jb = j, ob0 = o, kb = k0;
-		const bool prev_over = over_prev;
-		// HBM holds, complete, every byte below glo: batches <= j - 2, or all
-		// of batch j - 1 when it went straight to HBM
-		const int32_t glo = jb == 0 ? 0 : ((prev_over ? ob0 : o_prev) & ~15);
-		const int32_t cf = chunk_of(kb);
-		const int32_t hi_before = hi;
-		hi = max(hi, cf + 3);
-		if (!lds_wait_ge(abort_flag, &L.staged, hi_before)) {
-			bad = true;
-			break;
-		}
-		for (int32_t c = hi_before; c < hi; ++c) {
-			if (c != pfc) {
-				pp_load_chunk(abase, c, lim, tab, nsub, pf0, pf1, pr);
-				__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): a rare path's loads settle here
-			}
-			pp_stage_chunk(L, c, pf0, pf1, pr);
-			pfc = -1;
-		}
-		if (hi > hi_before)
-			lds_publish(&L.staged, hi);
-		S.lo = cf * BATCH - mis;
-		S.hi = hi * BATCH - mis;
-		// this batch's cut, then the next one's (its records are staged:
-		// chunks <= cf + 2), which places this wave's next batch: prefetch the
-		// chunk that batch will stage
-		PpCut cb;
-		advance(cb);
-		const int32_t oe = o;
-		bool next_over = false;
-		int32_t npf = 0;  // vector loads issued after this wave's last flush
-		if (k0 < nsub) {
-			hi = max(hi, chunk_of(k0) + 3);
-			PpCut cn;
-			advance(cn);
-			next_over = cn.over;
-			if (k0 < nsub && chunk_of(k0) + 3 > hi) {
-				pfc = hi;
-				pp_load_chunk(abase, pfc, lim, tab, nsub, pf0, pf1, pr);
-				npf = 3;
-			}
-		}
-		if (oe > cap) {
-			bad = true;
-			lds_publish(abort_flag, 1);
-			break;
-		}
-		if (cb.over) {
-			// ---- a sub-segment alone exceeds the batch limits: the 64
-			// sub-segments go straight to HBM (batch_global), alone -- after
-			// every earlier batch's bytes are final in HBM and in the window
-			if (!lds_wait_ge(abort_flag, &L.tok, jb - 1) || !lds_wait_ge(abort_flag, &L.done[w ^ 1], jb - 1)) {
-				bad = true;
-				break;
-			}
-			vm_wait();
-			const int32_t k = kb + lane;
-			const int32_t sub_s = k * SUB;
-			const int32_t sub_end = min(sub_s + SUB, n);
-			const uint64_t rec = (k < nsub) ? L.rrec[k & 255] : 0;
-			const uint32_t bm = uint32_t(rec);
-			const int32_t cnt = int32_t(min(uint32_t(rec >> 32), 1u << 24));
-			const int32_t p0 = bm ? sub_s + __builtin_ctz(bm) : n;
-			const int32_t incl = wave_incl_scan(cnt);
-			const int32_t a0 = ob0 & ~15;
-			if (lane == 0 && ob0 > a0)  // the window's unflushed tail
-				gstore_n(ob + a0, *reinterpret_cast<const u32x4*>(&L.oring[a0 & WMASK]), ob0 - a0);
-			vm_wait();
-			const bool ok = !__any(!batch_global(S, ob, olim, p0, sub_end, n, ob0 + incl - cnt, ob0, 0));
-			vm_wait();
-			if (!ok) {
-				bad = true;
-				lds_publish(abort_flag, 1);
-				break;
-			}
-			// the window's history again, from HBM (nontemporal: past the L1,
-			// which may hold lines of this batch from before their stores)
-			const int32_t x0 = max(oe - ORING2 + 16, 0) & ~15;
-			for (int32_t x = x0 + 16 * lane; x < oe + 15; x += 64 * 16)
-				*reinterpret_cast<u32x4*>(&L.oring[uint32_t(x) & WMASK]) =
-				    x + 16 <= cap ? __builtin_nontemporal_load(reinterpret_cast<const GLOBAL u32x4*>(ob + x))
-				                  : gload16(reinterpret_cast<uintptr_t>(ob) + uintptr_t(intptr_t(x)), olim);
-			__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-			lds_publish(&L.done[w], jb);
-			lds_publish(&L.tok, jb);
-			continue;
-		}
-		if (prev_over && !lds_wait_ge(abort_flag, &L.tok, jb - 1)) {
-			bad = true;  // (the batch before went straight to HBM: its window reload first)
-			break;
-		}
-
-		// ---- the batch's sequence starts, in output order
-		const int32_t base = kb * SUB;
-		int32_t N;
-		{
-			const int32_t k = kb + lane;
-			const int32_t sub_s = k * SUB;
-			const uint64_t rec = (k < nsub) ? L.rrec[k & 255] : 0;
-			uint32_t bm = uint32_t(rec);
-			const int32_t nseq = __popc(bm);
-			const int32_t incl_s = wave_incl_scan(nseq);
-			if (lane < cb.m) {
-				int32_t e = incl_s - nseq;
-				const uint16_t rel = uint16_t(sub_s - base);
-				for (; bm; bm &= bm - 1)
-					L.cst[w][e++] = uint16_t(rel + __builtin_ctz(bm));
-			}
-			N = wave_get(incl_s, cb.m - 1);
-		}
-		wave_lds_fence();
-		const int32_t gl = glo & ~127;  // HBM pieces end in whole lines below this
-
-		// ---- P: up to 64 sequences per round, placed by a prefix sum; each
-		// match split into its HBM part (hml bytes) and its window part
-		int32_t rL[RMAX], rlit[RMAX], roff[RMAX], rml[RMAX], rdst[RMAX], rbeg[RMAX], hml[RMAX];
-		bool pre = false, anyg = false;
-		{
-			int32_t o_round = ob0;
-			// both rounds parsed first, then the rare shapes, then placement
-			// (as decode_block)
-			bool fok[RMAX];
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r) {
-				rL[r] = rlit[r] = roff[r] = rml[r] = hml[r] = 0;
-				fok[r] = true;
-				const int32_t idx = 64 * r + lane;
-				if (idx < N) {
-					Seq q;
-					fok[r] = parse_fast_try(S, base + int32_t(L.cst[w][idx]), n, q);
-					rL[r] = q.L;
-					rlit[r] = q.lit;
-					roff[r] = q.off;
-					rml[r] = q.ml;
-				}
-			}
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r) {
-				if (__builtin_expect(__any(!fok[r]), 0)) {
-					if (!fok[r]) {
-						Seq q;
-						parse_seq(S, base + int32_t(L.cst[w][64 * r + lane]), n, q);
-						rL[r] = q.L;
-						rlit[r] = q.lit;
-						roff[r] = q.off;
-						rml[r] = q.ml;
-					}
-				}
-			}
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r) {
-				rbeg[r] = o_round;
-				if (64 * r < N) {
-					const int32_t len = rL[r] + rml[r];
-					const int32_t inc = wave_incl_scan(len);
-					rdst[r] = o_round + inc - len;
-					o_round += wave_last(inc);
-					const int32_t mdst = rdst[r] + rL[r];
-					if (rml[r] > 0) {
-						if (roff[r] > mdst)
-							pre = true;  // a reference before the block start (D2)
-						const int32_t room = gl - (mdst - roff[r]);
-						hml[r] = ((rml[r] + 15) & ~15) <= room ? rml[r] : max(room & ~15, 0);
-						if (hml[r] > 0)
-							anyg = true;
-					}
-				}
-			}
-		}
-		if (__any(pre)) {
-			bad = true;
-			lds_publish(abort_flag, 1);
-			break;
-		}
-
-		// ---- HBM-sourced parts: this wave's flush of batch j - 2 first (the
-		// prefetch loads issued after it may stay in flight), then the other
-		// wave's of batch j - 3; every load in flight before the first use: a
-		// part's first piece in its own lane, the rest of both rounds dealt
-		if (npf)
-			asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-		else
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		lds_publish(&L.done[w], max(jb - 2, -1));
-		u32x4 vg[RMAX], vr = u32x4{ 0u, 0u, 0u, 0u };
-		int32_t rtot[RMAX], rfirst[RMAX];
-		int32_t rpd = 0, rpn = 0;
-#pragma unroll
-		for (int r = 0; r < RMAX; ++r) {
-			vg[r] = vr;
-			rtot[r] = rfirst[r] = 0;
-		}
-		if (__any(anyg)) {
-			if (!lds_wait_ge(abort_flag, &L.done[w ^ 1], jb - 3)) {
-				bad = true;
-				break;
-			}
-			int32_t nc[RMAX];
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r) {
-				nc[r] = 0;
-				if (64 * r < N) {
-					const int32_t src = rdst[r] + rL[r] - roff[r];
-					if (hml[r] > 0)
-						__builtin_memcpy(&vg[r], ob + src, 16);
-					nc[r] = hml[r] > 0 ? max(((hml[r] + 15) >> 4) - 1, 0) : 0;
-				}
-			}
-			if (__any(nc[0] > 0 || nc[1] > 0)) {
-				const int32_t inc0 = wave_incl_scan(nc[0]);
-				const int32_t tot0 = wave_last(inc0);
-				const int32_t inc1 = tot0 + wave_incl_scan(nc[1]);
-				const int32_t tot = wave_last(inc1);
-				rtot[0] = tot0;
-				rtot[1] = tot - tot0;
-				rfirst[0] = 64;
-				rfirst[1] = max(64 - tot0, 0);
-				auto pack = [&](int32_t md, int32_t of, int32_t m, int32_t excl) -> uint64_t {
-					return uint64_t(uint16_t(md - ob0)) | (uint64_t(uint16_t(of)) << 16) |
-					       (uint64_t(uint16_t(m)) << 32) | (uint64_t(uint16_t(excl)) << 48);
-				};
-				uint64_t* ldesc = ldesc_of(V);
-				ldesc[lane] = pack(rdst[0] + rL[0], roff[0], hml[0], inc0 - nc[0]);
-				ldesc[64 + lane] = pack(rdst[1] + rL[1], roff[1], hml[1], inc1 - nc[1]);
-				const int32_t lo = min(chunk_owner2(V, inc0, nc[0], inc1, nc[1], 0), 127);
-				const uint64_t dd = ldesc[lo];
-				const int32_t od = ob0 + int32_t(dd & 0xffffu);
-				const int32_t ooff = int32_t((dd >> 16) & 0xffffu), oml = int32_t((dd >> 32) & 0xffffu);
-				const int32_t k = 1 + lane - int32_t(dd >> 48);
-				if (lane < tot) {
-					rpd = od + 16 * k;
-					rpn = min(16, oml - 16 * k);
-					__builtin_memcpy(&vr, ob + (od - ooff) + 16 * k, 16);
-				}
-				wave_lds_fence();  // ldesc / own are written again later
-			}
-		}
-
-		// ---- L: literals (input ring -> window), first pieces in-lane, the
-		// rest of both rounds dealt
-		{
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r)
-				if (rL[r] > 0)
-					ostore(V, rdst[r], fetch16(S, rlit[r]), min(16, rL[r]));
-			const int32_t nc0 = rL[0] > 16 ? (rL[0] - 1) >> 4 : 0;
-			const int32_t nc1 = rL[1] > 16 ? (rL[1] - 1) >> 4 : 0;
-			if (__any(nc0 > 0 || nc1 > 0)) {
-				const int32_t inc0 = wave_incl_scan(nc0);
-				const int32_t tot0 = wave_last(inc0);
-				const int32_t inc1 = tot0 + wave_incl_scan(nc1);
-				const int32_t tot = wave_last(inc1);
-				auto pack = [&](int32_t lit, int32_t dst, int32_t Lx, int32_t excl) -> uint64_t {
-					return uint64_t(uint16_t(lit - base)) | (uint64_t(uint16_t(dst - ob0)) << 16) |
-					       (uint64_t(uint16_t(Lx)) << 32) | (uint64_t(uint16_t(excl)) << 48);
-				};
-				uint64_t* ldesc = ldesc_of(V);
-				ldesc[lane] = pack(rlit[0], rdst[0], rL[0], inc0 - nc0);
-				ldesc[64 + lane] = pack(rlit[1], rdst[1], rL[1], inc1 - nc1);
-				for (int32_t t0 = 0; t0 < tot; t0 += 64) {
-					const int32_t t = t0 + lane;
-					const int32_t lo = min(chunk_owner2(V, inc0, nc0, inc1, nc1, t0), 127);
-					const uint64_t dd = ldesc[lo];
-					const int32_t lit = base + int32_t(dd & 0xffffu);
-					const int32_t dst = ob0 + int32_t((dd >> 16) & 0xffffu);
-					const int32_t Lx = int32_t((dd >> 32) & 0xffffu);
-					const int32_t k = 1 + t - int32_t(dd >> 48);
-					if (t < tot)
-						ostore(V, dst + 16 * k, fetch16(S, lit + 16 * k), min(16, Lx - 16 * k));
-				}
-			}
-		}
-		wave_lds_fence();
-
-		// ---- M: the HBM-sourced parts (sources in HBM: no order among them)
-		int32_t mring[RMAX], oring[RMAX], lring[RMAX];
-		__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-		if (rpn > 0)
-			ostore(V, rpd, vr, rpn);
-#pragma unroll
-		for (int r = 0; r < RMAX; ++r) {
-			mring[r] = oring[r] = lring[r] = 0;
-			if (64 * r < N) {
-				const int32_t mdst = rdst[r] + rL[r];
-				if (hml[r] > 0)
-					ostore(V, mdst, vg[r], min(16, hml[r]));
-				if (rtot[r] > rfirst[r]) {  // more than 64 dealt pieces (common on mixed data); the rest now
-					const int32_t nc = hml[r] > 0 ? max(((hml[r] + 15) >> 4) - 1, 0) : 0;
-					const int32_t inc = wave_incl_scan(nc);
-					for (int32_t t0 = rfirst[r]; t0 < rtot[r]; t0 += 64) {
-						const int32_t t = t0 + lane;
-						const int32_t lo = piece_owner(inc, t);
-						const int32_t k = 1 + t - (__shfl(inc, lo) - __shfl(nc, lo));
-						const int32_t osrc = __shfl(mdst - roff[r], lo), odst = __shfl(mdst, lo);
-						const int32_t oml = __shfl(hml[r], lo);
-						if (t < rtot[r]) {
-							u32x4 v;
-							__builtin_memcpy(&v, ob + osrc + 16 * k, 16);
-							ostore(V, odst + 16 * k, v, min(16, oml - 16 * k));
-						}
-					}
-					__builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-				}
-				// the window part: the match's bytes from hml on
-				mring[r] = mdst + hml[r];
-				oring[r] = roff[r];
-				lring[r] = rml[r] - hml[r];
-			}
-		}
-		wave_lds_fence();
-
-		// ---- window-sourced matches, after batch j - 1's
-		if (!lds_wait_ge(abort_flag, &L.tok, jb - 1)) {
-			bad = true;
-			break;
-		}
-		static_assert(RMAX == 2, "ring dealing pairs two rounds");
-		if (__any(lring[0] > RING_LANE_MAX || lring[1] > RING_LANE_MAX)) {
-			ring_pieces(V, mring, oring, lring, ob0);
-		} else {
-#pragma unroll
-			for (int r = 0; r < RMAX; ++r)
-				if (64 * r < N)
-					ring_lanes(V, mring[r], oring[r], lring[r], rbeg[r], rL[r], ob0 - RFLOOR2);
-		}
-		lds_publish(&L.tok, jb);
-
-		// ---- flush whole 16-byte units of [ob0, oe) (the first may start
-		// before ob0: batch j - 1's bytes, final since its token)
-		{
-			const int32_t u0 = ob0 >> 4, u1 = oe >> 4;
-#pragma unroll
-			for (int i = 0; i < FLUSH_ST; ++i) {
-				const int32_t u = u0 + lane + 64 * i;
-				if (u < u1)
-					*reinterpret_cast<GLOBAL u32x4*>(ob + (u << 4)) =
-					    *reinterpret_cast<const u32x4*>(&L.oring[(u << 4) & WMASK]);
-			}
-		}
-		if (next_over) {
-			// the next batch goes straight to HBM once this flush is complete
-			vm_wait();
-			lds_publish(&L.done[w], jb);
-		}
-	}
-	// the last partial unit (after both waves' batches), by wave 0
-	__syncthreads();
-	bad = bad || lds_peek(abort_flag) != 0;
-	if (!bad && tid == 0 && (o & 15))
-		gstore_n(ob + (o & ~15), *reinterpret_cast<const u32x4*>(&L.oring[(o & ~15) & WMASK]), o & 15);
-	return bad ? -1 : o;
-}
-
-// Independent blocks, both passes, two waves per block pipelining batches
-// (pass 1: index_block<2>, both waves walking each chunk).  Two waves per SIMD
-// (<= 256 VGPRs; the block checksum kernel's 118 still fit beside them at
-// one block per SIMD).
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2))) void k_decode_pp2(
-        const uint8_t* __restrict__ frame, uint64_t frame_len, const lz4ada_block_desc* __restrict__ desc,
-        uint32_t nblocks, uint8_t* __restrict__ tab_all, uint8_t* __restrict__ out,
-        lz4ada_block_status* __restrict__ status)
-{
-	__shared__ union {
-		PpLds2 d;
-		IdxLds<2> x;
-	} U;
-	if (blockIdx.x >= nblocks)
-		return;
-	const uint32_t b = blockIdx.x;
-	const int32_t tid = int32_t(threadIdx.x), w = tid >> 6;
-	index_block<2>(U.x, frame, frame_len, desc, b, tab_all, status);
-	// the table and status this block's pass 1 wrote are read back by both waves
-	vm_wait();
-	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	__syncthreads();
-	const lz4ada_block_desc d = desc[b];
-	if (status[b].code != DS_OK)
-		return;  // declined: its status says so
-	if (d.flags & LZ4ADA_BLOCK_STORED) {
-		const int32_t n = int32_t(d.in_len);
-		int32_t c = DS_OK;
-		if (n > int32_t(d.out_cap)) {
-			c = DS_OUT_OVERFLOW;
-		} else {  // each wave copies half
-			Src S0;
-			S0.in = gptr(frame) + d.in_off;
-			S0.lim = reinterpret_cast<uintptr_t>(frame) + frame_len;
-			const int32_t mid = (n >> 1) & ~1023;
-			const int32_t c0 = w == 0 ? 0 : mid, c1 = w == 0 ? mid : n;
-			if (d.flags & LZ4ADA_BLOCK_HAS_CKSUM)
-				wave_literal<0>(gptr(out) + d.out_off, c0, S0, c0, c1 - c0);
-			else
-				wave_literal<LZ4ADA_STORED_NT>(gptr(out) + d.out_off, c0, S0, c0, c1 - c0);
-		}
-		if (tid == 0)
-			put_status(status[b], c, n);
-		return;
-	}
-	PpLds2& L = U.d;
-	if (tid == 0) {
-		L.tok = -1;  // "batches <= -1 done"
-		L.staged = 0;
-		L.abort_ = 0;
-		L.done[0] = L.done[1] = -1;
-	}
-	__syncthreads();
-	const int32_t len = decode_block_pp2(L, frame, frame_len, desc, b, tab_all, out);
-	if (tid == 0) {
-		if (len < 0)
-			status[b].code = DS_RETRY;
-		else
-			put_status(status[b], DS_OK, len);
-	}
-}
+#include "lz4ada_idx_pair.inc"    // PpLds2 / WP2, the LDS hand-offs, decode_block_pp2, k_decode_pp2
 
 }  // namespace idx
 

@@ -10,16 +10,18 @@
 An instruction belongs to the call-site line inside decode_block or
 index_block that its .loc's inline chain leads to.  The phases are the
 stretches between the ISTAMP() marks of those two functions, read from the
-source, so they follow the file as it changes: pass 1's stage / lead-in /
-first walk / re-walk / table write (index_block) and pass 2's phases
-(decode_block), named as tools/idx_stamps.py names their cycles."""
+source (lz4ada_idx.hip and the part it includes, lz4ada_idx_pass1.inc), so
+they follow the files as they change: pass 1's stage / lead-in / first walk /
+re-walk / table write (index_block) and pass 2's phases (decode_block),
+named as tools/idx_stamps.py names their cycles."""
 import collections
 import os
 import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "bo-lz4-ada_amd", "csrc", "lz4ada_idx.hip")
+CSRC = os.path.join(ROOT, "bo-lz4-ada_amd", "csrc")
+UNIT, PASS1 = "lz4ada_idx.hip", "lz4ada_idx_pass1.inc"
 P1_NAMES = {"I_STAGE": "p1 stage", "I_LEAD": "p1 lead-in", "I_WALK0": "p1 first walk",
             "I_ITER": "p1 re-walk"}
 
@@ -32,31 +34,32 @@ def func_range(src, name):
     return a + 1, b + 1
 
 
-def phases(src):
-    """[(first line, last line, name)] of index_block and decode_block."""
+def phases(srcs):
+    """[(file, first line, last line, name)] of index_block and decode_block."""
     ph = []
-    for fn, tail, names in (("index_block", "p1 table write", P1_NAMES), ("decode_block", "end", {})):
+    for f, fn, tail, names in ((PASS1, "index_block", "p1 table write", P1_NAMES), (UNIT, "decode_block", "end", {})):
+        src = srcs[f]
         a, b = func_range(src, fn)
         cur = a
         for i in range(a, b + 1):
             m = re.search(r"\bISTAMP\((\w+)\)", src[i - 1])
             if m:
-                ph.append((cur, i, names.get(m.group(1), m.group(1))))
+                ph.append((f, cur, i, names.get(m.group(1), m.group(1))))
                 cur = i + 1
-        ph.append((cur, b, tail))
+        ph.append((f, cur, b, tail))
     return ph
 
 
 def main():
-    src = open(SRC).read().split("\n")
-    ph = phases(src)
-    kern = func_range(src, "k_decode_idx")
+    srcs = {f: open(os.path.join(CSRC, f)).read().split("\n") for f in (UNIT, PASS1)}
+    ph = phases(srcs)
+    kern = func_range(srcs[UNIT], "k_decode_idx")
 
-    def phase(line):
-        for a, b, n in ph:
-            if a <= line <= b:
+    def phase(loc):
+        for f, a, b, n in ph:
+            if f == loc[0] and a <= loc[1] <= b:
                 return n
-        return "other:%d" % line
+        return "other:%s:%d" % loc
 
     lines = open(sys.argv[1]).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_ZN6lz4ada3idx12k_decode_idxE\w*:", l))
@@ -67,8 +70,8 @@ def main():
             break
         m = re.match(r"\s*\.loc\s+\d+\s+\d+.*?;\s*(.*)$", l)
         if m:
-            chain = [int(x) for x in re.findall(r"lz4ada_idx\.hip:(\d+)", m.group(1))]
-            inner = [x for x in chain if not kern[0] <= x <= kern[1]]
+            chain = [(f, int(x)) for f, x in re.findall(r"(lz4ada_idx\w*\.\w+):(\d+)", m.group(1))]
+            inner = [c for c in chain if not (c[0] == UNIT and kern[0] <= c[1] <= kern[1])]
             cur = phase(inner[-1]) if inner else "kernel"
             continue
         s = l.strip()
